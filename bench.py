@@ -6,10 +6,14 @@ tests/golden/), 256x256 synthetic crops, B = 32 per GPU, fp32, rec+KL only (perc
 optimizer 1 skipped), VAE phase.  One process per GPU; N > 1 is launched by torch.distributed.run
 and shards the minibatch (weak scaling) with the bucketed RCCL all-reduce of generative-detection_amd/parallel.py.
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events around every launch of the dominant
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the `--steps` steps and prints the headline (`value`,
+`ms_per_step`); `--dump-outputs DIR` also writes what the last timed step computed as .npy files.  Everything else is `--full`:
+`roofline` is measured live with HIP events around every launch of the dominant
 kernel (the stride-1 3x3 convolution, forward + data-gradient: fused Winograd F(4x4,3x3); F(2x2,3x3) under ODVAE_CONV_WINOGRAD4=0,
-the direct implicit-GEMM kernel under ODVAE_CONV_WINOGRAD=0) during the timed steps;
-`cpu_baseline` times the CPU oracle (a port: the reference itself cannot be imported) on a bounded sample.
+the direct implicit-GEMM kernel under ODVAE_CONV_WINOGRAD=0) during the timed steps, `roofline_others` on one extra step, the host
+enqueue time on three more, `other_configs` in side runs of the other BASELINE.json configurations, and
+`cpu_baseline` times the CPU oracle (a port: the reference itself cannot be imported) on a bounded sample; the full record goes to
+bench_detail*.json.
 """
 import argparse
 import json
@@ -151,11 +155,21 @@ def parse():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU rehearsal of the N-rank launch path: ranks rendezvous over gloo, count themselves and run the "
                          "bucketed reducer on host tensors; no HIP kernel runs and the printed line is marked as such")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: live roofline (HIP events around the dominant kernel's launches in the timed steps, the other "
+                         "kernel families on one extra step), host enqueue time, the side runs of other configurations, the CPU baseline, "
+                         "and the full record in bench_detail*.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (losses, logged metrics, a fixed sample of the updated "
+                         "parameters and of their gradients) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short side measurements (configs[4] in bf16, the headline shape in bf16) the default run appends")
+                    help="skip the short side measurements (configs[4] in bf16, the headline shape in bf16) a --full run appends")
     ap.add_argument("--no-kernel-events", action="store_true")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def host_cores():
@@ -363,6 +377,34 @@ def timed_loop(step, first_index, steps, dev):
     return wall, host, diag
 
 
+DUMP_SAMPLE = 1 << 21   # parameters (and as many gradients) --dump-outputs writes: 8 MB each in f32, a fixed sample of the model's 88.6 M
+
+
+def dump_outputs(path, losses, model):
+    """--dump-outputs: what the last timed step computed, as float32 / float64 .npy files under `path` (~17 MB in all): `loss` (one
+    entry per optimizer of the step, what Trainer.training_batch returns), `log_<name>` (the scalars the step logged), and the same
+    DUMP_SAMPLE positions, drawn with a fixed seed over model.named_parameters() flattened in order, of the parameters after the
+    optimizer step (`params_sample`) and of the gradients the step left in `.grad` (`grads_sample`, 0 where a parameter has none)."""
+    import re
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, v):
+        a = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+    save("loss", torch.stack([l.reshape(()) for l in losses]))
+    for k, v in sorted(getattr(model, "logged_metrics", {}).items()):
+        if (torch.is_tensor(v) and v.numel() == 1) or isinstance(v, (int, float)):
+            save("log_" + re.sub(r"[^A-Za-z0-9_.-]", "_", k), v)
+    params = [p for _, p in model.named_parameters()]
+    total = sum(p.numel() for p in params)
+    idx = np.sort(np.random.default_rng(0).choice(total, size=min(DUMP_SAMPLE, total), replace=False))
+    idx = torch.from_numpy(idx).to(params[0].device)
+    with torch.no_grad():
+        save("params_sample", torch.cat([p.reshape(-1).float() for p in params])[idx])
+        save("grads_sample", torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in params])[idx])
+
+
 def side_run(dev, res, batch, steps, warmup, ckpt, precision, gan=False, force_dist=False):
     """A second, smaller measurement in the same process (one GPU): images/s of another BASELINE.json configuration, no kernel
     events.  The caching allocator is emptied first, so a run never starts inside what the previous one left reserved.  Returns the
@@ -566,13 +608,14 @@ def main():
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
-    if not args.no_kernel_events:
+    events = args.full and not args.no_kernel_events     # the live roofline: a plain run times the steps without per-launch events
+    if events:
         ops.KERNEL_EVENTS.enable()
         # A HIP timing event is a barrier packet with a release: the next kernel starts with nothing of its predecessor's tail
         # overlapped.  Around every 0.8 ms f32 conv that costs 0.3 % of the step; around every 0.29 ms bf16 conv it cost 25 %
         # (200 vs 251 images/s).  In bf16 mode one launch in eight of the dominant family is bracketed (17 per step).
         ops.KERNEL_EVENTS.sample = 8 if args.bf16 else 1
-    sample = 8 if (args.bf16 and not args.no_kernel_events) else 1   # launches / share below are scaled back by it (estimates when > 1)
+    sample = 8 if (args.bf16 and events) else 1   # launches / share below are scaled back by it (estimates when > 1)
     step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # one per step boundary, on the launch stream
     state0, alloc0, cg0 = gpu_state(dev), alloc_counters(dev), cgroup_cpu()
     gcw = GcWatch().__enter__()
@@ -581,7 +624,7 @@ def main():
     for i in range(args.steps):
         step_ev[i].record()
         host_t[i] = time.perf_counter()
-        step(args.warmup + i)
+        losses = step(args.warmup + i)
     step_ev[args.steps].record()
     host_t[args.steps] = time.perf_counter()
     host_s = host_t[args.steps] - t0      # the host has enqueued every launch of the timed steps; the GPU is still working
@@ -596,9 +639,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, model)     # before any further step changes the model
     dom_key = "conv_bf16" if args.bf16 else "conv3x3_128x128"
     mfma_peak = PEAK_BF16_MFMA_TFLOPS if args.bf16 else PEAK_F32_MFMA_TFLOPS
-    roof = ops.KERNEL_EVENTS.summary(dom_key) if not args.no_kernel_events else None
+    roof = ops.KERNEL_EVENTS.summary(dom_key) if events else None
     wino4 = False
     if roof is not None and not args.bf16:
         r4 = ops.KERNEL_EVENTS.summary("conv3x3_wino4")      # the F(4x4,3x3) kernel takes the >= 64-channel stride-1 convs: the dominant kernel
@@ -617,7 +662,7 @@ def main():
         others = {k: ops.KERNEL_EVENTS.summary(k) for k in ("conv3x3_wgrad_wino", "gemm_f32", "conv_wgrad_bf16", "conv1x1_bf16",
                                                             "flash_attn", "groupnorm")}
     ops.KERNEL_EVENTS.disable()
-    host1_ms = host_enqueue_ms(step, args.warmup + args.steps + 1) if not use_dist else None   # no events, outside the timed region
+    host1_ms = host_enqueue_ms(step, args.warmup + args.steps + 1) if args.full and not use_dist else None   # no events, outside the timed region
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -740,7 +785,7 @@ def main():
         out["peak_device_memory_gb"] = torch.cuda.max_memory_allocated(dev) / 1e9
         print("[bench] GPU leg done: %.2f images/s, %.1f ms/step" % (out["value"], ms), file=sys.stderr, flush=True)
         default_cfg = not (args.gan or args.bf16 or args.ckpt_decoder) and args.res == 256 and args.batch == 32
-        if world == 1 and default_cfg and not args.no_other_configs:
+        if world == 1 and default_cfg and args.full and not args.no_other_configs:
             # the other measured configurations of BASELINE.json, appended for the record (the headline above is untouched:
             # its model is released first, the side runs carry no events)
             del trainer, model
@@ -770,17 +815,20 @@ def main():
             except Exception:  # noqa: BLE001
                 pass
             print("[bench] side runs done", file=sys.stderr, flush=True)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # one warm-up step, then >= 3 timed steps (B=2 at 256x256: ~4.5 s each on 16 cores)
             out["cpu_baseline"] = cpu_baseline(args.res, batch=2 if args.res <= 256 else 1, steps=3 if args.res <= 256 else 1, warmup=1)
             # BASELINE.json configs[0] beside it: the reference's own CPU-runnable case (64x64, B=2, 10 steps)
             out["cpu_baseline"]["config1"] = cpu_baseline(64, batch=2, steps=10, warmup=1)
         sys.stdout.flush()
-        # the default invocation owns bench_detail.json; any other configuration writes a file of its own name (a profiling run of --gan must
-        # not overwrite the headline's record)
-        tag = "".join(t for t, on in (("_gan", args.gan), ("_bf16", args.bf16), ("_res%d" % args.res, args.res != 256), ("_b%d" % args.batch, args.batch != 32),
-                                      ("_ckpt", args.ckpt_decoder), ("_n%d" % world, world > 1), ("_dist1", args.force_dist and world == 1)) if on)
-        emit(out, json_fd, "bench_detail%s.json" % tag)
+        if not args.full:       # a plain run: the result line only, no detail record
+            os.write(json_fd, (compact_record(_json_safe(out)) + "\n").encode())
+        else:
+            # the default --full invocation owns bench_detail.json; any other configuration writes a file of its own name (a profiling run
+            # of --gan must not overwrite the headline's record)
+            tag = "".join(t for t, on in (("_gan", args.gan), ("_bf16", args.bf16), ("_res%d" % args.res, args.res != 256), ("_b%d" % args.batch, args.batch != 32),
+                                          ("_ckpt", args.ckpt_decoder), ("_n%d" % world, world > 1), ("_dist1", args.force_dist and world == 1)) if on)
+            emit(out, json_fd, "bench_detail%s.json" % tag)
     if use_dist:
         dist.destroy_process_group()
 

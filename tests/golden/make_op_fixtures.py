@@ -2,7 +2,8 @@
 
   tests/golden/ops_tiny.npz     per-op cases at tiny shapes: inputs, weights, outputs, upstream gradient, input and weight
                                 gradients of GroupNorm+swish, conv3x3 s1, Downsample conv (pad (0,1,0,1), s2), Upsample conv
-                                (nearest 2x), conv1x1, AttnBlock, ResnetBlock with a 1x1 shortcut.
+                                (nearest 2x); tests/golden/ops_tiny_blocks.npz the same for conv1x1, AttnBlock, ResnetBlock with a
+                                1x1 shortcut (two files, each under 1 MiB; load_op_fixtures() reads them as one mapping).
   tests/golden/model_ch32.npz   width-reduced model (ch=32, same ch_mult / attention / resolution), 64x64, B=2, seed 23,
                                 global_step 1: latent z, reconstruction, every scalar log term, total loss, the norm of every
                                 parameter gradient.  Weights are NOT stored: synthetic.fill_state_procedural(seed 23) derives
@@ -22,6 +23,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 GOLD = os.path.join(ROOT, "tests", "golden")
 YAML = os.path.join(GOLD, "autoencoder_kl_16x16x16.yaml")
+
+
+OPS_FILES = {"ops_tiny.npz": ("gn_swish", "conv3x3", "downsample", "upsample"), "ops_tiny_blocks.npz": ("conv1x1", "attn", "resblock")}
+
+
+def load_op_fixtures():
+    """The committed per-op cases of both OPS_FILES as one {name: array} mapping."""
+    out = {}
+    for f in OPS_FILES:
+        with np.load(os.path.join(GOLD, f)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def _rand(g, *shape, scale=1.0):
@@ -124,7 +137,9 @@ def model_case():
 
 if __name__ == "__main__":
     torch.set_num_threads(min(8, os.cpu_count() or 1))
-    np.savez_compressed(os.path.join(GOLD, "ops_tiny.npz"), **op_cases())
+    cases = op_cases()
+    for f, ops in OPS_FILES.items():
+        np.savez_compressed(os.path.join(GOLD, f), **{k: v for k, v in cases.items() if k.split(".")[0] in ops})
     np.savez_compressed(os.path.join(GOLD, "model_ch32.npz"), **model_case())
-    for f in ("ops_tiny.npz", "model_ch32.npz"):
+    for f in list(OPS_FILES) + ["model_ch32.npz"]:
         print(f, os.path.getsize(os.path.join(GOLD, f)) // 1024, "KiB")

@@ -1,4 +1,6 @@
 """Host logic: the reference's target:/params: config surface, learning-rate rule and module tree (CPU only)."""
+import hashlib
+import json
 import os
 
 import pytest
@@ -6,13 +8,14 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 YAML = os.path.join(ROOT, "tests", "golden", "autoencoder_kl_16x16x16.yaml")
-REF_YAML = "/root/reference/configs/autoencoder/pose/autoencoder_kl_16x16x16.yaml"
+REF_DIGEST = os.path.join(ROOT, "tests", "golden", "reference_config.json")   # size and SHA-256 of the reference's own yaml
 
 
 def test_yaml_fixture_is_the_untouched_reference_config():
-    if not os.path.exists(REF_YAML):
-        pytest.skip("reference not mounted")
-    assert open(YAML).read() == open(REF_YAML).read()
+    ref = json.load(open(REF_DIGEST))
+    data = open(YAML, "rb").read()
+    assert ref["file"].endswith(os.path.basename(YAML))
+    assert len(data) == ref["bytes"] and hashlib.sha256(data).hexdigest() == ref["sha256"]
 
 
 def test_config_load_merge_dotlist():

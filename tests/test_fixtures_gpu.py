@@ -1,4 +1,4 @@
-"""HIP path vs the COMMITTED fixtures of SURVEY.md 8(c) (tests/golden/ops_tiny.npz, model_ch32.npz; generator
+"""HIP path vs the COMMITTED fixtures of SURVEY.md 8(c) (tests/golden/ops_tiny*.npz, model_ch32.npz; generator
 tests/golden/make_op_fixtures.py): no live oracle on the GPU box, only numbers in the repo.  Tolerances as in
 test_ops_gpu.py / test_model_gpu.py: per-op forward 2e-4, backward 5e-4 of max|ref|; model-level 1e-3 / 5e-3."""
 import os
@@ -25,7 +25,11 @@ def close(a, b, tol, what):
 
 @pytest.fixture(scope="module")
 def ops_fix():
-    return np.load(os.path.join(GOLD, "ops_tiny.npz"))
+    out = {}
+    for f in ("ops_tiny.npz", "ops_tiny_blocks.npz"):    # one set of per-op cases in two files (make_op_fixtures.OPS_FILES)
+        with np.load(os.path.join(GOLD, f)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def _t(a, grad=False):

@@ -58,7 +58,11 @@ def test_full_pose_encoder_matches_reference_module(impl):
     assert np.allclose(z.grad.numpy(), g["dz"], rtol=1e-5, atol=1e-7)
     for k, p in net.named_parameters():
         assert abs(p.grad.double().norm().item() - float(g["gnorm." + k])) <= 1e-5 * float(g["gnorm." + k]), k
-        assert np.allclose(p.grad.reshape(-1)[:64].numpy(), g["ghead." + k], rtol=1e-5, atol=1e-8), k
+        # 1e-5 of each entry and of the head's largest entry: a weight gradient is an f32 sum over 256 positions x batch whose order
+        # depends on the host's BLAS kernel and thread count; near-cancelling entries then move by ~1e-6 of the head's scale (an
+        # exact float64 evaluation differs from the fixture by as much), which a bound on the entry alone cannot absorb
+        head = g["ghead." + k]
+        assert np.allclose(p.grad.reshape(-1)[:64].numpy(), head, rtol=1e-5, atol=1e-5 * float(np.abs(head).max())), k
 
 
 def test_oracle_reproduces_config1_goldens():
@@ -99,9 +103,10 @@ def _load_gen():
 
 def test_oracle_reproduces_op_fixtures():
     """the committed per-op vectors are what the oracle's torch-CPU ops give today."""
-    g = np.load(os.path.join(GOLD, "ops_tiny.npz"))
-    now = _load_gen().op_cases()
-    assert set(now.keys()) == set(g.files)
+    gen = _load_gen()
+    g = gen.load_op_fixtures()
+    now = gen.op_cases()
+    assert set(now.keys()) == set(g.keys())
     for k, v in now.items():
         assert np.allclose(v, g[k], rtol=1e-4, atol=1e-5), k
 

@@ -7,7 +7,7 @@ out=$1; shift
 cd /tmp && export TMPDIR=/tmp
 for ctr in FETCH_SIZE WRITE_SIZE; do
   d=/tmp/pmc_fam_$ctr; rm -rf $d
-  rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $d -o p -- python3 $root/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-events --no-other-configs > /dev/null 2> /tmp/pmc_fam_$ctr.err
+  rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $d -o p -- python3 $root/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-events --no-other-configs > /dev/null 2> /tmp/pmc_fam_$ctr.err
 done
 python3 - "$out" "$@" <<'PY'
 import csv, glob, json, sys
@@ -34,7 +34,7 @@ for k in kernels:
               "duration_ms_total_under_counters": sum(dv) / 1e6 if dv else None,
               "hbm_TB_per_s": (fb + wb) / (sum(dv) * 1e-9) / 1e12 if dv else None}
 steps = sum(len(v) for name, v in dur.items() if "adam_kernel" in name)      # one Adam launch per training step of this configuration
-json.dump({"method": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) -- python bench.py --steps 1 --warmup 1 "
+json.dump({"method": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) -- python bench.py --full --steps 1 --warmup 1 "
                      "--no-kernel-events (warm-up + timed + the three host-enqueue steps: every step of the process is counted, "
                      "steps_counted = launches of adam_kernel); FETCH_SIZE x2 (gfx950 wide-read correction), KiB -> bytes; durations from the FETCH_SIZE pass",
            "steps_counted": steps, "kernels": res}, open(out, "w"), indent=1)
