@@ -861,10 +861,17 @@ class _AttentionRecompute(Function):
         return dqkv, None
 
 
+# Fused f32 attention (flash_attn_f32.hip, _FlashAttentionF32): no T x T tensor in HBM, 7 products per backward instead of the GEMM
+# path's 4 (5 past the score budget).  ODVAE_ATTN_F32_FUSED=1 turns it on for supported shapes; off, the dispatch below is unchanged.
+ATTN_F32_FUSED = os.environ.get("ODVAE_ATTN_F32_FUSED", "0") == "1"
+
+
 def attention_qkv(qkv):
     if qkv.dtype == BF16:
         return _FlashAttention.apply(qkv)
     n, c3, h, w = qkv.shape
+    if ATTN_F32_FUSED and qkv.dtype == torch.float32 and _L().odvae_flash_attn_f32_supported(n, h * w, c3 // 3):
+        return _FlashAttentionF32.apply(qkv)
     per_image = (h * w) ** 2 * 4
     if n * per_image > ATTN_SCORE_BUDGET:
         return _AttentionRecompute.apply(qkv, max(1, ATTN_SCORE_BUDGET // per_image))
@@ -1766,6 +1773,51 @@ class _FlashAttention(Function):
                                                dqkv.data_ptr(), delta.data_ptr(), _lib.stream_ptr()), "flash_attn_bwd")
         # algorithmic: the five products of the backward (S, dP, dV, dK, dQ); issued: seven (S and dP are formed in both kernels)
         KERNEL_EVENTS.end("flash_attn", 10.0 * t * t * c * n, tag, 2.0 * n * t * 8 * c, issued=14.0 * t * t * c * n)
+        return dqkv
+
+
+def _aligned_cl(t):
+    """_cl(t) with a 16-byte aligned base (the fused f32 kernels load float4 rows)."""
+    t = _cl(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=CL)
+
+
+class _FlashAttentionF32(Function):
+    """softmax(q k^T C^-1/2) v from the packed f32 projection [N, 3C, H, W] with the T x T scores on the CU (flash_attn_f32.hip);
+    only qkv, o and the per-row base-2 log-sum-exp are kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, qkv):
+        L = _L()
+        qkv = _aligned_cl(qkv)
+        n, c3, h, w = qkv.shape
+        c, t = c3 // 3, h * w
+        if not L.odvae_flash_attn_f32_supported(n, t, c):
+            raise _lib.HipLibraryError("flash attention f32: unsupported shape N=%d T=%d C=%d" % (n, t, c))
+        o = _new_cl(n, c, h, w, qkv)
+        lse = torch.empty(n, t, dtype=torch.float32, device=qkv.device)
+        tag = KERNEL_EVENTS.begin(secondary=True)
+        _lib.check(L.odvae_flash_attn_fwd_f32(qkv.data_ptr(), n, t, c, float(c) ** -0.5, o.data_ptr(), lse.data_ptr(), _lib.stream_ptr()),
+                   "flash_attn_fwd_f32")
+        KERNEL_EVENTS.end("flash_attn", 4.0 * t * t * c * n, tag, 4.0 * n * t * 4 * c)
+        ctx.save_for_backward(qkv, o, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        L = _L()
+        qkv, o, lse = ctx.saved_tensors
+        do = _aligned_cl(do)
+        n, c3, h, w = qkv.shape
+        c, t = c3 // 3, h * w
+        dqkv = _new_cl(n, c3, h, w, qkv)
+        delta = torch.empty(n * t, dtype=torch.float32, device=qkv.device)
+        tag = KERNEL_EVENTS.begin(secondary=True)
+        _lib.check(L.odvae_flash_attn_bwd_f32(qkv.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), n, t, c, float(c) ** -0.5,
+                                              dqkv.data_ptr(), delta.data_ptr(), _lib.stream_ptr()), "flash_attn_bwd_f32")
+        # algorithmic: the five products of the backward; issued: seven (S and dP are formed in both kernels; C = 512: eight, the
+        # dK and dV launches each form S)
+        KERNEL_EVENTS.end("flash_attn", 10.0 * t * t * c * n, tag, 4.0 * n * t * 8 * c, issued=(16.0 if c == 512 else 14.0) * t * t * c * n)
         return dqkv
 
 

@@ -360,6 +360,13 @@ int odvae_flash_attn_fwd_bf16(const void* qkv, int N, int T, int C, float scale,
 /* dqkv [N][T][3C] from d_o, o, lse2; delta_ws f32 [N*T] scratch */
 int odvae_flash_attn_bwd_bf16(const void* qkv, const void* o, const void* d_o, const float* lse2, int N, int T, int C, float scale,
                               void* dqkv, float* delta_ws, void* stream);
+/* ---- flash_attn_f32.hip: the same fused attention on f32 operands (exact-f32 MFMA); scores never in HBM ---------------------- */
+int odvae_flash_attn_f32_supported(int N, int T, int C);   /* pure host query: N in 1..65535, T >= 1, C in 64/128/256/512 */
+/* qkv f32 [N][T][3C] (q | k | v) -> o f32 [N][T][C], lse2 f32 [N][T] = log2 sum_j exp(score_ij * scale) */
+int odvae_flash_attn_fwd_f32(const float* qkv, int N, int T, int C, float scale, float* o, float* lse2, void* stream);
+/* dqkv f32 [N][T][3C] from d_o, o, lse2; delta f32 [N*T] receives rowsum(d_o * o).  No atomics: bit-reproducible */
+int odvae_flash_attn_bwd_f32(const float* qkv, const float* o, const float* d_o, const float* lse2, int N, int T, int C, float scale,
+                             float* dqkv, float* delta, void* stream);
 /* ---- bf16_ops.hip: GroupNorm(32, eps 1e-6) + swish with bf16 activations / f32 statistics, dtype hand-offs ---------------------- */
 size_t odvae_groupnorm_bf16_workspace_bytes(int N, int HW, int C, int G);
 int odvae_groupnorm_fwd_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
