@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import anomaly
 from . import lib as _lib
 from . import ops
 from .distributions import DiagonalGaussianDistribution
@@ -115,6 +116,7 @@ class LPIPSWithDiscriminator(nn.Module):
 
     def adaptive_weight_one_pass(self, nll_loss, g_loss, reconstructions, last_layer):
         """(d_weight, g_nll, g_g): the adaptive weight of calculate_adaptive_weight and the two gradients w.r.t. the reconstruction."""
+        anomaly.watch((nll_loss, g_loss))      # torch's anomaly mode checks these backward passes too (no-op when it is off)
         g_nll = torch.autograd.grad(nll_loss, reconstructions, retain_graph=True)[0]
         g_g = torch.autograd.grad(g_loss, reconstructions, retain_graph=True)[0]
         with ops.weight_gradient_only():      # (needs_input_grad is fixed at forward time: without this each probe also runs conv_out's data gradient)
@@ -127,6 +129,7 @@ class LPIPSWithDiscriminator(nn.Module):
     def calculate_adaptive_weight(self, nll_loss, g_loss, last_layer=None):
         if last_layer is None:
             last_layer = self.last_layer[0]
+        anomaly.watch((nll_loss, g_loss))
         nll_grads = torch.autograd.grad(nll_loss, last_layer, retain_graph=True)[0]
         g_grads = torch.autograd.grad(g_loss, last_layer, retain_graph=True)[0]
         d_weight = torch.norm(nll_grads) / (torch.norm(g_grads) + 1e-4)

@@ -38,6 +38,13 @@ def parse(argv):
     return ap.parse_known_args(argv)
 
 
+def trainer_kwargs(trainer_cfg):
+    """The `lightning.trainer` keys of the yaml this Trainer honours: gradient_clip_val, precision and detect_anomaly (yaml:138; absent
+    = None, which leaves the choice to ODVAE_DETECT_ANOMALY)."""
+    return {"gradient_clip_val": trainer_cfg.get("gradient_clip_val", None), "precision": trainer_cfg.get("precision", None),
+            "detect_anomaly": trainer_cfg.get("detect_anomaly", None)}
+
+
 def main(argv=None):
     opt, unknown = parse(sys.argv[1:] if argv is None else argv)
     seed_everything(opt.seed)
@@ -63,8 +70,7 @@ def main(argv=None):
         logger = _Logger()
         for name, cb_cfg in lightning.get("callbacks", Config.create()).items():
             callbacks.append(instantiate_from_config(cb_cfg))
-    trainer = Trainer(model, gradient_clip_val=trainer_cfg.get("gradient_clip_val", None), precision=trainer_cfg.get("precision", None),
-                      callbacks=callbacks, logger=logger)
+    trainer = Trainer(model, callbacks=callbacks, logger=logger, **trainer_kwargs(trainer_cfg))
     bs = config.data.params.batch_size
     for step in range(opt.steps):
         batch = synthetic.make_batch(bs, opt.height, seed=opt.seed + step)

@@ -12,6 +12,8 @@ import os
 
 import torch
 
+from . import anomaly
+from .anomaly import AnomalyError  # noqa: F401  (raised by training_batch; importable from here)
 from .parallel import GradReducer
 
 
@@ -28,7 +30,8 @@ class _TrainerHandle:
 
 class Trainer:
     def __init__(self, model, gradient_clip_val=None, optimizer_indices=(0, 1), process_group=None, bucket_mb=None, precision=None,
-                 distributed=None, comm_dtype=None, callbacks=(), logger=None, comm_f32_accumulate=False):
+                 distributed=None, comm_dtype=None, callbacks=(), logger=None, comm_f32_accumulate=False,
+                 detect_anomaly=None):
         """optimizer_indices: which of the model's optimizers run each batch; (0,) is the "rec+KL only" benchmark
         configuration (discriminator off, optimizer 1 skipped -- SURVEY.md 8(d)).
         comm_dtype: dtype of the gradient buckets on the wire; None = f32 in every precision -- what the reference's `strategy: ddp`
@@ -37,7 +40,11 @@ class Trainer:
         bucket_mb: f32 megabytes of gradient arena per all-reduce; None = 32, or 16 with bf16 buckets (8 MB on the wire: ~18
         collectives inside the bf16 step's ~50 ms backward).
         distributed: None = data-parallel exactly when a process group is given or the default group has more than one rank
-        (what `strategy: ddp` amounts to, yaml:137); False = never (a single-process reference run inside a rank)."""
+        (what `strategy: ddp` amounts to, yaml:137); False = never (a single-process reference run inside a rank).
+        detect_anomaly: lightning.trainer.detect_anomaly of the yaml (:138).  False = off; True or "nan" = torch's anomaly mode semantics
+        (the first backward node that returns a NaN output raises AnomalyError before clipping and the optimizer step); "nonfinite" also
+        flags +-Inf; None reads ODVAE_DETECT_ANOMALY (unset / 0 = off, 1 = nan, nonfinite).  The checks run on the device
+        (anomaly.py): one host wait per optimizer step."""
         self.model = model
         # callbacks: objects with the pytorch_lightning.Callback hooks used by the reference's yaml (callbacks.ImageLogger, ...);
         # `on_train_batch_end` runs after the last optimizer step of a batch, as under PL's automatic optimisation.  logger: anything
@@ -51,6 +58,8 @@ class Trainer:
         if precision is not None:   # lightning.trainer.precision of the yaml (:139): 32 or "bf16"
             model.set_precision(precision)
         self.clip = gradient_clip_val
+        self.detect_anomaly = anomaly.parse_mode(detect_anomaly)
+        self.anomaly = anomaly.Detector(self.detect_anomaly, model) if self.detect_anomaly else None
         self.optimizer_indices = tuple(optimizer_indices)
         opts, _ = model.configure_optimizers()
         self.optimizers = opts
@@ -102,16 +111,26 @@ class Trainer:
         for idx in self.optimizer_indices:
             opt = self.optimizers[idx]
             saved = self._toggle(idx)
+            an = self.anomaly
             try:
+                if an is not None:
+                    an.begin(_device_of(model))      # before training_step: PoseLoss's torch.autograd.grad passes are checked too
                 loss = model.training_step(batch, batch_idx, idx)
                 opt.zero_grad(set_to_none=True)   # FusedAdam: gradients are gathered into its arena after the backward (optim.gather_grads)
                 red = self.reducers[idx] if self.reducers else None
                 if red is not None:
                     red.prepare_for_backward()
-                    (loss * red.inv_world).backward()   # sum over ranks of grad(loss / world) = DDP's mean gradient
+                    root = loss * red.inv_world         # sum over ranks of grad(loss / world) = DDP's mean gradient
+                    if an is not None:
+                        an.watch(root)
+                    root.backward()
                     red.finish()
                 else:
+                    if an is not None:
+                        an.watch(loss)
                     loss.backward()
+                if an is not None:
+                    self._check_anomaly(an, idx, red)
                 if self.clip:
                     if hasattr(opt, "clip_grad_norm_"):
                         opt.clip_grad_norm_(self.clip)
@@ -120,11 +139,29 @@ class Trainer:
                 opt.step()
             finally:
                 self._untoggle(saved)
+                if an is not None:
+                    an.end()
             model._global_step += 1
             losses.append(loss.detach())
         for cb in self.callbacks:
             cb.on_train_batch_end(self, model, losses, batch, batch_idx)
         return losses
+
+    def _check_anomaly(self, an, idx, red):
+        """One host wait for the phase's anomaly record (all-reduced MIN over the ranks when data-parallel, so every rank raises);
+        AnomalyError before clip / step / the global_step increment: no parameter, moment or step count takes in the bad step."""
+        group = None
+        if red is not None:
+            import torch.distributed as dist
+            group = red.group if red.group is not None else dist.group.WORLD
+        found = an.check(group)
+        if found is None:
+            return
+        name, index, module = found
+        rank, world = _rank(), _world()
+        gs = int(self.model.global_step)
+        raise AnomalyError("%s (optimizer %d, global_step %d, rank %d of %d)" % (an.message(name, index, module), idx, gs, rank, world),
+                           node=name, output_index=index, module=module, optimizer_idx=idx, global_step=gs, rank=rank)
 
     def check_device_health(self, where=""):
         """Reads the library's two device-side counters (odvae_device_health: one device synchronisation, so it is called only where the
@@ -309,6 +346,17 @@ def _batch_size(batch):
             if isinstance(v, (dict, list, tuple)) and any(torch.is_tensor(x) for x in (v.values() if isinstance(v, dict) else v)):
                 return _batch_size(v)
     return 1
+
+
+def _device_of(model):
+    for p in model.parameters():
+        return p.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _world():
+    import torch.distributed as dist
+    return dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
 
 
 def _rank():

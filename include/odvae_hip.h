@@ -386,6 +386,17 @@ size_t odvae_colsum_bf16_workspace_bytes(int64_t rows, int C);
 /* out f32 [C] = column sums of x bf16 [rows][C] (bias gradients) */
 int odvae_colsum_bf16(const void* x, int64_t rows, int C, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- anomaly.hip: the NaN check torch.autograd.set_detect_anomaly(True) makes on every backward output, on the device ----------
+ * One launch scans up to 8 outputs of one backward node (any dense layout: ptr = lowest element, numel elements).  dtype 0 f32, 1 bf16;
+ * mode 0 flags NaN (either sign, quiet or signalling), mode 1 also +-Inf.  A hit does one atomic min of
+ * (node_seq << 20) | output_index on *record, so it holds the earliest node and its lowest offending output; clean data leaves it
+ * untouched.  odvae_anomaly_reset sets it to ODVAE_ANOMALY_CLEAN.  The descriptors are read on the host and passed in the kernel
+ * arguments: the array may be freed when the call returns. */
+#define ODVAE_ANOMALY_CLEAN 0x7fffffffffffffffull
+typedef struct { const void* ptr; int64_t numel; int32_t dtype; int32_t output_index; } OdvaeAnomalyTensor;
+int odvae_anomaly_scan(const OdvaeAnomalyTensor* tensors /* host */, int n, int64_t node_seq, int mode, uint64_t* record, void* stream);
+int odvae_anomaly_reset(uint64_t* record, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
