@@ -15,7 +15,6 @@ HIP_SOURCES = ["gemm_f32.hip", "conv3x3_f32.hip", "conv3x3_wino_f32.hip", "conv3
 CXX_SOURCES = ["runtime.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", CSRC]
-FLAGS += os.environ.get("ODVAE_EXTRA_HIPCC_FLAGS", "").split()   # diagnostic builds (-DODVAE_STAMPS, ...); use with force=True
 # Per-file code-generation switches (none in use).  Tried on flash_attn_bf16.hip: `-mllvm -amdgpu-mfma-vgpr-form=1` removes the
 # 256 v_accvgpr_read/write per 32 MFMAs that hipcc's default register split puts at the loop back-edge of the attention kernels
 # (592 vs 565 TFLOP/s forward), but the D >= 256 forward kernels then return wrong results (tests/test_bf16_gpu.py), so it stays off.

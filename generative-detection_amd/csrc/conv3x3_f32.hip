@@ -7,18 +7,16 @@
 //   data-gradient of MODE 1 (stride-2 transposed conv)               -> MODE 3
 //   Upsample + conv by output parity class (four 2x2-tap convs on the low-res input, pre-summed weights:
 //   16 instead of 36 tap-products per input pixel)                   -> MODE 5;  its data gradient, a 4x4-tap
-//   stride-2 pad-1 conv over dy with pre-summed weights             -> MODE 6   (v2 kernel only)
+//   stride-2 pad-1 conv over dy with pre-summed weights             -> MODE 6
 // reached from src/modules/autoencodermodules/feat_encoder.py:4, feat_decoder.py:4 of the reference.
 // The data-gradient of MODE 0 is MODE 0 itself on weights packed with flipped taps and swapped
 // channel roles (odvae_conv3x3_pack_f32 makes both packs).
 //
 // Implicit GEMM: M = output pixels (block tile = 8x16 patch = 128 px), N = Cout, K = 9 taps x Cin.
 // Per chunk of KC input channels the block stages the input halo patch once ([halo px][KC] in LDS,
-// reused by all 9 taps) and streams the 9 per-tap weight slices [KC/4][BN][4] through a 2-deep LDS
-// ring (loads for tap t+1 are issued into registers before tap t's MFMAs, written after them).
-// A and B fragments are ds_read_b128: four k-steps per read, k order (8g + 4*half + j) on both.
+// reused by all 9 taps).  A fragments are ds_read_b128 from it, B fragments 16-byte loads from the
+// weight pack: four k-steps per read, k order (8g + 4*half + j) on both.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -43,14 +41,12 @@ template <> struct Halo<3> { static constexpr int H = TH / 2 + 1, W = TW / 2 + 1
 template <> struct Halo<5> { static constexpr int H = TH + 2, W = TW + 2; };          // tile = low-res pixels
 template <> struct Halo<6> { static constexpr int H = 2 * TH + 2, W = 2 * TW + 2; };  // halo over dy at 2x resolution
 
-// halo pixel index for output pixel (r,c) of the tile and tap (kh,kw); ok=false -> operand is zero
+// halo pixel index for output pixel (r,c) of the tile and tap (kh,kw)
 template <int MODE>
-__device__ __forceinline__ int halo_index(int r, int c, int kh, int kw, bool& ok) {
-  ok = true;
+__device__ __forceinline__ int halo_index(int r, int c, int kh, int kw) {
   if (MODE == 0) return (r + kh) * Halo<0>::W + (c + kw);
   if (MODE == 1) return (2 * r + kh) * Halo<1>::W + (2 * c + kw);
   if (MODE == 2) return ((r + kh + 1) >> 1) * Halo<2>::W + ((c + kw + 1) >> 1);
-  ok = (((r + kh) | (c + kw)) & 1) == 0;
   return ((r + kh) >> 1) * Halo<3>::W + ((c + kw) >> 1);
 }
 
@@ -64,181 +60,13 @@ __device__ __forceinline__ void halo_origin(int oy0, int ox0, int& iy0, int& ix0
   else { iy0 = oy0 / 2 - 1; ix0 = ox0 / 2 - 1; }
 }
 
-// WMT x WNT MFMA tiles per wave, WAVES_M x WAVES_N waves (4 waves; WAVES_M*WMT = 4 M-tiles of 32 px)
-template <int MODE, int KC, int WMT, int WNT, int WAVES_M, int WAVES_N>
-__global__ __launch_bounds__(256) void conv3x3_kernel(ConvParams p) {
-  static_assert(WAVES_M * WAVES_N == 4 && WAVES_M * WMT == 4, "tile layout");
-  constexpr int BN = WAVES_N * WNT * 32;
-  constexpr int HS = KC + 4;                          // halo row stride (floats)
-  constexpr int HPIX = Halo<MODE>::H * Halo<MODE>::W;
-  constexpr int QC = KC / 4;                          // channel quads per chunk
-  constexpr int HALO_F4 = HPIX * QC;                  // float4 per halo stage
-  constexpr int HALO_IT = (HALO_F4 + 255) / 256;
-  constexpr int W_F4 = QC * BN;                       // float4 per tap slice
-  constexpr int W_IT = (W_F4 + 255) / 256;
-  __shared__ __attribute__((aligned(16))) float smem[HPIX * HS + 2 * W_F4 * 4];
-  float* Hs = smem;
-  float* Ws = smem + HPIX * HS;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-  const int li = lane & 31, h = lane >> 5;
-
-  int t = blockIdx.x;
-  const int tx = t % p.tiles_x; t /= p.tiles_x;
-  const int ty = t % p.tiles_y; const int n = t / p.tiles_y;
-  const int oy0 = ty * TH, ox0 = tx * TW;
-  const int n0 = blockIdx.y * BN;
-  int iy0, ix0;
-  halo_origin<MODE>(oy0, ox0, iy0, ix0);
-  const float* xn = p.x + (int64_t)n * p.Hi * p.Wi * p.Cin;
-  const bool vec = (p.Cin & 3) == 0;
-
-  f32x16 acc[WMT][WNT];
-#pragma unroll
-  for (int a = 0; a < WMT; ++a)
-#pragma unroll
-    for (int b = 0; b < WNT; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-  float4 hreg[HALO_IT], wreg[W_IT];
-
-  auto load_halo = [&](int c0) {
-#pragma unroll
-    for (int i = 0; i < HALO_IT; ++i) {
-      const int f = tid + 256 * i;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (f < HALO_F4) {
-        const int hp = f / QC, q = f % QC;
-        const int iy = iy0 + hp / Halo<MODE>::W, ix = ix0 + hp % Halo<MODE>::W;
-        const int c = c0 + 4 * q;
-        if (iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi && c < p.Cin) {
-          const float* src = xn + ((int64_t)iy * p.Wi + ix) * p.Cin + c;
-          if (vec) v = *reinterpret_cast<const float4*>(src);
-          else {
-            v.x = src[0];
-            if (c + 1 < p.Cin) v.y = src[1];
-            if (c + 2 < p.Cin) v.z = src[2];
-            if (c + 3 < p.Cin) v.w = src[3];
-          }
-        }
-      }
-      hreg[i] = v;
-    }
-  };
-  auto store_halo = [&]() {
-#pragma unroll
-    for (int i = 0; i < HALO_IT; ++i) {
-      const int f = tid + 256 * i;
-      if (f < HALO_F4) *reinterpret_cast<float4*>(Hs + (f / QC) * HS + 4 * (f % QC)) = hreg[i];
-    }
-  };
-  auto load_w = [&](int c0, int tap) {
-    const float* src = p.wpk + ((int64_t)tap * (p.CinP / 4) + c0 / 4) * p.CoutP * 4;
-#pragma unroll
-    for (int i = 0; i < W_IT; ++i) {
-      const int f = tid + 256 * i;
-      if (f < W_F4) {
-        const int q = f / BN, nn = f % BN;
-        wreg[i] = *reinterpret_cast<const float4*>(src + ((int64_t)q * p.CoutP + n0 + nn) * 4);
-      }
-    }
-  };
-  auto store_w = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < W_IT; ++i) {
-      const int f = tid + 256 * i;
-      if (f < W_F4) *reinterpret_cast<float4*>(Ws + (buf * W_F4 + f) * 4) = wreg[i];
-    }
-  };
-
-  const int nchunks = p.CinP / KC;
-  load_halo(0);
-  load_w(0, 0);
-  for (int ch = 0; ch < nchunks; ++ch) {
-    store_halo();
-#pragma unroll 1
-    for (int tap = 0; tap < 9; ++tap) {
-      store_w(tap & 1);
-      __syncthreads();
-      // prefetch the next weight slice (and, near the end of the chunk, the next halo)
-      if (tap < 8) load_w(ch * KC, tap + 1);
-      else if (ch + 1 < nchunks) load_w((ch + 1) * KC, 0);
-      if (tap == 7 && ch + 1 < nchunks) load_halo((ch + 1) * KC);
-
-      const int kh = tap / 3, kw = tap % 3;
-      int aoff[WMT]; bool aok[WMT];
-#pragma unroll
-      for (int mt = 0; mt < WMT; ++mt) {
-        const int pm = (wm * WMT + mt) * 32 + li;
-        aoff[mt] = halo_index<MODE>(pm / TW, pm % TW, kh, kw, aok[mt]) * HS + 4 * h;
-      }
-      const float* Wb = Ws + (tap & 1) * W_F4 * 4;
-#pragma unroll
-      for (int g = 0; g < KC / 8; ++g) {
-        float4 a[WMT], b[WNT];
-#pragma unroll
-        for (int mt = 0; mt < WMT; ++mt) {
-          a[mt] = *reinterpret_cast<const float4*>(Hs + aoff[mt] + g * 8);
-          if (MODE == 3 && !aok[mt]) a[mt] = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int nt = 0; nt < WNT; ++nt)
-          b[nt] = *reinterpret_cast<const float4*>(Wb + ((g * 2 + h) * BN + (wn * WNT + nt) * 32 + li) * 4);
-#pragma unroll
-        for (int mt = 0; mt < WMT; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < WNT; ++nt) {
-            acc[mt][nt] = mfma32(a[mt].x, b[nt].x, acc[mt][nt]);
-            acc[mt][nt] = mfma32(a[mt].y, b[nt].y, acc[mt][nt]);
-            acc[mt][nt] = mfma32(a[mt].z, b[nt].z, acc[mt][nt]);
-            acc[mt][nt] = mfma32(a[mt].w, b[nt].w, acc[mt][nt]);
-          }
-      }
-    }
-    __syncthreads();  // every wave is done with this chunk's halo before it is overwritten
-  }
-
-  // epilogue: lane = output channel, registers = pixels
-  float* yn = p.y + (int64_t)n * p.Ho * p.Wo * p.Cout;
-  const float* rn = p.residual ? p.residual + (int64_t)n * p.Ho * p.Wo * p.Cout : nullptr;
-#pragma unroll
-  for (int nt = 0; nt < WNT; ++nt) {
-    const int co = n0 + (wn * WNT + nt) * 32 + li;
-    if (co >= p.Cout) continue;
-    const float bv = p.bias ? p.bias[co] : 0.f;
-#pragma unroll
-    for (int mt = 0; mt < WMT; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int pm = (wm * WMT + mt) * 32 + acc_row(r, lane);
-        const int oy = oy0 + pm / TW, ox = ox0 + pm % TW;
-        if (oy < p.Ho && ox < p.Wo) {
-          const int64_t o = ((int64_t)oy * p.Wo + ox) * p.Cout + co;
-          float v = acc[mt][nt][r] + bv;
-          if (rn) v += rn[o];
-          if (p.act) v = fmaxf(v, 0.f);
-          yn[o] = v;
-        }
-      }
-    }
-  }
-}
-
-#ifdef ODVAE_STAMPS
-// Diagnostic build only (tools/conv_stamps.py): s_memtime stamps of the v2 kernel's phases, per wave, for the
-// first 4096 blocks.  Never compiled into libodvae_hip.so.
-__device__ unsigned long long g_stamps[4096 * 4 * 4];
-#define ODVAE_T() __builtin_amdgcn_s_memtime()
-#endif
-
-// ---- v2 main loop ------------------------------------------------------------------------------------
-// Same tiling and epilogue, different feeding: weight fragments go global/L2 -> registers directly (the pack
-// layout makes one coalesced 16-byte load per lane a whole B fragment for four k-steps; prefetched one k-group
-// = 16 MFMAs ahead), so LDS holds only the input halo, double-buffered per KC-channel chunk.  One
-// __syncthreads() per chunk (9*KC/8*16 = 576 MFMAs per wave at KC = 32) instead of one per tap (32 MFMAs):
-// rocprof PMC on v1 showed 39 % of wave cycles parked at the per-tap barrier / waitcnt with 3 blocks per CU.
+// ---- main loop ---------------------------------------------------------------------------------------
+// WMT x WNT MFMA tiles per wave, WAVES_M x WAVES_N waves (4 waves; WAVES_M*WMT = 4 M-tiles of 32 px).
+// Weight fragments go global/L2 -> registers directly (the pack layout makes one coalesced 16-byte load per lane
+// a whole B fragment for four k-steps; prefetched one k-group = 16 MFMAs ahead), so LDS holds only the input
+// halo, double-buffered per KC-channel chunk.  One __syncthreads() per chunk (9*KC/8*16 = 576 MFMAs per wave at
+// KC = 32) instead of one per tap (32 MFMAs): rocprof PMC on a per-tap-barrier form showed 39 % of wave cycles
+// parked at that barrier / waitcnt with 3 blocks per CU (profiles/r01_conv3x3_pmc.md).
 template <int MODE, int KC, int WMT, int WNT, int WAVES_M, int WAVES_N, int MINW = 1>
 __global__ __launch_bounds__(256, MINW) void conv3x3_kernel_v2(ConvParams p) {
   static_assert(WAVES_M * WAVES_N == 4 && WAVES_M * WMT == 4, "tile layout");
@@ -407,15 +235,11 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_kernel_v2(ConvParams p) {
       int hp;
       if (MODE == 5) hp = (pr + py + tap / KW) * Halo<5>::W + (pc + px + tap % KW);
       else if (MODE == 6) hp = (2 * pr + tap / KW) * Halo<6>::W + (2 * pc + tap % KW);
-      else { bool ok; hp = halo_index<(MODE <= 3 ? MODE : 0)>(pr, pc, tap / 3, tap % 3, ok); }
+      else hp = halo_index<(MODE <= 3 ? MODE : 0)>(pr, pc, tap / 3, tap % 3);
       const int off = hp * HS + 4 * h + 8 * g;
       a[mt] = *reinterpret_cast<const float4*>(Hs + off);   // MODE 3: dead taps read a harmless in-range pixel
     }
   };
-#ifdef ODVAE_STAMPS
-  const unsigned long long st_start = ODVAE_T();
-  unsigned long long st_bar = 0;
-#endif
   // weight fragments run TWO steps ahead (L2 latency under load exceeds one 16-MFMA step); bn2 is the far slot
   float4 bn2[WNT];
   auto load_b_step = [&](int ch, int it, bool valid, float4 (&b)[WNT]) {   // step `it` may spill into chunk ch+1
@@ -427,9 +251,6 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_kernel_v2(ConvParams p) {
   load_b(0, 1 / NG, 1 % NG, bn);
   store_halo(smem);
   __syncthreads();
-#ifdef ODVAE_STAMPS
-  const unsigned long long st_loop = ODVAE_T();
-#endif
 
   for (int ch = 0; ch < nchunks; ++ch) {
     const float* Hs = smem + (ch & 1) * HPIX * HS;
@@ -461,18 +282,9 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_kernel_v2(ConvParams p) {
 #pragma unroll
       for (int mt = 0; mt < WMT; ++mt) ac[mt] = an[mt];
     }
-#ifdef ODVAE_STAMPS
-    const unsigned long long st_b0 = ODVAE_T();
-#endif
     if (more) store_halo(smem + ((ch + 1) & 1) * HPIX * HS);
     __syncthreads();
-#ifdef ODVAE_STAMPS
-    st_bar += ODVAE_T() - st_b0;
-#endif
   }
-#ifdef ODVAE_STAMPS
-  const unsigned long long st_mma = ODVAE_T();
-#endif
 
   // Epilogue: stores only (bias and residual were folded into the accumulators' initial value)
   const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(p.y + (int64_t)n * p.Ho * p.Wo * p.Cout, 0, img_bytes, 0x00020000);
@@ -488,13 +300,6 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_kernel_v2(ConvParams p) {
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(relu ? fmaxf(v, 0.f) : v), yrsrc, pb + cobyte[nt], 0, 0);
       }
     }
-#ifdef ODVAE_STAMPS
-  if (blockIdx.y == 0 && blockIdx.x < 4096 && lane == 0) {
-    const unsigned long long st_done = ODVAE_T();
-    unsigned long long* o = g_stamps + ((size_t)blockIdx.x * 4 + wave) * 4;
-    o[0] = st_loop - st_start; o[1] = st_mma - st_loop; o[2] = st_bar; o[3] = st_done - st_mma;
-  }
-#endif
 }
 
 // OIHW -> fwd pack [t][CinP/4][CoutP][4] and dgrad pack [t'][CoutP_d/4][CinP_d][4] (flipped taps)
@@ -718,12 +523,6 @@ constexpr int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
 extern "C" {
 
-#ifdef ODVAE_STAMPS
-int odvae_debug_read_stamps(unsigned long long* host, size_t count) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), count * sizeof(unsigned long long));
-}
-#endif
-
 // padded reduction / output channel counts of a weight pack (reduce = channels summed over)
 int odvae_conv3x3_pack_reduce_pad(int c_reduce) { return round_up(c_reduce, 32); }
 int odvae_conv3x3_pack_out_pad(int c_out) { return c_out <= 32 ? 32 : round_up(c_out, 128); }
@@ -797,48 +596,33 @@ int odvae_conv3x3_f32(int mode, const float* x, int N, int Hi, int Wi, int Cin,
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool narrow = Cout <= 32;
   dim3 block(256);
-  static const bool thin_off = getenv("ODVAE_CONV_THIN_OFF") != nullptr;
-  if (mode == 0 && Cin == 3 && Wo % 32 == 0 && !thin_off) {
+  if (mode == 0 && Cin == 3 && Wo % 32 == 0) {
     const int64_t ntiles = (int64_t)N * Ho * (Wo / 32);
     const int blocks = (int)std::min<int64_t>(1024, ceil_div64(ntiles, 4));
     hipLaunchKernelGGL(conv3x3_thin_in_kernel, dim3(blocks, ceil_div(Cout, 128)), block, 0, st, p);
     ODVAE_LAUNCH_CHECK("conv3x3 thin-in");
     return ODVAE_OK;
   }
-  static const bool thin_out_off = getenv("ODVAE_CONV_THIN_OUT_OFF") != nullptr;
-  if (mode == 0 && Cout <= 3 && Cin == 128 && !residual && act == 0 && !thin_out_off) {      // decoder.conv_out: the reconstruction
+  if (mode == 0 && Cout <= 3 && Cin == 128 && !residual && act == 0) {      // decoder.conv_out: the reconstruction
     p.tiles_x = ceil_div(Wo, TO_TW); p.tiles_y = ceil_div(Ho, TO_TH);
     ODVAE_CHECK_ARG((int64_t)p.tiles_x * p.tiles_y * N < (1ll << 31), "conv3x3: too many tiles");
     hipLaunchKernelGGL(conv3x3_thin_out_kernel<128>, dim3((unsigned)(p.tiles_x * p.tiles_y * N)), block, 0, st, p);
     ODVAE_LAUNCH_CHECK("conv3x3 thin-out");
     return ODVAE_OK;
   }
-  // ODVAE_CONV_VARIANT=0 selects the first per-tap-barrier kernel (kept for in-process A/B timing and as the
-  // "before" of profiles/r01_conv3x3_pmc.md); 1 (default) = v2
-  static const int variant = getenv("ODVAE_CONV_VARIANT") ? atoi(getenv("ODVAE_CONV_VARIANT")) : 1;
-  const bool use_v1 = variant == 0 && mode <= 3;
-#define ODVAE_CONV_LAUNCH(KERNEL, MODE, KC)                                                                      \
-  if (narrow) hipLaunchKernelGGL((KERNEL<MODE, KC, 1, 1, 4, 1>), dim3((unsigned)sp, p.CoutP / 32), block, 0, st, p); \
-  else hipLaunchKernelGGL((KERNEL<MODE, KC, 2, 2, 2, 2>), dim3((unsigned)sp, p.CoutP / 128), block, 0, st, p)
-  if (use_v1) {
-    switch (mode) {
-      case 0: ODVAE_CONV_LAUNCH(conv3x3_kernel, 0, 16); break;
-      case 1: ODVAE_CONV_LAUNCH(conv3x3_kernel, 1, 8); break;
-      case 2: ODVAE_CONV_LAUNCH(conv3x3_kernel, 2, 16); break;
-      default: ODVAE_CONV_LAUNCH(conv3x3_kernel, 3, 16); break;
-    }
-  } else {
-    switch (mode) {
-      case 0: ODVAE_CONV_LAUNCH(conv3x3_kernel_v2, 0, 32); break;
-      case 1: ODVAE_CONV_LAUNCH(conv3x3_kernel_v2, 1, 8); break;
-      case 2: ODVAE_CONV_LAUNCH(conv3x3_kernel_v2, 2, 32); break;
-      case 5:
-        if (narrow) hipLaunchKernelGGL((conv3x3_kernel_v2<5, 32, 1, 1, 4, 1>), dim3((unsigned)sp, p.CoutP / 32, 4), block, 0, st, p);
-        else hipLaunchKernelGGL((conv3x3_kernel_v2<5, 32, 2, 2, 2, 2>), dim3((unsigned)sp, p.CoutP / 128, 4), block, 0, st, p);
-        break;
-      case 6: ODVAE_CONV_LAUNCH(conv3x3_kernel_v2, 6, 8); break;
-      default: ODVAE_CONV_LAUNCH(conv3x3_kernel_v2, 3, 32); break;
-    }
+#define ODVAE_CONV_LAUNCH(MODE, KC)                                                                                         \
+  if (narrow) hipLaunchKernelGGL((conv3x3_kernel_v2<MODE, KC, 1, 1, 4, 1>), dim3((unsigned)sp, p.CoutP / 32), block, 0, st, p); \
+  else hipLaunchKernelGGL((conv3x3_kernel_v2<MODE, KC, 2, 2, 2, 2>), dim3((unsigned)sp, p.CoutP / 128), block, 0, st, p)
+  switch (mode) {
+    case 0: ODVAE_CONV_LAUNCH(0, 32); break;
+    case 1: ODVAE_CONV_LAUNCH(1, 8); break;
+    case 2: ODVAE_CONV_LAUNCH(2, 32); break;
+    case 5:
+      if (narrow) hipLaunchKernelGGL((conv3x3_kernel_v2<5, 32, 1, 1, 4, 1>), dim3((unsigned)sp, p.CoutP / 32, 4), block, 0, st, p);
+      else hipLaunchKernelGGL((conv3x3_kernel_v2<5, 32, 2, 2, 2, 2>), dim3((unsigned)sp, p.CoutP / 128, 4), block, 0, st, p);
+      break;
+    case 6: ODVAE_CONV_LAUNCH(6, 8); break;
+    default: ODVAE_CONV_LAUNCH(3, 32); break;
   }
 #undef ODVAE_CONV_LAUNCH
   ODVAE_LAUNCH_CHECK("conv3x3");

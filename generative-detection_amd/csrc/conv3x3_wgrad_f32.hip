@@ -13,7 +13,6 @@
 // one dy read feeds nine MFMAs.  Blocks write partial slabs; a second kernel sums them in a fixed order
 // (deterministic) and writes OIHW.  db = column sums of dy ride along in the ci-tile-0 blocks.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -641,12 +640,10 @@ __global__ void conv3x3_wgrad_thin_reduce_kernel(const float* __restrict__ slab,
 
 struct Plan { int v2, up, th, tiles_x, tiles_y, ntiles, nsplit, tiles_per_split, CinP, CoutP, ci_tiles, co_tiles; };
 
-// v2 (LDS-DMA) whenever both channel counts allow 16-byte pieces and the 128-wide co tile is not mostly padding;
-// ODVAE_WGRAD_V1=1 forces the register-staged kernel (in-process A/B)
+// v2 (LDS-DMA) whenever both channel counts allow 16-byte pieces and the 128-wide co tile is not mostly padding
 Plan make_plan(int mode, int N, int Ho, int Wo, int Cin, int Cout) {
-  static const bool force_v1 = getenv("ODVAE_WGRAD_V1") != nullptr;
   Plan pl;
-  pl.up = mode == 5 && !force_v1 && Cin % 4 == 0 && Cout % 4 == 0;
+  pl.up = mode == 5 && Cin % 4 == 0 && Cout % 4 == 0;
   if (pl.up) {   // tiles of 2 x 16 LOW-RES pixels (Ho, Wo are the output's: twice the input's)
     pl.v2 = 1; pl.th = UP_TH;
     pl.tiles_x = ceil_div(Wo / 2, TW); pl.tiles_y = ceil_div(Ho / 2, UP_TH);
@@ -661,7 +658,7 @@ Plan make_plan(int mode, int N, int Ho, int Wo, int Cin, int Cout) {
     return pl;
   }
   if (mode == 5) mode = 2;   // channel counts the DMA kernel cannot take: dense form
-  pl.v2 = !force_v1 && Cin % 4 == 0 && Cout % 4 == 0 && Cout > 64;
+  pl.v2 = Cin % 4 == 0 && Cout % 4 == 0 && Cout > 64;
   const int bci = pl.v2 ? BCI2 : BC, bco = pl.v2 ? BCO2 : BC;
   pl.th = pl.v2 ? (mode == 1 ? 2 : 4) : (mode == 1 ? 4 : 8);
   pl.tiles_x = ceil_div(Wo, TW);
@@ -672,8 +669,7 @@ Plan make_plan(int mode, int N, int Ho, int Wo, int Cin, int Cout) {
   pl.ci_tiles = pl.CinP / bci;
   pl.co_tiles = pl.CoutP / bco;
   const int ctiles = pl.ci_tiles * pl.co_tiles;
-  static const int v2_blocks = getenv("ODVAE_WGRAD_BLOCKS") ? atoi(getenv("ODVAE_WGRAD_BLOCKS")) : 256;   // one block per CU, one round (512: -3..-10 %)
-  int nsplit = ceil_div(pl.v2 ? v2_blocks : 1024, ctiles);   // v2 runs one 8-wave block per CU
+  int nsplit = ceil_div(pl.v2 ? 256 : 1024, ctiles);   // v2 runs one 8-wave block per CU, one round (512: -3..-10 %)
   if (nsplit > pl.ntiles) nsplit = pl.ntiles;
   if (nsplit < 1) nsplit = 1;
   pl.tiles_per_split = ceil_div(pl.ntiles, nsplit);
@@ -684,9 +680,8 @@ Plan make_plan(int mode, int N, int Ho, int Wo, int Cin, int Cout) {
 // thin-side kernel: stride-1 conv whose input or output has <= 3 channels (conv_in / conv_out)
 constexpr int THIN_BLOCKS = 1024, THIN_BIAS_BLOCKS = 256;
 bool thin_applies(int mode, int Hi, int Wi, int Cin, int Cout) {
-  static const bool off = getenv("ODVAE_WGRAD_V1") != nullptr;
   const int cb = Cin <= 3 ? Cout : Cin;
-  return !off && mode == 0 && (Cin <= 3) != (Cout <= 3) && Wi % 16 == 0 && cb % 4 == 0 && cb >= 32 &&
+  return mode == 0 && (Cin <= 3) != (Cout <= 3) && Wi % 16 == 0 && cb % 4 == 0 && cb >= 32 &&
          (int64_t)Hi * Wi * cb * 4 < 0x7FFFFFF0ll;
 }
 size_t thin_workspace_floats(int Cin, int Cout) {

@@ -18,7 +18,6 @@
 // chunk k.  Each block writes its partial dU slab; the reduction sums the slabs in a fixed order (deterministic),
 // applies G^T . G and writes OIHW.  The bias gradient rides along: dM[xi = (1,1)] is the sum of the tile's four dy pixels.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -101,11 +100,7 @@ __device__ __forceinline__ void wgw_body(const WgwParams& p, float* dsm, const i
   set_bases();
   float4 xr[2][4], yr[2][2];
   auto fetch_x = [&]() {
-#ifdef ODVAE_WGW_NOFETCH   // ablation build: every fetch is answered with zeros by the descriptor, no memory traffic
-    const bool valid = false;
-#else
     const bool valid = tl < end_tile;
-#endif
     const bool rok0 = valid && (ra != 0 || tty > 0), rok1 = valid && (rb != 3 || tty < p.TY - 1);
     const bool cok0 = ttx > 0, cok3 = ttx < p.TX - 1;
     const unsigned xo0 = xoff + (unsigned)(ra * p.W) * cin4, xo1 = xoff + (unsigned)(rb * p.W) * cin4;
@@ -117,11 +112,7 @@ __device__ __forceinline__ void wgw_body(const WgwParams& p, float* dsm, const i
     }
   };
   auto fetch_y = [&]() {     // and advance to this thread's tile of the following chunk
-#ifdef ODVAE_WGW_NOFETCH   // ablation build: every fetch is answered with zeros by the descriptor, no memory traffic
-    const bool valid = false;
-#else
     const bool valid = tl < end_tile;
-#endif
     const unsigned yo0 = yoff, yo1 = yoff + (unsigned)p.W * cout4;
     const bool u0 = valid && ya != 0, u1 = valid && yb != 0;
 #pragma unroll
@@ -332,9 +323,8 @@ void plan(int N, int H, int W, int Cin, int Cout, WgwParams& p) {
   p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.TY = H / 2; p.TX = W / 2;
   p.total_tiles = N * p.TY * p.TX;
   p.total_chunks = ceil_div(p.total_tiles, CT);
-  static const int target = getenv("ODVAE_WGRAD_WINO_BLOCKS") ? atoi(getenv("ODVAE_WGRAD_WINO_BLOCKS")) : 256;
   const int base = 4 * (Cin / 128) * (Cout / 128);
-  int ns = std::max(1, std::min(target / base, p.total_chunks));
+  int ns = std::max(1, std::min(256 / base, p.total_chunks));   // one 8-wave block per CU, one round
   p.chunks_per_split = ceil_div(p.total_chunks, ns);
   p.nsplit = ceil_div(p.total_chunks, p.chunks_per_split);
 }

@@ -22,7 +22,6 @@
 // (packed f32 math); V is [xi][quad][tile][4], so an A fragment is 1 KB contiguous.  One barrier per chunk; V and the halo
 // are double-buffered.  The output transform goes through LDS one tile row at a time (36 values per (tile, co) -> 16 pixels).
 #include "bf16_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -73,13 +72,6 @@ __device__ __forceinline__ f32x2 lds_ld64f(unsigned a) { return *(const __attrib
 __device__ __forceinline__ void lds_st64f(unsigned a, f32x2 v) { *(__attribute__((address_space(3))) f32x2*)(uintptr_t)a = v; }
 __device__ __forceinline__ float lds_ld32f(unsigned a) { return *(const __attribute__((address_space(3))) float*)(uintptr_t)a; }
 __device__ __forceinline__ void lds_st32f(unsigned a, float v) { *(__attribute__((address_space(3))) float*)(uintptr_t)a = v; }
-// -DODVAE_W4_ABL=<bits>: timing-only ablation builds (results are wrong): 1 no output transform, 2 no input transform in the loop,
-// 4 no weight refills, 8 no A-fragment reads, 16 no halo DMA in the loop, 32 no wait for the DMA at the end of a chunk, 64 no barrier,
-// 128 epilogue without the stores, 256 without the LDS exchange, 512 without its barriers, 1024 every other weight refill only,
-// 2048 no output transform at all
-#ifndef ODVAE_W4_ABL
-#define ODVAE_W4_ABL 0
-#endif
 template <int N> __device__ __forceinline__ void wait_vm_but() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // one row of (B^T d) times B: six values t[0..5] along x -> the six V entries of that row, stored 1 KB apart
@@ -276,24 +268,24 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(Wino4Params p) {
     const unsigned Vc = v0 + (ch & 1) * V_B + a_off;
     const bool more = ch + 1 < nchunks;
     const int chn = more ? ch + 1 : 0;      // past the last chunk: chunk 0 again, the next tile's first fragments (same output channels)
-    if (!(ODVAE_W4_ABL & 16)) dma_halo_or_none(ch + 2, ch & 1);
+    dma_halo_or_none(ch + 2, ch & 1);
     f32x4 a = lds_ld128f(Vc);
 #pragma unroll
     for (int j = 0; j < 9; ++j) {
       f32x4 an = a;
-      if (j < 8 && !(ODVAE_W4_ABL & 8)) an = lds_ld128f(Vc + (j + 1) * 1024);
-      ODVAE_W4_AWAIT((ODVAE_W4_ABL & 20) ? 0 : (ODVAE_W4_ABL & 1024) ? 4 + HALO_DMA_PER_WAVE : 8 + HALO_DMA_PER_WAVE, b[j]);
+      if (j < 8) an = lds_ld128f(Vc + (j + 1) * 1024);
+      ODVAE_W4_AWAIT(8 + HALO_DMA_PER_WAVE, b[j]);
       acc[j] = mfma32(a.x, b[j].x, acc[j]);
       acc[j] = mfma32(a.y, b[j].y, acc[j]);
       acc[j] = mfma32(a.z, b[j].z, acc[j]);
       acc[j] = mfma32(a.w, b[j].w, acc[j]);
-      if (!(ODVAE_W4_ABL & 4) && (!(ODVAE_W4_ABL & 1024) || (j & 1) == 0)) load_b(chn, j, b[j]);
+      load_b(chn, j, b[j]);
       a = an;
-      if (!(ODVAE_W4_ABL & 2) && (j == 2 || j == 6) && j == t_at && more)
+      if ((j == 2 || j == 6) && j == t_at && more)
         transform(halo0 + ((ch + 1) & 1) * HALO_B, v0 + ((ch + 1) & 1) * V_B);
     }
-    if (!(ODVAE_W4_ABL & 32)) wait_vm_but<(ODVAE_W4_ABL & 20) ? 0 : (ODVAE_W4_ABL & 1024) ? 5 : 9>();      // this wave's halo pieces of chunk ch+2 (older than the nine refills) have landed
-    if (!(ODVAE_W4_ABL & 64)) __syncthreads();
+    wait_vm_but<9>();      // this wave's halo pieces of chunk ch+2 (older than the nine refills) have landed
+    __syncthreads();
   }
   wait_vm_but<0>();      // the last refills have landed: their registers stay live across the output transform
   const int n = cur.n, oy0 = cur.oy0, ox0 = cur.ox0;
@@ -328,20 +320,12 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(Wino4Params p) {
   const int cstep = p.Cout * 4, rstep = (POOL ? p.W >> 1 : p.W) * p.Cout * 4;
   const unsigned x_wr = (unsigned)(X0 + ((ct * 36 + 9 * g) * 4 * 64 + lane_e) * 4);
   const unsigned x_rd = (unsigned)(X0 + ((ct2 * 36 * 4 + e2) * 64 + lane_e) * 4);
-  if (ODVAE_W4_ABL & 2048) {      // timing only: no output transform at all (the accumulators are consumed by one guarded store)
-    float sacc = 0.f;
+#pragma unroll
+  for (int rq = 0; rq < 4; ++rq) {
 #pragma unroll
     for (int j = 0; j < 9; ++j)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) sacc += acc[j][r];
-    if (sacc == 12345.678f) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(sacc), yrsrc, 0, 0, 0);
-  }
-#pragma unroll
-  for (int rq = 0; rq < ((ODVAE_W4_ABL & 2048) ? 0 : 4); ++rq) {
-#pragma unroll
-    for (int j = 0; j < 9; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) if (!(ODVAE_W4_ABL & 256)) lds_st32f(x_wr + (j * 4 + e) * 256, acc[j][4 * rq + e]);
+      for (int e = 0; e < 4; ++e) lds_st32f(x_wr + (j * 4 + e) * 256, acc[j][4 * rq + e]);
     // element (register 4 rq + e2, lane) is tile (row rq, column 4 h + e2): a 4x4 pixel block of one output channel
     const int py = oy0 + 4 * rq, px = ox0 + 4 * (4 * h_e + e2);
     const unsigned base = !(py < p.H && px < p.W && co < p.Cout) ? OOB
@@ -366,7 +350,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(Wino4Params p) {
         for (int c = 0; c < 4; ++c)
           gx[a][c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(gxrsrc, base, a * rstep + c * cstep, 0));
     }
-    if (!(ODVAE_W4_ABL & 512)) __syncthreads();
+    __syncthreads();
     float psum = 0.f, psq = 0.f;      // STATS: this pass's share of the GroupNorm statistics; parked in LDS at the end of the pass, so
                                       // that nothing of it stays in a register across the passes (with two accumulators live over
                                       // the whole output transform hipcc spilled nine registers into scratch)
@@ -376,7 +360,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(Wino4Params p) {
     for (int i = 0; i < 6; ++i) {
       float m[6];
 #pragma unroll
-      for (int j = 0; j < 6; ++j) m[j] = (ODVAE_W4_ABL & 256) ? acc[(6 * i + j) % 9][4 * rq + (i & 3)] : lds_ld32f(x_rd + (6 * i + j) * 1024);
+      for (int j = 0; j < 6; ++j) m[j] = lds_ld32f(x_rd + (6 * i + j) * 1024);
       const float s1 = m[1] + m[2], d1 = m[1] - m[2], s2 = m[3] + m[4], d2 = m[3] - m[4];
       tt[i][0] = m[0] + s1 + s2;
       tt[i][1] = d1 + 2.f * d2;
@@ -400,8 +384,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(Wino4Params p) {
       } else {
 #pragma unroll
         for (int a = 0; a < 4; ++a)
-          if (!(ODVAE_W4_ABL & 128) || yv[a] == 12345.678f)
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(yv[a]), yrsrc, base, a * rstep + c * cstep, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(yv[a]), yrsrc, base, a * rstep + c * cstep, 0);
       }
       if (STATS && base != OOB) {      // (a 4x4 tile is inside the image as a whole: H and W are multiples of 4)
 #pragma unroll
@@ -425,7 +408,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(Wino4Params p) {
     // the next tile's halo: with a residual the 16 loads + 16 stores of pass 0 are younger than it, without one the 32 stores of passes 0, 1
     // (EPI_POOL writes 4 values per pass: its two halo chunks are awaited outright after pass 1 -- 8 stores younger)
     if (has_next && rq == ((!GNB && p.residual) || GNB ? 0 : 1)) { if (POOL) wait_vm_but<8>(); else wait_vm_but<32>(); }
-    if (rq < 3 && !(ODVAE_W4_ABL & 512)) __syncthreads();     // X is rewritten by the next pass
+    if (rq < 3) __syncthreads();     // X is rewritten by the next pass
   }
   // ---- GroupNorm statistics of this tile for the layer that reads y: (sum, sum of squares) per channel group, one slot per
   // (image, tile, group) written by exactly one block -- the consumer's finalize kernel adds the tiles up in f64, in fixed order ----
@@ -661,8 +644,7 @@ static int wino4_launch(const float* x, int N, int H, int W, int Cin, const floa
   ODVAE_CHECK_ARG((int64_t)36 * p.CinP * p.CoutP * 4 < 0x7FFFFFF0ll, "conv3x3_wino4: pack too large");
   const int64_t sp = (int64_t)p.tiles_x * p.tiles_y * N;
   ODVAE_CHECK_ARG(sp < (1ll << 31), "conv3x3_wino4: too many tiles");
-  static const bool xcd = getenv("ODVAE_TILE_XCD") == nullptr || atoi(getenv("ODVAE_TILE_XCD")) != 0;
-  p.xcd = xcd ? 1 : 0;
+  p.xcd = 1;
   const auto kern = gnb ? conv3x3_wino4_kernel<EPI_GNBWD, false>
                   : pool ? conv3x3_wino4_kernel<EPI_POOL, false>
                   : up ? (gn_partial ? conv3x3_wino4_kernel<EPI_STATS, true> : conv3x3_wino4_kernel<EPI_NONE, true>)
@@ -674,14 +656,13 @@ static int wino4_launch(const float* x, int N, int H, int W, int Cin, const floa
     return ODVAE_ERR_HIP;
   }
   // persistent form: one block per CU; needs a grid that splits evenly over the output-channel blocks and >= 2 tiles per block
-  static const bool no_persist = getenv("ODVAE_WINO_PERSIST") != nullptr && atoi(getenv("ODVAE_WINO_PERSIST")) == 0;
   static const int cus = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
     return n;
   }();
   const int ny = p.CoutP / BN;
-  p.persist = (!no_persist && cus % (8 * ny) == 0 && sp >= 2 * (cus / ny)) ? 1 : 0;
+  p.persist = (cus % (8 * ny) == 0 && sp >= 2 * (cus / ny)) ? 1 : 0;
   if (p.persist) hipLaunchKernelGGL(kern, dim3(cus), dim3(512), lds_bytes, static_cast<hipStream_t>(stream), p);
   else hipLaunchKernelGGL(kern, dim3((unsigned)sp, ny), dim3(512), lds_bytes, static_cast<hipStream_t>(stream), p);
   ODVAE_LAUNCH_CHECK("conv3x3_wino4");

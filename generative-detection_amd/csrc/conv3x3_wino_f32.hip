@@ -14,7 +14,6 @@
 // each wave folds its row (M A, registers only), the rows meet through LDS (A^T), and bias / residual / store follow.
 // The arithmetic is f32 throughout; only the summation order differs from the direct form (error ~1e-6 relative).
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -590,17 +589,15 @@ int odvae_conv3x3_wino_f32(const float* x, int N, int H, int W, int Cin, const f
   p.tiles_x = ceil_div(W, TW); p.tiles_y = ceil_div(H, TH); p.act = act;
   const int64_t sp = (int64_t)p.tiles_x * p.tiles_y * N;
   ODVAE_CHECK_ARG(sp < (1ll << 31), "conv3x3_wino: too many tiles");
-  static const bool no8 = getenv("ODVAE_WINO_4WAVE") != nullptr;
-  if (Cout % BN8 == 0 && !no8) {
+  if (Cout % BN8 == 0) {
     // the persistent form needs >= 2 tiles per block, an even chunk count >= 4 and a grid that splits evenly over the co blocks
-    static const bool no_persist = getenv("ODVAE_WINO_PERSIST") != nullptr && atoi(getenv("ODVAE_WINO_PERSIST")) == 0;
     static const int cus = [] {      // one persistent block per CU (256 on MI355X)
       int dev = 0, n = 0;
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
       return n;
     }();
     const int ny = p.CoutP / BN8, nchunks = p.CinP / KC, G = cus;
-    const bool persist = !no_persist && nchunks >= 4 && (nchunks & 1) == 0 && G % (8 * ny) == 0 && sp >= 2 * (G / ny);
+    const bool persist = nchunks >= 4 && (nchunks & 1) == 0 && G % (8 * ny) == 0 && sp >= 2 * (G / ny);
     const size_t smem = (size_t)(persist ? X_OFF_PERSIST + 16384 : 2 * HALO_F + 2 * V_F) * sizeof(float);
     auto kern = persist ? conv3x3_wino8_kernel<true> : conv3x3_wino8_kernel<false>;
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
@@ -608,8 +605,7 @@ int odvae_conv3x3_wino_f32(const float* x, int N, int H, int W, int Cin, const f
       odvae_set_error("conv3x3_wino: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
       return ODVAE_ERR_HIP;
     }
-    static const bool xcd = getenv("ODVAE_TILE_XCD") == nullptr || atoi(getenv("ODVAE_TILE_XCD")) != 0;
-    p.xcd = xcd ? 1 : 0;
+    p.xcd = 1;
     if (persist) hipLaunchKernelGGL(kern, dim3(G), dim3(512), smem, static_cast<hipStream_t>(stream), p);
     else hipLaunchKernelGGL(kern, dim3((unsigned)sp, ny), dim3(512), smem, static_cast<hipStream_t>(stream), p);
   } else {

@@ -16,7 +16,6 @@
 // Block = 8x16 output pixels x BCO output channels, 4 waves; per KC input channels the halo patch [halo px][KC + 8] is
 // staged once (double-buffered, branch-free buffer loads with hardware zero fill), ONE barrier per chunk.
 #include "bf16_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -444,8 +443,7 @@ static int conv_bf16_impl(int mode, const void* x, int N, int Hi, int Wi, int Ci
   p.CinP = odvae_conv_bf16_reduce_pad(Cin); p.CoutP = odvae_conv_bf16_out_pad(Cout);
   p.tiles_x = ceil_div(Wo, TW); p.tiles_y = ceil_div(Ho, 8); p.out_f32 = out_f32;
   p.gn_partial = gn_partial; p.gn_groups = gn_groups; p.gn_cpg = gn_groups > 0 ? Cout / gn_groups : 0;
-  static const bool xcd = getenv("ODVAE_TILE_XCD") == nullptr || atoi(getenv("ODVAE_TILE_XCD")) != 0;
-  p.xcd = xcd ? 1 : 0;
+  p.xcd = 1;
   ODVAE_CHECK_ARG((int64_t)N * p.tiles_x * p.tiles_y < 0x7FFFFFFFll, "conv_bf16: too many tiles");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool k64 = p.CinP % 64 == 0;

@@ -512,25 +512,6 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // wait until at most N of this wave's vector-memory operations are outstanding (N = the pieces of the newest fetch batch: a batch is
 // given two periods to land -- it is issued for the tile after next -- and only the batch before it has to be complete at a barrier)
 template <int N> __device__ __forceinline__ void wait_vm_all_but() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#ifndef ODVAE_FLASH_PAIR_PRIO
-#define ODVAE_FLASH_PAIR_PRIO 1
-#endif
-__device__ __forceinline__ bool flash_pair_prio() { return ODVAE_FLASH_PAIR_PRIO != 0; }
-// -DODVAE_FLASH_STAMPS: s_memtime stamps in the dK/dV pair kernel (diagnostic build; tools/flash_stamps.py reads them with
-// odvae_flash_debug_stamps).  Per role (A, B): cycles summed over the periods of block 0, pair 0, of the sections
-//   0 tile fetch issue | 1 ring fill + (B) dS arithmetic | 2 second product (16 MFMAs) | 3 first product (16 MFMAs) | 4 (A) probabilities |
-//   5 vmcnt wait | 6 barrier
-#ifdef ODVAE_FLASH_STAMPS
-__device__ unsigned long long g_flash_stamps[2][8];
-#define FSTAMP(k) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); sacc_[k] += now_ - last_; last_ = now_; } while (0)   /* scalar registers only: no memory traffic inside the loop */
-#else
-#define FSTAMP(k) do { } while (0)
-#endif
-// timing-only ablation builds (tools/ab_build.py ... -DODVAE_FLASH_ABL=mask; results are WRONG): 1 = no tile fetch inside the loop,
-// 2 = no barrier inside the loop, 4 = no softmax / dS arithmetic, 8 = no second product, 16 = no first product
-#ifndef ODVAE_FLASH_ABL
-#define ODVAE_FLASH_ABL 0
-#endif
 
 template <int D>
 struct PairGeom {
@@ -550,7 +531,7 @@ __device__ __forceinline__ int swz16(int row) { return ((row & 3) << 2) | ((row 
 // tile rows j RPP .. j RPP + RPP - 1; lane (r_in = lane / CPR, chp = lane % CPR) fills chunk position chp of row j RPP + r_in with source
 // chunk chp ^ swz16(row).  The row part of the source offset is scalar arithmetic; per lane it is a shift, an OR, an XOR and an add
 // (issuing a piece used to carry fourteen vector instructions, a 32-bit vector multiply among them: 160-180 cycles per piece, a fifth of
-// a dK/dV period -- in-kernel stamps, tools/flash_stamps.py).  full = the tile lies inside the matrix (no per-lane range check).
+// a dK/dV period -- in-kernel stamps, profiles/r03_flash_dkv_stamps.txt).  full = the tile lies inside the matrix (no per-lane range check).
 template <int D>
 __device__ __forceinline__ void dma_piece(i32x4_t rsrc, unsigned lds_tile, int j, int row0, int T, int ld, int col0, bool full, int lane) {
   using G = PairGeom<D>;
@@ -628,8 +609,7 @@ __global__ __launch_bounds__(512) void flash_dkv_pair_kernel(FlashP p) {
   const int role = wave >> 2, pair = wave & 3;             // role 0 = A (S, P, dV), 1 = B (dP, dS, dK)
   // Waves w and w + 4 (a pair) share a SIMD.  A runs ahead: its MFMAs take the matrix pipe first, B's vector work (dS) hides under
   // them at the start of a period and B's MFMAs fill the pipe while A computes the next tile's probabilities at its end.
-  if (ODVAE_FLASH_PAIR_PRIO == 1 && role == 0) __builtin_amdgcn_s_setprio(2);
-  if (ODVAE_FLASH_PAIR_PRIO == 2 && role == 1) __builtin_amdgcn_s_setprio(2);
+  if (role == 0) __builtin_amdgcn_s_setprio(2);
   const int QB = (p.T + 127) / 128;
   int n, kb;
   pair_block_coords(p.N, QB, n, kb);
@@ -647,7 +627,7 @@ __global__ __launch_bounds__(512) void flash_dkv_pair_kernel(FlashP p) {
   const bool kok = key0 + li < p.T;
   const int ntiles = (p.T + 31) / 32;
 
-  // Fetch duty (in-kernel stamps, tools/flash_stamps.py): a piece costs ~100-150 cycles of the issuing wave's time; issued by every wave
+  // Fetch duty (in-kernel stamps, profiles/r03_flash_dkv_stamps.txt): a piece costs ~100-150 cycles of the issuing wave's time; issued by every wave
   // at the top of a period -- the first form -- all four SIMDs sat without an MFMA for ~800 of 3 600 cycles, and B (dS arithmetic in front
   // of its MFMAs, its MFMAs behind A's on the shared pipe) is the long pole while A waits a quarter of the period at the barrier.  So the A
   // waves alone fetch -- PIECES / 2 tile pieces each, waves 0 and 1 the two row-constant pieces as well -- and they do it BETWEEN their
@@ -711,7 +691,6 @@ __global__ __launch_bounds__(512) void flash_dkv_pair_kernel(FlashP p) {
   };
   // A: P = exp2(c S - lse2) of the tile in `stage`, handed to B through exchange buffer `xsel`, and its fragments for the dV product
   auto probabilities = [&](unsigned stage, unsigned xsel) {
-    if (ODVAE_FLASH_ABL & 4) { pf[0] = frag_from_acc(s1, 0); pf[1] = frag_from_acc(s1, 1); return; }
 #pragma unroll
     for (int gp = 0; gp < 2; ++gp) {     // two row-constant reads in flight at a time (two LDS latencies per tile, not four; four do not fit the registers)
       const f32x4 la = lds_ld128f(constl + stage + 64 * gp), lb = lds_ld128f(constl + stage + 64 * gp + 32);
@@ -740,21 +719,15 @@ __global__ __launch_bounds__(512) void flash_dkv_pair_kernel(FlashP p) {
   // a wave waits out an LDS latency once per period, not once per product.  In the last period the first product runs on a stale
   // stage and its result is dropped.
   constexpr int NB = D / 16, NA = D / 16, RING = D >= 256 ? 4 : 6;   // D = 256 sits at 256 registers with four fragments in flight
-#ifdef ODVAE_FLASH_STAMPS
-  const bool stamp_on = blockIdx.x == 0 && pair == 0;
-  unsigned long long sacc_[7] = {0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last_ = __builtin_amdgcn_s_memtime();
-#endif
   for (int j = 0; j < ntiles; ++j) {
-    const bool fetching = role == 0 && j + 3 < ntiles && !(ODVAE_FLASH_ABL & 1);   // into the stage tile j - 1 left (free since the barrier above)
-    FSTAMP(0);
+    const bool fetching = role == 0 && j + 3 < ntiles;   // into the stage tile j - 1 left (free since the barrier above)
     const unsigned xsel = (j & 1) * 4 * XB;
     const unsigned rv = rowl + nxt;
     bf16x8 ring[RING];
     auto fetch = [&](int i) -> bf16x8 { return i < NB ? tr_frag_sw<D>(cur, trl, i & 1, i >> 1) : row_frag(rv, i - NB); };
 #pragma unroll
     for (int i = 0; i < RING; ++i) ring[i] = fetch(i);
-    if (role == 1 && !(ODVAE_FLASH_ABL & 4)) {   // dS = P (dP - delta) scale from A's probabilities (the ring's first reads are in flight)
+    if (role == 1) {   // dS = P (dP - delta) scale from A's probabilities (the ring's first reads are in flight)
 #pragma unroll
       for (int sfr = 0; sfr < 2; ++sfr) {      // per fragment: its eight probabilities (one read) and the two row-constant quads, in flight together
         // P in fragment order: dword k of fragment s holds P of registers 8 s + 2 k (low half) and 8 s + 2 k + 1 (high half)
@@ -770,44 +743,32 @@ __global__ __launch_bounds__(512) void flash_dkv_pair_kernel(FlashP p) {
       pf[0] = frag_from_acc(s1, 0);
       pf[1] = frag_from_acc(s1, 1);
     }
-    FSTAMP(1);
 #pragma unroll
     for (int i = 0; i < NB + NA; ++i) {
       __builtin_amdgcn_sched_barrier(0);
-#ifdef ODVAE_FLASH_STAMPS
-      if (i == NB) FSTAMP(2);
-#endif
       if (i < NB) {
-        if (!(ODVAE_FLASH_ABL & 8)) acc[i >> 1] = mfma_bf16(ring[i % RING], pf[i & 1], acc[i >> 1]);
+        acc[i >> 1] = mfma_bf16(ring[i % RING], pf[i & 1], acc[i >> 1]);
       } else {
         if (i == NB) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) s1[r] = 0.f;
         }
-        if (!(ODVAE_FLASH_ABL & 16)) s1 = mfma_bf16(ring[i % RING], bf[i - NB], s1);
+        s1 = mfma_bf16(ring[i % RING], bf[i - NB], s1);
       }
       if (i + RING < NB + NA) ring[i % RING] = fetch(i + RING);
       if ((i & 3) == 1 && (i >> 2) < NPA && fetching) fetch_piece(j + 3, fre, i >> 2);      // A: one fetch piece per four MFMAs
       if (i == 3 && fetching) fetch_piece(j + 3, fre, NPA);                                  // (waves 0, 1: the row constants)
       __builtin_amdgcn_sched_barrier(0);
     }
-    FSTAMP(3);
     if (role == 0) probabilities(nxt, xsel ^ (4 * XB));
-    FSTAMP(4);
     const unsigned t = cur; cur = nxt; nxt = nx2; nx2 = fre; fre = t;
     // tile j + 2 is read in the next period (first product) and was fetched in the previous one: everything but the batch just issued
     // has to have landed (waves 0 and 1 carry one row-constant piece more)
     if (!fetching) wait_vm_all_but<0>();          // (B waves have no vector-memory operations in the loop at all)
     else if (wave < 2) wait_vm_all_but<NPA + 1>();
     else wait_vm_all_but<NPA>();
-    FSTAMP(5);
-    if (!(ODVAE_FLASH_ABL & 2)) __syncthreads();
-    FSTAMP(6);
+    __syncthreads();
   }
-#ifdef ODVAE_FLASH_STAMPS
-  if (stamp_on && lane == 0)
-    for (int k = 0; k < 7; ++k) g_flash_stamps[role][k] += sacc_[k];
-#endif
   if (kok) {
     bf16_t* row = p.out + ((int64_t)n * p.T + key0 + li) * C3 + (role == 0 ? 2 * p.C : p.C);
 #pragma unroll
@@ -832,7 +793,7 @@ __global__ __launch_bounds__(512) void flash_dq_pair_kernel(FlashP p) {
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int role = wave >> 2, pair = wave & 3;             // role 0 = A (S^T, dP^T, dS^T), 1 = B (dQ^T)
-  if (role == 0 && flash_pair_prio()) __builtin_amdgcn_s_setprio(2);   // the producer is the long pole: the consumer's MFMAs fill the gaps it leaves
+  if (role == 0) __builtin_amdgcn_s_setprio(2);   // the producer is the long pole: the consumer's MFMAs fill the gaps it leaves
   const int QB = (p.T + 127) / 128;
   int n, qb;
   pair_block_coords(p.N, QB, n, qb);
@@ -977,7 +938,7 @@ __global__ __launch_bounds__(512) void flash_fwd_pair_kernel(FlashP p) {
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int role = wave >> 2, pair = wave & 3;             // role 0 = A (S^T, softmax), 1 = B (O^T)
-  if (role == 0 && flash_pair_prio()) __builtin_amdgcn_s_setprio(2);
+  if (role == 0) __builtin_amdgcn_s_setprio(2);
   const int QB = (p.T + 127) / 128;
   int n, qb;
   pair_block_coords(p.N, QB, n, qb);
@@ -1153,11 +1114,6 @@ void launch_dyn(K kernel, dim3 grid, int lds_bytes, hipStream_t st, const FlashP
     }                                                                                                                  \
     ODVAE_LAUNCH_CHECK(name);                                                                                          \
   } while (0)
-// ODVAE_FLASH_BWD_V1=1 keeps the first-generation kernels (one 32-row problem per wave; forward and backward) for in-process A/B runs
-bool flash_bwd_v1() {
-  static const bool v = [] { const char* e = getenv("ODVAE_FLASH_BWD_V1"); return e && e[0] == '1'; }();
-  return v;
-}
 constexpr int fwd_lds(int D, int DV, int KBT) { return 2 * (KBT * (D + 8) + KBT * (DV + 32)) * 2; }
 constexpr int dq_lds(int D, int KBT) { return 2 * (2 * KBT * (D + 8)) * 2; }
 constexpr int dkv_lds(int D, int KBT) { return 2 * (2 * KBT * (D + 8) + 4 * KBT) * 2; }
@@ -1167,15 +1123,6 @@ bool shape_ok(int N, int T, int C) {
 }
 
 }  // namespace
-
-#ifdef ODVAE_FLASH_STAMPS
-extern "C" int odvae_flash_debug_stamps(unsigned long long* out16, int reset) {
-  (void)hipDeviceSynchronize();
-  if (out16) (void)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_flash_stamps), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_flash_stamps), z, sizeof(z)); }
-  return 0;
-}
-#endif
 
 extern "C" {
 
@@ -1190,18 +1137,15 @@ int odvae_flash_attn_fwd_bf16(const void* qkv, int N, int T, int C, float scale,
   p.qkv = static_cast<const bf16_t*>(qkv); p.out = static_cast<bf16_t*>(o); p.lse2 = lse2; p.N = N; p.T = T; p.C = C; p.scale = scale;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int qb = ceil_div(T, 128);
-  if (!flash_bwd_v1() && (C == 128 || C == 256) && (int64_t)qb * N < 0x7FFFFFFF) {
+  // (the 1-D grid of qb * N blocks needs no bound of its own: shape_ok's N <= 65535 and T * 3C * 2 < 2^31 keep it below 2^31)
+  if (C == 128 || C == 256) {
     if (C == 256) launch_dyn(flash_fwd_pair_kernel<256>, dim3(qb * N), fwd_pair_lds<256>(), st, p, 512);
     else launch_dyn(flash_fwd_pair_kernel<128>, dim3(qb * N), fwd_pair_lds<128>(), st, p, 512);
     ODVAE_FLASH_LAUNCH_CHECK("flash_attn_fwd (pair kernel)");
     return ODVAE_OK;
   }
-  switch (C) {
-    case 64:  launch_dyn(flash_fwd_kernel<64, 64, 64>, dim3(qb, N, 1), fwd_lds(64, 64, 64), st, p); break;
-    case 128: launch_dyn(flash_fwd_kernel<128, 128, 64>, dim3(qb, N, 1), fwd_lds(128, 128, 64), st, p); break;
-    case 256: launch_dyn(flash_fwd_kernel<256, 256, 32>, dim3(qb, N, 1), fwd_lds(256, 256, 32), st, p); break;
-    default:  launch_dyn(flash_fwd_kernel<512, 128, 32>, dim3(qb, N, 4), fwd_lds(512, 128, 32), st, p); break;
-  }
+  if (C == 64) launch_dyn(flash_fwd_kernel<64, 64, 64>, dim3(qb, N, 1), fwd_lds(64, 64, 64), st, p);
+  else launch_dyn(flash_fwd_kernel<512, 128, 32>, dim3(qb, N, 4), fwd_lds(512, 128, 32), st, p);
   ODVAE_FLASH_LAUNCH_CHECK("flash_attn_fwd");
   return ODVAE_OK;
 }
@@ -1221,7 +1165,7 @@ int odvae_flash_attn_bwd_bf16(const void* qkv, const void* o, const void* d_o, c
   hipLaunchKernelGGL(flash_delta_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, p.d_o, p.o, rows, C, delta_ws);
   ODVAE_LAUNCH_CHECK("flash_attn delta");
   const int qb = ceil_div(T, 128);
-  if (!flash_bwd_v1() && (C == 128 || C == 256) && (int64_t)qb * N < 0x7FFFFFFF) {
+  if (C == 128 || C == 256) {      // (grid bound: as in the forward)
     if (C == 256) {
       launch_dyn(flash_dq_pair_kernel<256>, dim3(qb * N), dq_pair_lds<256>(), st, p, 512);
       launch_dyn(flash_dkv_pair_kernel<256>, dim3(qb * N), dkv_pair_lds<256>(), st, p, 512);
@@ -1232,19 +1176,12 @@ int odvae_flash_attn_bwd_bf16(const void* qkv, const void* o, const void* d_o, c
     ODVAE_FLASH_LAUNCH_CHECK("flash_attn_bwd (pair kernels)");
     return ODVAE_OK;
   }
-  switch (C) {
-    case 64:
-      launch_dyn(flash_dq_kernel<64, 64, 64>, dim3(qb, N, 1), dq_lds(64, 64), st, p);
-      launch_dyn(flash_dkv_kernel<64, 64, 64>, dim3(qb, N, 1), dkv_lds(64, 64), st, p); break;
-    case 128:
-      launch_dyn(flash_dq_kernel<128, 128, 64>, dim3(qb, N, 1), dq_lds(128, 64), st, p);
-      launch_dyn(flash_dkv_kernel<128, 128, 64>, dim3(qb, N, 1), dkv_lds(128, 64), st, p); break;
-    case 256:
-      launch_dyn(flash_dq_kernel<256, 256, 64>, dim3(qb, N, 1), dq_lds(256, 64), st, p);
-      launch_dyn(flash_dkv_kernel<256, 128, 32>, dim3(qb, N, 2), dkv_lds(256, 32), st, p); break;
-    default:
-      launch_dyn(flash_dq_kernel<512, 128, 32>, dim3(qb, N, 4), dq_lds(512, 32), st, p);
-      launch_dyn(flash_dkv_kernel<512, 64, 32>, dim3(qb, N, 8), dkv_lds(512, 32), st, p); break;
+  if (C == 64) {
+    launch_dyn(flash_dq_kernel<64, 64, 64>, dim3(qb, N, 1), dq_lds(64, 64), st, p);
+    launch_dyn(flash_dkv_kernel<64, 64, 64>, dim3(qb, N, 1), dkv_lds(64, 64), st, p);
+  } else {
+    launch_dyn(flash_dq_kernel<512, 128, 32>, dim3(qb, N, 4), dq_lds(512, 32), st, p);
+    launch_dyn(flash_dkv_kernel<512, 64, 32>, dim3(qb, N, 8), dkv_lds(512, 32), st, p);
   }
   ODVAE_FLASH_LAUNCH_CHECK("flash_attn_bwd");
   return ODVAE_OK;

@@ -17,7 +17,6 @@
 // step j of lane half h is k = 8g + 4h + j, so A and B always agree.
 // Split-K (grid.y) covers the long-K/small-MN products (wgrad: K = B*H*W).
 #include "bf16_common.h"   // LDS in 32-bit addresses, LDS-DMA by inline asm
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -515,10 +514,6 @@ __global__ void gemm_splitk_reduce_kernel(GemmParams p, int batches) {
     const int batch = (int)(idx / mn);
     const int64_t rem = idx - (int64_t)batch * mn;
     const int row = (int)(rem / p.N), col = (int)(rem - (int64_t)row * p.N);
-#ifdef ODVAE_OLD_REDUCE      // A/B build: one serial chain (the form before round 4's last week)
-    float s_old = 0.f;
-    for (int q = 0; q < p.splits; ++q) s_old += p.partial[((int64_t)q * batches + batch) * mn + rem];
-#endif
     float sk[4] = {0.f, 0.f, 0.f, 0.f};      // four independent chains (one chain of `splits` dependent round trips otherwise)
     int sp = 0;
     for (; sp + 3 < p.splits; sp += 4) {
@@ -527,9 +522,6 @@ __global__ void gemm_splitk_reduce_kernel(GemmParams p, int batches) {
     }
     for (; sp < p.splits; ++sp) sk[0] += p.partial[((int64_t)sp * batches + batch) * mn + rem];
     float s = (sk[0] + sk[1]) + (sk[2] + sk[3]);
-#ifdef ODVAE_OLD_REDUCE
-    s = s_old;
-#endif
     s *= p.alpha;
     if (p.bias) s += p.bias[col];
     const int64_t o = batch * p.sC + (int64_t)row * p.ldc + col;
@@ -538,15 +530,7 @@ __global__ void gemm_splitk_reduce_kernel(GemmParams p, int batches) {
   }
 }
 
-// ODVAE_GEMM_DMA: unset = per shape (see odvae_gemm_f32), 1 = LDS-DMA form everywhere, 0 = register-staged form everywhere
-int g_dma_mode = -2;      // -2: environment not read yet
-int dma_mode() {
-  if (g_dma_mode == -2) {
-    const int v = getenv("ODVAE_GEMM_DMA") == nullptr ? -1 : atoi(getenv("ODVAE_GEMM_DMA"));
-    g_dma_mode = v < 0 ? -1 : (v > 2 ? 2 : v);
-  }
-  return g_dma_mode;
-}
+int g_dma_mode = -1;      // operand staging, set by odvae_gemm_select_staging (-1: per shape, see odvae_gemm_f32)
 template <typename K>
 int launch_dma(K kern, dim3 grid, hipStream_t st, const GemmParams& p, unsigned lds_bytes = DmaGeom<32>::LDS_B) {
   const unsigned DMA_LDS_B = lds_bytes;
@@ -561,9 +545,8 @@ int launch_dma(K kern, dim3 grid, hipStream_t st, const GemmParams& p, unsigned 
 
 int choose_splits(int M, int N, int K, int batch) {
   const int64_t tiles = (int64_t)ceil_div(M, BM) * ceil_div(N, BN) * batch;
-  static const int target = getenv("ODVAE_GEMM_SPLIT_BLOCKS") ? atoi(getenv("ODVAE_GEMM_SPLIT_BLOCKS")) : 512;   // two blocks per CU; 1024 / 256 measured 8-12 % slower
   if (tiles >= 512 || K <= 1024) return 1;
-  int64_t s = target / tiles;
+  int64_t s = 512 / tiles;           // two blocks per CU; 1024 / 256 measured 8-12 % slower
   const int64_t max_by_k = K / 512;  // at least 16 k-tiles per split
   if (s > max_by_k) s = max_by_k;
   if (s < 1) s = 1;
@@ -575,10 +558,10 @@ int choose_splits(int M, int N, int K, int batch) {
 extern "C" {
 
 // Operand staging of odvae_gemm_f32 / odvae_gemm_softmax_bwd_f32: -1 per shape (default), 0 through registers (global -> VGPR -> ds_write,
-// one LDS stage, up to three blocks per CU), 1 by LDS-DMA (two stages, one barrier per step).  ODVAE_GEMM_DMA presets it.  Returns the
-// previous setting; 2 = LDS-DMA with 16-wide steps (32 KB, four blocks per CU).  Results are identical (same products, same summation order).
+// one LDS stage, up to three blocks per CU), 1 by LDS-DMA (two stages, one barrier per step), 2 LDS-DMA with 16-wide steps (32 KB, four
+// blocks per CU).  Returns the previous setting.  Results are identical (same products, same summation order).
 int odvae_gemm_select_staging(int mode) {
-  const int prev = dma_mode();
+  const int prev = g_dma_mode;
   g_dma_mode = mode < 0 ? -1 : (mode > 2 ? 2 : mode);
   return prev;
 }
@@ -686,10 +669,9 @@ static int gemm_f32_impl(int transA, int transB, int M, int N, int K, float alph
   // Which form: measured on the step's shapes (tools/gemm_probe.py, TFLOP/s, LDS-DMA vs register-staged): TN (both operands
   // row-contiguous: dV = P^T dO, dK = dS^T Q, the 1x1 weight gradients) 140.6 vs 132.3 and 127.2 vs 120.7; NN 132.6 vs 133.5; NT (both
   // k-contiguous, K = 256: QK^T, dO V^T, 1x1 forward) 122.2 vs 129.3 -- eight steps per block there, and the 64 KB of the two DMA stages
-  // cost the third block per CU that covers prologue and store bursts.  So: LDS-DMA where A is row-contiguous, ODVAE_GEMM_DMA=1 / 0
-  // forces it on / off everywhere.
-  const int dma_env = dma_mode();
-  const int bkt = dma_env < 0 ? (!a_kc ? 32 : 0) : (dma_env == 0 ? 0 : (dma_env == 2 ? 16 : 32));
+  // cost the third block per CU that covers prologue and store bursts.  So: LDS-DMA where A is row-contiguous; odvae_gemm_select_staging
+  // forces one form everywhere.
+  const int bkt = g_dma_mode < 0 ? (!a_kc ? 32 : 0) : (g_dma_mode == 0 ? 0 : (g_dma_mode == 2 ? 16 : 32));
   if (bkt == 32) {
     const int rc = a_kc && b_kc ? launch_dma(gemm_f32_dma_kernel<true, true>, grid, st, p)
                  : a_kc         ? launch_dma(gemm_f32_dma_kernel<true, false>, grid, st, p)
@@ -765,10 +747,10 @@ static int gemm_smb_impl(int M, int N, int K, float alpha, const float* A, int l
   p.splits = 1; p.k_per_split = ceil_div(K, BK) * BK; p.tiles_m = ceil_div(M, BM);
   p.rowsub = rowdot; p.emul = P; p.sRow = strideRow; p.rowmul = rowmul; p.rowout = nullptr; p.flag = nullptr; p.pred = nullptr;
   dim3 grid(p.tiles_m * ceil_div(N, BN), 1, batch), block(256);
-  if (dma_mode() == 2) {
+  if (g_dma_mode == 2) {
     const int rc = launch_dma(gemm_f32_dma_kernel<true, true, true, 16>, grid, static_cast<hipStream_t>(stream), p, DmaGeom<16>::LDS_B);
     if (rc != ODVAE_OK) return rc;
-  } else if (dma_mode() == 1) {
+  } else if (g_dma_mode == 1) {
     const int rc = launch_dma(gemm_f32_dma_kernel<true, true, true>, grid, static_cast<hipStream_t>(stream), p);
     if (rc != ODVAE_OK) return rc;
   } else {

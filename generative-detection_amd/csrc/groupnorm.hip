@@ -29,24 +29,13 @@ __device__ __forceinline__ float sigmoid_f(float u) { return __builtin_amdgcn_rc
 __device__ __forceinline__ float swish_f(float u) { return u * sigmoid_f(u); }
 
 // streaming accesses of the apply passes: every byte is touched once by this kernel and next by another one a gigabyte later
-#ifndef ODVAE_GN_NT
-#define ODVAE_GN_NT 1
-#endif
 typedef float gn_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld_stream(const float4* p) {
-#if ODVAE_GN_NT
   const gn_f4 v = __builtin_nontemporal_load(reinterpret_cast<const gn_f4*>(p));
   return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
 }
 __device__ __forceinline__ void st_stream(float4* p, float4 v) {
-#if ODVAE_GN_NT
   __builtin_nontemporal_store(gn_f4{v.x, v.y, v.z, v.w}, reinterpret_cast<gn_f4*>(p));
-#else
-  *p = v;
-#endif
 }
 
 // ---- forward statistics -------------------------------------------------------------------------

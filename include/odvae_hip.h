@@ -44,7 +44,7 @@ const char* odvae_target_arch(void);  /* "gfx950" */
 size_t odvae_gemm_f32_workspace_bytes(int M, int N, int K, int batch);
 /* operand staging of the two GEMM entry points: -1 per shape (default: LDS-DMA where A is row-contiguous), 0 through registers,
  * 1 by LDS-DMA (`buffer_load ... lds`, two stages of 32-wide steps), 2 the same with 16-wide steps (four blocks per CU); identical
- * results; returns the previous setting.  Env preset: ODVAE_GEMM_DMA. */
+ * results; returns the previous setting. */
 int odvae_gemm_select_staging(int mode);
 int odvae_gemm_f32(int transA, int transB, int M, int N, int K, float alpha,
                    const float* A, int lda, int64_t strideA,
