@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ_DIR = os.path.join(HERE, "build")
 LIB_PATH = os.path.join(HERE, "libodvae_hip.so")
-HIP_SOURCES = ["gemm_f32.hip", "conv3x3_f32.hip", "conv3x3_wino_f32.hip", "conv3x3_wino4_f32.hip", "conv3x3_wgrad_f32.hip", "conv3x3_wgrad_wino_f32.hip", "groupnorm.hip", "elementwise.hip",
+HIP_SOURCES = ["gemm_f32.hip", "gemm_f32_split.hip", "conv3x3_f32.hip", "conv3x3_wino_f32.hip", "conv3x3_wino4_f32.hip", "conv3x3_wgrad_f32.hip", "conv3x3_wgrad_wino_f32.hip", "groupnorm.hip", "elementwise.hip",
                "gan_f32.hip", "lpips_f32.hip", "patch_u8.hip", "pose_f32.hip", "linear_f32.hip",
                "conv_bf16.hip", "conv_wgrad_bf16.hip", "flash_attn_bf16.hip", "bf16_ops.hip",
                "flash_attn_f32.hip", "anomaly.hip"]
@@ -18,10 +18,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", CSRC]
 # Per-file code-generation switches (none in use).  Tried on flash_attn_bf16.hip: `-mllvm -amdgpu-mfma-vgpr-form=1` removes the
 # 256 v_accvgpr_read/write per 32 MFMAs that hipcc's default register split puts at the loop back-edge of the attention kernels
 # (592 vs 565 TFLOP/s forward), but the D >= 256 forward kernels then return wrong results (tests/test_bf16_gpu.py), so it stays off.
-# In use: -fno-slp-vectorize for the attention file.  At -O3 hipcc packs adjacent f32 multiplies / adds of the softmax sections into
+# In use: -fno-slp-vectorize for the attention file and the bf16-split GEMM (its row sums and splits sit beside MFMAs too).  At -O3 hipcc packs adjacent f32 multiplies / adds of the softmax sections into
 # v_pk_mul_f32 / v_pk_add_f32; beside MFMAs a packed f32 op costs more issue time than the two plain ones it replaces
 # (MI355X_MICROARCH.md, "price of one filler beside MFMAs").
-PER_FILE_FLAGS = {"flash_attn_bf16.hip": ["-fno-slp-vectorize"]}
+PER_FILE_FLAGS = {"flash_attn_bf16.hip": ["-fno-slp-vectorize"], "gemm_f32_split.hip": ["-fno-slp-vectorize"]}
 
 
 def _stale(target, deps):
@@ -33,7 +33,7 @@ def _stale(target, deps):
 
 def _compile(src):
     obj = os.path.join(OBJ_DIR, os.path.basename(src) + ".o")
-    deps = [src, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "bf16_common.h"), os.path.join(CSRC, "gn_finalize.h"), os.path.abspath(__file__)]
+    deps = [src, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "bf16_common.h"), os.path.join(CSRC, "gn_finalize.h"), os.path.join(CSRC, "gemm_f32_tile.h"), os.path.abspath(__file__)]
     if _stale(obj, deps):
         cmd = [HIPCC] + FLAGS + PER_FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -16,12 +16,12 @@
 // consecutive rows, conflict-free).  Both reads use the same k order inside a group of 8:
 // step j of lane half h is k = 8g + 4h + j, so A and B always agree.
 // Split-K (grid.y) covers the long-K/small-MN products (wgrad: K = B*H*W).
-#include "bf16_common.h"   // LDS in 32-bit addresses, LDS-DMA by inline asm
+#include "gemm_f32_tile.h"   // block geometry, GemmParams, output tails (shared with gemm_f32_split.hip); LDS-DMA by inline asm
 #include <type_traits>
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 32;
+using namespace gemm_tile;
 constexpr int LDS_KC = BK + 4;    // [row][k] tile row stride (floats)
 constexpr int LDS_RC = BM + 4;    // [k][row] tile row stride (floats)
 constexpr int TILE_FLOATS = BM * LDS_KC;  // 4608 >= BK*LDS_RC = 4224
@@ -41,28 +41,6 @@ template <int BKT> struct DmaGeom {
   static constexpr int ROW_SHIFT = BKT == 32 ? 3 : 2, SWZ_SHIFT = BKT == 32 ? 1 : 2, SWZ_MASK = SLOTS - 1;
 };
 __device__ __forceinline__ float lds_ld32(unsigned a) { return *(const __attribute__((address_space(3))) float*)(uintptr_t)a; }
-
-struct GemmParams {
-  const float* A; const float* B; float* C;
-  const float* bias; const float* residual;
-  float* partial;      // split-K slabs [split][batch][M][N] or nullptr
-  int M, N, K;
-  int lda, ldb, ldc;
-  int64_t sA, sB, sC;
-  float alpha;
-  int splits, k_per_split;
-  int tiles_m;
-  // softmax-backward epilogue (EPI_SMB kernels only): C = alpha * emul .* (A B^T - rowsub[row]) (* rowmul[row]); emul has C's layout
-  const float* rowsub; const float* emul; int64_t sRow;
-  const float* rowmul;   // EPI_SMB: optional second row factor (1 / l_i when emul holds unnormalised exponentials), or null
-  // EPI_EXPB: C = exp(alpha * (A B^T - rowsub[row])) -- attention scores leave the QK^T product as exponentials relative to a per-row
-  //           upper bound of the scores instead of the row maximum: no separate softmax pass over the T x T tensor
-  // EPI_ROWNORM (A k-contiguous, unsplit): l[row] = sum_k A[row][k] is accumulated beside the products, C = A B / l[row];
-  //           rowout[row] = 1 / l[row] (written by the first column tile); *flag |= 1 where l is not a normal number >= 1e-30
-  float* rowout; int* flag;
-  const int* pred;       // gemm_f32_pred_kernel: nothing happens unless *pred != 0
-};
-constexpr int EPI_NONE = 0, EPI_SMB = 1, EPI_EXPB = 2, EPI_ROWNORM = 3;
 
 // Operand tiles are fetched through a buffer descriptor that starts at the tile's origin (first row of the block, first k of
 // the split): the per-lane byte offsets are computed once, a step only changes a scalar offset, and rows / k beyond the
@@ -245,26 +223,17 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
   const int wm = wave >> 1, wn = wave & 1;
   const int li = lane & 31, h = lane >> 5;
 
-  // Output addressing: 32-bit byte offsets into a buffer descriptor that starts at this block's first row; rows >= M
-  // and columns >= N get an offset past num_records (loads return 0, stores are dropped): no compares, no 64-bit
-  // math per element.  The accumulators START at the residual (the host guarantees alpha == 1 with a residual), so
+  // Output addressing (TileOut): rows >= M and columns >= N get an offset past num_records.
+  // The accumulators START at the residual (the host guarantees alpha == 1 with a residual), so
   // the epilogue is stores only -- vmcnt counts loads and stores in order; a load between stores serialises them.
   const bool to_partial = p.partial != nullptr;
   float* Cb = to_partial ? p.partial + ((int64_t)split * gridDim.z + batch) * (int64_t)p.M * p.N : p.C + batch * p.sC;
   const int ldc = to_partial ? p.N : p.ldc;
-  const unsigned OOB = 0x7FFFFFF0u;
-  const int rows_here = min(BM, p.M - m0);
-  const int tile_bytes = ((rows_here - 1) * ldc + p.N) * 4;
-  unsigned colbyte[2];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int col = n0 + wn * 64 + nt * 32 + li;
-    colbyte[nt] = col < p.N ? (unsigned)col * 4u : OOB;
-  }
-  auto row_byte = [&](int mt, int r) -> unsigned {
-    const int row = wm * 64 + mt * 32 + acc_row(r, lane);   // within the block tile
-    return row < rows_here ? (unsigned)(row * ldc) * 4u : OOB;
-  };
+  TileOut out;
+  out.init(p.M, p.N, ldc, m0, n0);
+  const int rows_here = out.rows_here, tile_bytes = out.tile_bytes;
+  const unsigned (&colbyte)[2] = out.colbyte;
+  auto row_byte = [&](int mt, int r) -> unsigned { return out.row_byte(mt, r); };
 
   f32x16 acc[2][2];
   // per-row vectors (rowsub, rowmul) of this tile: buffer loads whose descriptor ends at the tile's last row -- rows past it read 0, no
@@ -425,7 +394,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
   }      // register-staged form
 
   // epilogue: lane owns column (n0 + wn*64 + nt*32 + li); rows come from the register index.  Stores only.
-  const __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(Cb + (int64_t)m0 * ldc, 0, tile_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t crsrc = out.rsrc(Cb + (int64_t)m0 * ldc);
   float bv[2];
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt)
@@ -452,22 +421,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
     for (int t = 0; t < 2; ++t) rowl[t] += __shfl_xor(rowl[t], 32, 64);
     if (wn == 0 && h == 0) { rl[wm * 64 + li] = rowl[0]; rl[wm * 64 + 32 + li] = rowl[1]; }
     __syncthreads();
-    bool bad = false;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wm * 64 + mt * 32 + acc_row(r, lane);
-        const float l = rl[row];
-        const float rinv = 1.f / l;
-        bad |= row < rows_here && !(l >= 1e-30f && l < 3.0e38f);
-        const unsigned rb_ = row_byte(mt, r);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[mt][nt][r] * rinv), crsrc, rb_ + colbyte[nt], 0, 0);
-        if (tile_n == 0 && wn == 0 && li == 0 && row < rows_here) p.rowout[batch * p.sRow + m0 + row] = rinv;
-      }
-    if (p.flag && __any(bad) && lane == 0) atomicOr(p.flag, 1);
+    store_rownorm(out, crsrc, acc, rl, p, batch, m0, tile_n);
     return;
   }
   if constexpr (SMB) {   // per 32-row half: all loads of the multiplier tile first, then its stores (one half's 32 values live at a time: the
@@ -494,15 +448,7 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
     }
     return;
   }
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const unsigned rb_ = row_byte(mt, r);
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[mt][nt][r] * alpha + bv[nt]), crsrc, rb_ + colbyte[nt], 0, 0);
-    }
+  store_plain(out, crsrc, acc, alpha, bv);
 }
 
 // sums the split-K slabs, then alpha / bias / residual
@@ -541,16 +487,6 @@ int launch_dma(K kern, dim3 grid, hipStream_t st, const GemmParams& p, unsigned 
   }
   hipLaunchKernelGGL(kern, grid, dim3(256), DMA_LDS_B, st, p);
   return ODVAE_OK;
-}
-
-int choose_splits(int M, int N, int K, int batch) {
-  const int64_t tiles = (int64_t)ceil_div(M, BM) * ceil_div(N, BN) * batch;
-  if (tiles >= 512 || K <= 1024) return 1;
-  int64_t s = 512 / tiles;           // two blocks per CU; 1024 / 256 measured 8-12 % slower
-  const int64_t max_by_k = K / 512;  // at least 16 k-tiles per split
-  if (s > max_by_k) s = max_by_k;
-  if (s < 1) s = 1;
-  return (int)s;
 }
 
 }  // namespace
@@ -662,6 +598,7 @@ static int gemm_f32_impl(int transA, int transB, int M, int N, int K, float alph
   hipStream_t st = static_cast<hipStream_t>(stream);
   dim3 grid(p.tiles_m * ceil_div(N, BN), p.splits, batch), block(256);
   const bool a_kc = !transA, b_kc = transB != 0;
+  const bool split = split_eligible(g_dma_mode, transB, M, N, K, batch, bias, residual);
   // 32-bit byte offsets inside one block's operand window (128 rows x the split's k range)
   ODVAE_CHECK_ARG((a_kc ? (int64_t)BM * lda : (int64_t)p.k_per_split * lda) * 4 < 0x7FFFFFF0ll &&
                   (b_kc ? (int64_t)BN * ldb : (int64_t)p.k_per_split * ldb) * 4 < 0x7FFFFFF0ll,
@@ -671,7 +608,10 @@ static int gemm_f32_impl(int transA, int transB, int M, int N, int K, float alph
   // k-contiguous, K = 256: QK^T, dO V^T, 1x1 forward) 122.2 vs 129.3 -- eight steps per block there, and the 64 KB of the two DMA stages
   // cost the third block per CU that covers prologue and store bursts.  So: LDS-DMA where A is row-contiguous; odvae_gemm_select_staging
   // forces one form everywhere.
+  // Deep plain products (K >= 1024, B row-contiguous, unsplit, staging per shape: split_eligible) leave the f32 MFMA altogether: sums of
+  // six bf16 products of exactly split operands, gemm_f32_split.hip.
   const int bkt = g_dma_mode < 0 ? (!a_kc ? 32 : 0) : (g_dma_mode == 0 ? 0 : (g_dma_mode == 2 ? 16 : 32));
+  if (split) return launch_split(p, transA, false, batch, st);
   if (bkt == 32) {
     const int rc = a_kc && b_kc ? launch_dma(gemm_f32_dma_kernel<true, true>, grid, st, p)
                  : a_kc         ? launch_dma(gemm_f32_dma_kernel<true, false>, grid, st, p)
@@ -800,6 +740,7 @@ int odvae_gemm_rownorm_f32(int M, int N, int K, const float* A, int lda, int64_t
   p.sA = strideA; p.sB = strideB; p.sC = strideC; p.alpha = 1.f;
   p.splits = 1; p.k_per_split = ceil_div(K, BK) * BK; p.tiles_m = ceil_div(M, BM);
   p.rowsub = nullptr; p.emul = nullptr; p.sRow = strideRow; p.rowmul = nullptr; p.rowout = rinv; p.flag = flag; p.pred = nullptr;
+  if (split_eligible(g_dma_mode, 0, M, N, K, batch, nullptr, nullptr)) return launch_split(p, 0, true, batch, static_cast<hipStream_t>(stream));
   hipLaunchKernelGGL((gemm_f32_kernel<true, false, EPI_ROWNORM>), dim3(p.tiles_m * ceil_div(N, BN), 1, batch), dim3(256), 0, static_cast<hipStream_t>(stream), p);
   ODVAE_LAUNCH_CHECK("gemm_rownorm");
   return ODVAE_OK;

@@ -1,0 +1,267 @@
+// The T-deep f32 products of the attention (O = P V, dQ = dS K: NN; dV = P^T dO, dK = dS^T Q: TN) on the bf16 matrix pipe.
+//
+// An f32 number x is exactly hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) (round to nearest even;
+// both differences are exact in f32: 8 + 8 + 8 significand bits).  Of the nine cross products of two split operands six are kept,
+// accumulated in f32 by v_mfma_f32_32x32x16_bf16, smallest first within every 16 k:
+//     a_lo b_hi, a_hi b_lo, a_mid b_mid, a_mid b_hi, a_hi b_mid, a_hi b_hi
+// The dropped ones (mid lo, lo mid, lo lo) are below 2^-22 of sum_k |a_k| |b_k|.  Six bf16 MFMAs take 6/16 of the cycles of the f32
+// MFMAs they replace.  No atomics in the sums and a fixed order: two runs give the same bits.  An Inf operand gives x - hi = NaN, so
+// Inf and NaN inputs both come out as NaN (never as a finite number).
+//
+// Block = 256 threads = 4 waves (2x2), block tile 128x128, wave tile 64x64, 32 k per step -- gemm_f32.hip's geometry, whose output
+// tails (gemm_f32_tile.h) are used as they are.  The operands are split in the loader, in registers: a thread fetches eight
+// consecutive k of one row (k-contiguous operand: two 16-byte loads; row-contiguous operand: eight 4-byte loads, lane = row, so a
+// wave reads 256 contiguous bytes per k), splits them and writes one ds_write_b128 per plane.  LDS holds [operand][plane][row][32 k]
+// in bf16, rows of 64 bytes = four 16-byte slots, XOR-swizzled by the row (tile_byte) so that neither the fragment reads nor the
+// loader's writes meet a bank conflict.  One fragment = one ds_read_b128; the
+// transposition of a row-contiguous operand costs nothing.  One LDS stage of 48 KB, the next step's operands wait in registers while
+// this step's MFMAs run; two or three blocks share a CU and cover each other's split / store phases.
+#include "gemm_f32_tile.h"
+
+namespace {
+
+using namespace gemm_tile;
+
+constexpr unsigned PLANE_B = BM * BK * 2;        // 8 192: one bf16 plane of one operand tile
+constexpr unsigned OPER_B = 3 * PLANE_B;         // hi, mid, lo
+constexpr unsigned OOB = 0x7FFFFFF0u;
+constexpr int HI = 0, MID = 1, LO = 2;
+
+// byte of (row, 16-byte slot) inside one plane.  The XOR pattern f(row) = bit 2 of the row | (bit 1 ^ bit 3) << 1 is the one (found by
+// enumeration over the lane groups of MI355X_MICROARCH.md, LDS) that serves both sides: the sixteen rows of every ds_read_b128 lane
+// group fall on sixteen different 16-byte columns of the 256-byte bank row, and the eight consecutive rows of a ds_write_b128 lane
+// group (row-contiguous loader: lane = row, one slot) on the eight columns of the 128-byte one.
+__device__ __forceinline__ unsigned tile_byte(int row, int slot) {
+  const int f = ((row >> 2) & 1) | ((((row >> 1) ^ (row >> 3)) & 1) << 1);
+  return (unsigned)(row * 64 + ((slot ^ f) << 4));
+}
+
+// two floats -> two bf16 in one dword (first in bits 0..15), round to nearest even: a plain cast, which hipcc turns into
+// v_cvt_pk_bf16_f32 and schedules like any other instruction (NaN stays NaN)
+__device__ __forceinline__ unsigned cvt_pk_bf16(float first, float second) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{first, second}, bf16x2));
+}
+
+// x[0..7] (consecutive k of one row) -> the three planes' 16 bytes
+__device__ __forceinline__ void split8(const float (&x)[8], u32x4 (&pl)[3]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float x0 = x[2 * j], x1 = x[2 * j + 1];
+    const unsigned h = cvt_pk_bf16(x0, x1);
+    const float r0 = x0 - bf16_lo(h), r1 = x1 - bf16_hi(h);
+    const unsigned m = cvt_pk_bf16(r0, r1);
+    const float s0 = r0 - bf16_lo(m), s1 = r1 - bf16_hi(m);
+    pl[HI][j] = h; pl[MID][j] = m; pl[LO][j] = cvt_pk_bf16(s0, s1);
+  }
+}
+__device__ __forceinline__ void store_unit(unsigned lds_oper, int row, int slot, const float (&x)[8]) {
+  u32x4 pl[3];
+  split8(x, pl);
+  const unsigned a = lds_oper + tile_byte(row, slot);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) lds_st128(a + q * PLANE_B, pl[q]);
+}
+
+// One operand's loader.  A unit = eight consecutive k of one row; 128 rows x 4 slots = 512 units, two per thread.
+// KC (G[row][k]): unit u = tid + 256 i is row u >> 2, slot u & 3.   RC (G[k][row]): row tid & 127, slot (tid >> 7) + 2 i.
+// Rows past the operand and k past K are never fetched: their offsets are replaced by one past num_records (reads as 0).
+template <bool KC>
+struct SplitLoader {
+  __amdgpu_buffer_rsrc_t rsrc;
+  unsigned voff[2];
+  unsigned ld_bytes;
+  int kvalid;
+  float x[2][8];
+
+  __device__ __forceinline__ void init(const float* G, int ld, int row0, int nrows, int K) {
+    const int tid = threadIdx.x;
+    kvalid = K;
+    ld_bytes = (unsigned)ld * 4u;
+    if (KC) {
+      const int rows = min(BM, nrows - row0);
+      const int64_t bytes = ((int64_t)(rows - 1) * ld + K) * 4;
+      rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G) + (int64_t)row0 * ld, 0, (int)(bytes < 0x7FFFFFF0ll ? bytes : 0x7FFFFFF0ll), 0x00020000);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int u = tid + 256 * i;
+        voff[i] = (u >> 2) < rows ? (unsigned)(((u >> 2) * ld + 8 * (u & 3)) * 4) : OOB;
+      }
+    } else {
+      const int64_t bytes = ((int64_t)(K - 1) * ld + (nrows - row0)) * 4;
+      rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(G) + row0, 0, (int)(bytes < 0x7FFFFFF0ll ? bytes : 0x7FFFFFF0ll), 0x00020000);
+      const int row = tid & 127;
+      voff[0] = row0 + row < nrows ? (unsigned)((tid >> 7) * 8 * ld + row) * 4u : OOB;
+      voff[1] = 0;
+    }
+  }
+  // k0 = first k of the step (uniform).  TAIL: the step may reach past K (the first and the last step are fetched this way; every
+  // other one carries no compare and no select)
+  template <bool TAIL>
+  __device__ __forceinline__ void load(int k0) {
+    const int tid = threadIdx.x;
+    const bool tail = TAIL && k0 + BK > kvalid;
+    if (KC) {
+      const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane(k0) * 4u;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {     // K % 4 == 0: a 16-byte load is inside or outside as a whole
+          unsigned vo = voff[i] + 16u * q;
+          if (tail && k0 + 8 * ((tid + 256 * i) & 3) + 4 * q >= kvalid) vo = OOB;
+          const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, soff, 0);
+          x[i][4 * q] = __uint_as_float(v.x); x[i][4 * q + 1] = __uint_as_float(v.y);
+          x[i][4 * q + 2] = __uint_as_float(v.z); x[i][4 * q + 3] = __uint_as_float(v.w);
+        }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane(k0 + 16 * i + j) * ld_bytes;
+          unsigned vo = voff[0];
+          if (tail && k0 + 8 * (tid >> 7) + 16 * i + j >= kvalid) vo = OOB;
+          x[i][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, vo, soff, 0));
+        }
+    }
+  }
+  __device__ __forceinline__ void store(unsigned lds_oper) const {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if (KC) store_unit(lds_oper, (tid + 256 * i) >> 2, tid & 3, x[i]);
+      else    store_unit(lds_oper, tid & 127, (tid >> 7) + 2 * i, x[i]);
+    }
+  }
+};
+
+template <bool A_KC, bool ROWNORM>
+// three blocks per CU (168 registers, 3 x 48 KB of LDS): 5 % faster than two on the attention shapes; s_setprio around the MFMAs: nothing
+__global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(GemmParams p) {
+  static_assert(!ROWNORM || A_KC, "the row sums are taken by the k-contiguous loader");
+  __shared__ __attribute__((aligned(16))) char smem[2 * OPER_B];
+  const int tile_m = blockIdx.x % p.tiles_m, tile_n = blockIdx.x / p.tiles_m, batch = blockIdx.z;
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const float* A = p.A + batch * p.sA;
+  const float* B = p.B + batch * p.sB;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, h = lane >> 5;
+
+  TileOut out;
+  out.init(p.M, p.N, p.ldc, m0, n0);
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+
+  const unsigned ldsA = lds_addr_of(smem), ldsB = ldsA + OPER_B;
+  // fragment of 32-row tile t, 16-k half kk, plane q: adr[kk] + t * 2048 + q * PLANE_B (rows t*32 + li share li's swizzle: it looks at row bits 1..3)
+  unsigned adrA[2], adrB[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    adrA[kk] = ldsA + tile_byte(wm * 64 + li, 2 * kk + h);
+    adrB[kk] = ldsB + tile_byte(wn * 64 + li, 2 * kk + h);
+  }
+
+  SplitLoader<A_KC> fa;
+  SplitLoader<false> fb;
+  fa.init(A, p.lda, m0, p.M, p.K);
+  fb.init(B, p.ldb, n0, p.N, p.K);
+  float rowl[2] = {0.f, 0.f};      // ROWNORM: this thread's share (its 8 of every 32 k) of the sums of rows (tid >> 2) + {0, 64}
+  auto stage = [&]() {
+    if constexpr (ROWNORM) {       // from the unsplit values, fixed order; k past K reads as 0
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        rowl[i] += ((fa.x[i][0] + fa.x[i][1]) + (fa.x[i][2] + fa.x[i][3])) + ((fa.x[i][4] + fa.x[i][5]) + (fa.x[i][6] + fa.x[i][7]));
+    }
+    fa.store(ldsA);
+    fb.store(ldsB);
+  };
+  auto products = [&]() {
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      bf16x8 a[2][3], b[2][3];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          a[t][q] = frag_from_u32x4(lds_ld128(adrA[kk] + t * 2048u + q * PLANE_B));
+          b[t][q] = frag_from_u32x4(lds_ld128(adrB[kk] + t * 2048u + q * PLANE_B));
+        }
+      constexpr int ORDER[6][2] = {{LO, HI}, {HI, LO}, {MID, MID}, {MID, HI}, {HI, MID}, {HI, HI}};   // smallest first
+#pragma unroll
+      for (int o = 0; o < 6; ++o)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = mfma_bf16(a[mt][ORDER[o][0]], b[nt][ORDER[o][1]], acc[mt][nt]);
+    }
+  };
+  fa.template load<true>(0);
+  fb.template load<true>(0);
+  stage();
+  __syncthreads();
+  int k0 = BK;      // first k of the step being fetched
+  for (; k0 + BK <= p.K; k0 += BK) {
+    fa.template load<false>(k0);
+    fb.template load<false>(k0);
+    products();
+    __syncthreads();
+    stage();
+    __syncthreads();
+  }
+  if (k0 < p.K) {      // a last, partial step
+    fa.template load<true>(k0);
+    fb.template load<true>(k0);
+    products();
+    __syncthreads();
+    stage();
+    __syncthreads();
+  }
+  products();
+  __syncthreads();
+
+  const __amdgpu_buffer_rsrc_t crsrc = out.rsrc(p.C + batch * p.sC + (int64_t)m0 * p.ldc);
+  if constexpr (ROWNORM) {
+    float* rl = reinterpret_cast<float*>(smem);      // [128]; the operand tiles are dead: the loop ended on a barrier
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      rowl[i] += __shfl_xor(rowl[i], 1, 64);
+      rowl[i] += __shfl_xor(rowl[i], 2, 64);
+    }
+    if ((threadIdx.x & 3) == 0) { rl[threadIdx.x >> 2] = rowl[0]; rl[64 + (threadIdx.x >> 2)] = rowl[1]; }
+    __syncthreads();
+    store_rownorm(out, crsrc, acc, rl, p, batch, m0, tile_n);
+  } else {
+    const float bv[2] = {0.f, 0.f};
+    store_plain(out, crsrc, acc, p.alpha, bv);
+  }
+}
+
+}  // namespace
+
+namespace gemm_tile {
+
+// The one dispatch rule of both entry points (odvae_gemm_f32, odvae_gemm_rownorm_f32): the bf16-split form runs where the
+// contraction is deep and the launch is neither tuned by hand nor anything but a plain batched product:
+//   staging per shape (a forced staging mode means "the f32 MFMA kernel"), no split-K, B row-contiguous (NN / TN),
+//   K >= 1024, no bias, no residual.
+bool split_eligible(int staging_mode, int transB, int M, int N, int K, int batch, const float* bias, const float* residual) {
+  return staging_mode == -1 && choose_splits(M, N, K, batch) == 1 && transB == 0 && K >= 1024 && !bias && !residual;
+}
+
+int launch_split(const GemmParams& p, int transA, bool rownorm, int batch, hipStream_t st) {
+  const dim3 grid(p.tiles_m * ceil_div(p.N, BN), 1, batch), block(256);
+  if (rownorm)       hipLaunchKernelGGL((gemm_f32_split_kernel<true, true>), grid, block, 0, st, p);
+  else if (!transA)  hipLaunchKernelGGL((gemm_f32_split_kernel<true, false>), grid, block, 0, st, p);
+  else               hipLaunchKernelGGL((gemm_f32_split_kernel<false, false>), grid, block, 0, st, p);
+  ODVAE_LAUNCH_CHECK("gemm_f32 (bf16 split)");
+  return ODVAE_OK;
+}
+
+}  // namespace gemm_tile

@@ -40,11 +40,17 @@ const char* odvae_target_arch(void);  /* "gfx950" */
  * C[b] = alpha * op(A[b]) * op(B[b]) (+ bias[col]) (+ residual[b]); row-major;
  * transA=0: A is [M][K]; transA=1: A is stored [K][M]; transB=0: B is [K][N]; transB=1: B is stored [N][K].
  * Stands in for the 1x1 convolutions (nin_shortcut, AttnBlock q/k/v/proj_out, quant_conv_obj/pose,
- * post_quant_conv: src/models/autoencoder.py:88-90,179-180) and AttnBlock's torch.bmm products. */
+ * post_quant_conv: src/models/autoencoder.py:88-90,179-180) and AttnBlock's torch.bmm products.
+ * Deep plain products -- staging per shape (below), unsplit (odvae_gemm_f32_workspace_bytes == 0), transB = 0, K >= 1024, no bias, no
+ * residual: the attention's P V, P^T dO, dS K, dS^T Q at 4 096 tokens from batch 8 up -- do not run on v_mfma_f32_32x32x2_f32: each f32
+ * operand is split exactly into three bf16 numbers in the loader and six of the nine cross products are accumulated in f32 on the bf16
+ * MFMA (gemm_f32_split.hip).  The result is within 2^-22 of sum_k |a_k| |b_k| of the f32 kernel's (the dropped products), deterministic;
+ * an Inf operand yields NaN.  odvae_gemm_select_staging(0 | 1 | 2) forces the f32 MFMA kernel at every shape. */
 size_t odvae_gemm_f32_workspace_bytes(int M, int N, int K, int batch);
 /* operand staging of the two GEMM entry points: -1 per shape (default: LDS-DMA where A is row-contiguous), 0 through registers,
  * 1 by LDS-DMA (`buffer_load ... lds`, two stages of 32-wide steps), 2 the same with 16-wide steps (four blocks per CU); identical
- * results; returns the previous setting. */
+ * results among 0 / 1 / 2, which always mean the f32 MFMA kernel; -1 also lets deep plain products run as bf16 splits (above); returns
+ * the previous setting. */
 int odvae_gemm_select_staging(int mode);
 int odvae_gemm_f32(int transA, int transB, int M, int N, int K, float alpha,
                    const float* A, int lda, int64_t strideA,
@@ -216,6 +222,8 @@ int odvae_gemm_softmax_bwd_f32(int M, int N, int K, float alpha, const float* A,
  *   odvae_attn_row_bound_f32: qkv [N][T][3C] (q | k | v per token) -> bound [N*T] (unscaled), *flag = 0; nk_scratch [N*T]
  *   odvae_gemm_exp_bound_f32: E = exp(alpha * (A B^T - rowbound[row])); A [M][K], B [N][K]
  *   odvae_gemm_rownorm_f32:   C = (A B) / l[row], l = row sums of A [M][K]; B [K][N]; rinv [batch][M] = 1 / l; *flag |= (some l < 1e-30 or not finite)
+ *                             (under odvae_gemm_f32's rule for deep products A B is a sum of six bf16 products of split operands; l is summed from
+ *                             the unsplit f32 values and the flag condition is the same)
  *   odvae_gemm_pred_f32:      odvae_gemm_f32 (unsplit shapes, no bias / residual) under the predicate
  *   odvae_softmax_rows_pred_f32: odvae_softmax_rows_f32 under the predicate, and ones[row] = 1
  * Backward with P given as (E, rinv): odvae_rowdot_scale_f32 (out[i] = a_i . b_i, a_scaled[i][:] = a[i][:] * row_scale[i]: D_i and dO_i / l_i),

@@ -9,6 +9,7 @@
 //   kernel here is timed separately.
 // Block = 128 x 128 outputs, 4 waves of 64 x 64 (2 x 2 tiles of v_mfma_f32_32x32x16_bf16), K in steps of 32 through a double-buffered LDS stage
 // ([plane][row][32 + 8 pad] bf16: conflict-free ds_read_b128), operands staged through registers.
+// The kernel that was shipped after this probe (operands split in the loader, T-deep products only): generative-detection_amd/csrc/gemm_f32_split.hip.
 // Build: hipcc --offload-arch=gfx950 -O3 tools/gemm_bf16x3_probe.hip -o tools/bin/gemm_bf16x3 ; run on the GPU box: tools/bin/gemm_bf16x3
 #include <hip/hip_runtime.h>
 #include <math.h>
