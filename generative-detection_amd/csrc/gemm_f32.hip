@@ -236,26 +236,9 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
   auto row_byte = [&](int mt, int r) -> unsigned { return out.row_byte(mt, r); };
 
   f32x16 acc[2][2];
-  // per-row vectors (rowsub, rowmul) of this tile: buffer loads whose descriptor ends at the tile's last row -- rows past it read 0, no
-  // guard (32 guarded loads per lane, each waited for on its own, cost ~4 us per block: 8 % of a QK^T-shaped tile)
   float rmv[2][16];      // SMB: rowmul[row] (or 1)
   if constexpr (SMB || EXPB) {   // accumulators start at -rowsub[row]: the products then add up to dP - D (EXPB: to s - bound)
-    const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.rowsub) + batch * p.sRow + m0, 0, rows_here * 4, 0x00020000);
-    const bool has_mul = SMB && p.rowmul != nullptr;
-    const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_mul ? p.rowmul : p.rowsub) + batch * p.sRow + m0, 0, has_mul ? rows_here * 4 : 0, 0x00020000);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wm * 64 + mt * 32 + acc_row(r, lane);
-        const float d = -__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(srs, row * 4, 0, 0));
-        acc[mt][0][r] = d; acc[mt][1][r] = d;
-        if constexpr (SMB) {
-          const float m = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(mrs, row * 4, 0, 0));
-          rmv[mt][r] = has_mul ? m : 1.f;
-        }
-      }
+    GEMM_TILE_FETCH_ROW_VECTORS(out, wm, lane, p, batch, m0, SMB, acc, rmv);
   } else if (!to_partial && p.residual) {
     const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(p.residual) + batch * p.sC + (int64_t)m0 * ldc, 0, tile_bytes, 0x00020000);
@@ -400,17 +383,8 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
   for (int nt = 0; nt < 2; ++nt)
     bv[nt] = (!to_partial && p.bias) ? p.bias[min(n0 + wn * 64 + nt * 32 + li, p.N - 1)] : 0.f;
   const float alpha = to_partial ? 1.f : p.alpha;
-  if constexpr (EXPB) {  // exponentials of (score - row bound): exp2 of one product
-    const float a2 = alpha * 1.44269504088896f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const unsigned rb_ = row_byte(mt, r);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(__builtin_amdgcn_exp2f(acc[mt][nt][r] * a2)), crsrc, rb_ + colbyte[nt], 0, 0);
-      }
+  if constexpr (EXPB) {
+    GEMM_TILE_STORE_EXPB(out, crsrc, acc, alpha);
     return;
   }
   if constexpr (ROWNORM) {
@@ -424,28 +398,10 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p, float* smem, int 
     store_rownorm(out, crsrc, acc, rl, p, batch, m0, tile_n);
     return;
   }
-  if constexpr (SMB) {   // per 32-row half: all loads of the multiplier tile first, then its stores (one half's 32 values live at a time: the
-                         // kernel fits 168 registers and three blocks share a CU, so that a block's epilogue runs under two others' MFMAs)
+  if constexpr (SMB) {
     const __amdgpu_buffer_rsrc_t ersrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(p.emul) + batch * p.sC + (int64_t)m0 * ldc, 0, tile_bytes, 0x00020000);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      float pv[2][16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const unsigned rb_ = row_byte(mt, r);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-          pv[nt][r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ersrc, rb_ + colbyte[nt], 0, 0));
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const unsigned rb_ = row_byte(mt, r);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[mt][nt][r] * (alpha * rmv[mt][r]) * pv[nt][r]), crsrc, rb_ + colbyte[nt], 0, 0);
-      }
-    }
+    GEMM_TILE_STORE_SMB(out, crsrc, ersrc, acc, alpha, rmv);
     return;
   }
   store_plain(out, crsrc, acc, alpha, bv);
@@ -611,7 +567,7 @@ static int gemm_f32_impl(int transA, int transB, int M, int N, int K, float alph
   // Deep plain products (K >= 1024, B row-contiguous, unsplit, staging per shape: split_eligible) leave the f32 MFMA altogether: sums of
   // six bf16 products of exactly split operands, gemm_f32_split.hip.
   const int bkt = g_dma_mode < 0 ? (!a_kc ? 32 : 0) : (g_dma_mode == 0 ? 0 : (g_dma_mode == 2 ? 16 : 32));
-  if (split) return launch_split(p, transA, false, batch, st);
+  if (split) return launch_split(p, transA, EPI_NONE, batch, st);
   if (bkt == 32) {
     const int rc = a_kc && b_kc ? launch_dma(gemm_f32_dma_kernel<true, true>, grid, st, p)
                  : a_kc         ? launch_dma(gemm_f32_dma_kernel<true, false>, grid, st, p)
@@ -686,6 +642,10 @@ static int gemm_smb_impl(int M, int N, int K, float alpha, const float* A, int l
   p.sA = strideA; p.sB = strideB; p.sC = strideC; p.alpha = alpha;
   p.splits = 1; p.k_per_split = ceil_div(K, BK) * BK; p.tiles_m = ceil_div(M, BM);
   p.rowsub = rowdot; p.emul = P; p.sRow = strideRow; p.rowmul = rowmul; p.rowout = nullptr; p.flag = nullptr; p.pred = nullptr;
+  if (split_tt_eligible(g_dma_mode, M, N, K, batch)) {
+    ODVAE_CHECK_ARG((int64_t)BM * lda * 4 < 0x7FFFFFF0ll && (int64_t)BN * ldb * 4 < 0x7FFFFFF0ll, "gemm_softmax_bwd: one block's operand window exceeds 2 GiB");
+    return launch_split(p, 0, EPI_SMB, batch, static_cast<hipStream_t>(stream));
+  }
   dim3 grid(p.tiles_m * ceil_div(N, BN), 1, batch), block(256);
   if (g_dma_mode == 2) {
     const int rc = launch_dma(gemm_f32_dma_kernel<true, true, true, 16>, grid, static_cast<hipStream_t>(stream), p, DmaGeom<16>::LDS_B);
@@ -717,6 +677,10 @@ int odvae_gemm_exp_bound_f32(int M, int N, int K, float alpha,
   p.sA = strideA; p.sB = strideB; p.sC = strideC; p.alpha = alpha;
   p.splits = 1; p.k_per_split = ceil_div(K, BK) * BK; p.tiles_m = ceil_div(M, BM);
   p.rowsub = rowbound; p.emul = nullptr; p.sRow = strideRow; p.rowmul = nullptr; p.rowout = nullptr; p.flag = nullptr; p.pred = nullptr;
+  if (split_tt_eligible(g_dma_mode, M, N, K, batch)) {
+    ODVAE_CHECK_ARG((int64_t)BM * lda * 4 < 0x7FFFFFF0ll && (int64_t)BN * ldb * 4 < 0x7FFFFFF0ll, "gemm_exp_bound: one block's operand window exceeds 2 GiB");
+    return launch_split(p, 0, EPI_EXPB, batch, static_cast<hipStream_t>(stream));
+  }
   hipLaunchKernelGGL((gemm_f32_kernel<true, true, EPI_EXPB>), dim3(p.tiles_m * ceil_div(N, BN), 1, batch), dim3(256), 0, static_cast<hipStream_t>(stream), p);
   ODVAE_LAUNCH_CHECK("gemm_exp_bound");
   return ODVAE_OK;
@@ -740,7 +704,7 @@ int odvae_gemm_rownorm_f32(int M, int N, int K, const float* A, int lda, int64_t
   p.sA = strideA; p.sB = strideB; p.sC = strideC; p.alpha = 1.f;
   p.splits = 1; p.k_per_split = ceil_div(K, BK) * BK; p.tiles_m = ceil_div(M, BM);
   p.rowsub = nullptr; p.emul = nullptr; p.sRow = strideRow; p.rowmul = nullptr; p.rowout = rinv; p.flag = flag; p.pred = nullptr;
-  if (split_eligible(g_dma_mode, 0, M, N, K, batch, nullptr, nullptr)) return launch_split(p, 0, true, batch, static_cast<hipStream_t>(stream));
+  if (split_eligible(g_dma_mode, 0, M, N, K, batch, nullptr, nullptr)) return launch_split(p, 0, EPI_ROWNORM, batch, static_cast<hipStream_t>(stream));
   hipLaunchKernelGGL((gemm_f32_kernel<true, false, EPI_ROWNORM>), dim3(p.tiles_m * ceil_div(N, BN), 1, batch), dim3(256), 0, static_cast<hipStream_t>(stream), p);
   ODVAE_LAUNCH_CHECK("gemm_rownorm");
   return ODVAE_OK;

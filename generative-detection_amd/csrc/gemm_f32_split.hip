@@ -1,4 +1,5 @@
-// The T-deep f32 products of the attention (O = P V, dQ = dS K: NN; dV = P^T dO, dK = dS^T Q: TN) on the bf16 matrix pipe.
+// The f32 products of the attention on the bf16 matrix pipe: the T-deep ones (O = P V, dQ = dS K: NN; dV = P^T dO, dK = dS^T Q: TN) and
+// the two that write T x T (E = exp(alpha (Q K^T - bound)), dS = alpha E rinv (dO V^T - D): NT, both operands k-contiguous).
 //
 // An f32 number x is exactly hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) (round to nearest even;
 // both differences are exact in f32: 8 + 8 + 8 significand bits).  Of the nine cross products of two split operands six are kept,
@@ -136,10 +137,14 @@ struct SplitLoader {
   }
 };
 
-template <bool A_KC, bool ROWNORM>
-// three blocks per CU (168 registers, 3 x 48 KB of LDS): 5 % faster than two on the attention shapes; s_setprio around the MFMAs: nothing
+template <bool A_KC, bool B_KC, int EPI>
+// three blocks per CU (168 registers, 3 x 48 KB of LDS): 5 % faster than two on the T-deep attention shapes, 5-6 % on the T x T ones at
+// K = 256 and 11-27 % at K = 128 (few steps deep: two other blocks' MFMAs cover a block's first split and its 64 KB tail);
+// s_setprio around the MFMAs: nothing
 __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(GemmParams p) {
+  constexpr bool ROWNORM = EPI == EPI_ROWNORM, EXPB = EPI == EPI_EXPB, SMB = EPI == EPI_SMB;
   static_assert(!ROWNORM || A_KC, "the row sums are taken by the k-contiguous loader");
+  static_assert(!(EXPB || SMB) || (A_KC && B_KC), "the T x T tails belong to the NT form");
   __shared__ __attribute__((aligned(16))) char smem[2 * OPER_B];
   const int tile_m = blockIdx.x % p.tiles_m, tile_n = blockIdx.x / p.tiles_m, batch = blockIdx.z;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
@@ -169,7 +174,7 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(GemmParams p) {
   }
 
   SplitLoader<A_KC> fa;
-  SplitLoader<false> fb;
+  SplitLoader<B_KC> fb;
   fa.init(A, p.lda, m0, p.M, p.K);
   fb.init(B, p.ldb, n0, p.N, p.K);
   float rowl[2] = {0.f, 0.f};      // ROWNORM: this thread's share (its 8 of every 32 k) of the sums of rows (tid >> 2) + {0, 64}
@@ -237,6 +242,26 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(GemmParams p) {
     if ((threadIdx.x & 3) == 0) { rl[threadIdx.x >> 2] = rowl[0]; rl[64 + (threadIdx.x >> 2)] = rowl[1]; }
     __syncthreads();
     store_rownorm(out, crsrc, acc, rl, p, batch, m0, tile_n);
+  } else if constexpr (EXPB || SMB) {
+    // -rowsub[row] joins the finished sum (the f32 kernel starts its accumulators there): the six products of every 16 k stay
+    // "smallest first" among themselves, the subtraction rounds once, and the row vectors take registers only after the loop
+    f32x16 nsub[2][2];
+    float rmv[2][16];
+    if constexpr (SMB) __builtin_amdgcn_sched_barrier(0);      // the tail's 96 loads stay behind the last MFMAs' operands (else: one spill)
+    GEMM_TILE_FETCH_ROW_VECTORS(out, wm, lane, p, batch, m0, SMB, nsub, rmv);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[mt][nt][r] += nsub[mt][nt][r];
+    if constexpr (EXPB) {
+      GEMM_TILE_STORE_EXPB(out, crsrc, acc, p.alpha);
+    } else {
+      const __amdgpu_buffer_rsrc_t ersrc = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<float*>(p.emul) + batch * p.sC + (int64_t)m0 * p.ldc, 0, out.tile_bytes, 0x00020000);
+      GEMM_TILE_STORE_SMB(out, crsrc, ersrc, acc, p.alpha, rmv);
+    }
   } else {
     const float bv[2] = {0.f, 0.f};
     store_plain(out, crsrc, acc, p.alpha, bv);
@@ -247,19 +272,32 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(GemmParams p) {
 
 namespace gemm_tile {
 
-// The one dispatch rule of both entry points (odvae_gemm_f32, odvae_gemm_rownorm_f32): the bf16-split form runs where the
-// contraction is deep and the launch is neither tuned by hand nor anything but a plain batched product:
+// The dispatch rule of odvae_gemm_f32 and odvae_gemm_rownorm_f32: the bf16-split form runs where the contraction is deep and the
+// launch is neither tuned by hand nor anything but a plain batched product:
 //   staging per shape (a forced staging mode means "the f32 MFMA kernel"), no split-K, B row-contiguous (NN / TN),
 //   K >= 1024, no bias, no residual.
 bool split_eligible(int staging_mode, int transB, int M, int N, int K, int batch, const float* bias, const float* residual) {
   return staging_mode == -1 && choose_splits(M, N, K, batch) == 1 && transB == 0 && K >= 1024 && !bias && !residual;
 }
 
-int launch_split(const GemmParams& p, int transA, bool rownorm, int batch, hipStream_t st) {
+// The dispatch rule of the two T x T products (odvae_gemm_exp_bound_f32, odvae_gemm_softmax_bwd[_scaled]_f32; NT, K = the channels):
+//   staging per shape (a forced staging mode means "the f32 MFMA kernel" here too), enough 128 x 128 blocks to fill the chip
+//   twice over (512, choose_splits' threshold: the T = 256 mid blocks stay where they are), K >= 64.
+// The lower bound on K, measured at T = 4096, batch 32 (ms per launch, split vs f32 MFMA; E first, dS second): K = 256 1.50 vs 2.15 and
+// 1.67 vs 2.36, K = 128 0.87 vs 1.22 and 1.06 vs 1.45, K = 64 0.59 vs 0.73 and 0.88 vs 0.97, K = 32 0.53 vs 0.52 and 0.80 vs 0.83: a
+// single step deep both forms take what the 2.1 GB store takes (4 TB/s) and the second form buys nothing.
+constexpr int SPLIT_TT_MIN_K = 64;
+bool split_tt_eligible(int staging_mode, int M, int N, int K, int batch) {
+  return staging_mode == -1 && (int64_t)ceil_div(M, BM) * ceil_div(N, BN) * batch >= 512 && K >= SPLIT_TT_MIN_K;
+}
+
+int launch_split(const GemmParams& p, int transA, int epi, int batch, hipStream_t st) {
   const dim3 grid(p.tiles_m * ceil_div(p.N, BN), 1, batch), block(256);
-  if (rownorm)       hipLaunchKernelGGL((gemm_f32_split_kernel<true, true>), grid, block, 0, st, p);
-  else if (!transA)  hipLaunchKernelGGL((gemm_f32_split_kernel<true, false>), grid, block, 0, st, p);
-  else               hipLaunchKernelGGL((gemm_f32_split_kernel<false, false>), grid, block, 0, st, p);
+  if (epi == EPI_EXPB)          hipLaunchKernelGGL((gemm_f32_split_kernel<true, true, EPI_EXPB>), grid, block, 0, st, p);
+  else if (epi == EPI_SMB)      hipLaunchKernelGGL((gemm_f32_split_kernel<true, true, EPI_SMB>), grid, block, 0, st, p);
+  else if (epi == EPI_ROWNORM)  hipLaunchKernelGGL((gemm_f32_split_kernel<true, false, EPI_ROWNORM>), grid, block, 0, st, p);
+  else if (!transA)             hipLaunchKernelGGL((gemm_f32_split_kernel<true, false, EPI_NONE>), grid, block, 0, st, p);
+  else                          hipLaunchKernelGGL((gemm_f32_split_kernel<false, false, EPI_NONE>), grid, block, 0, st, p);
   ODVAE_LAUNCH_CHECK("gemm_f32 (bf16 split)");
   return ODVAE_OK;
 }

@@ -106,9 +106,72 @@ __device__ __forceinline__ void store_rownorm(const TileOut& o, __amdgpu_buffer_
   if (p.flag && __any(bad) && o.lane == 0) atomicOr(p.flag, 1);
 }
 
-// The bf16-split form (gemm_f32_split.hip): true when this product runs there, see split_eligible
+// The EPI_EXPB / EPI_SMB pieces below are shared as TEXT, not as functions: hipcc optimises a callee on its own before it inlines it,
+// and the tails of the f32 kernels then come out with one v_mul_lo_u32 per output row (41 against 9, as store_plain's do) instead of
+// the add chains they were measured with.  Expanded in place they assemble to the same instructions as when they were written there.
+// `o` is the block's TileOut, `p` its GemmParams, `wm` and `lane` the thread's wave row and lane.
+
+// The per-row vectors of this block tile as the lane's accumulator registers see them: seed[mt][nt][r] = -rowsub[row] (f32x16 [2][2]),
+// and, where MUL, rmv[mt][r] = rowmul[row] (1 when rowmul is null).  Buffer loads whose descriptor ends at the tile's last row -- rows
+// past it read 0, no guard (32 guarded loads per lane, each waited for on its own, cost ~4 us per block: 8 % of a QK^T-shaped tile)
+#define GEMM_TILE_FETCH_ROW_VECTORS(o, wm, lane, p, batch, m0, MUL, seed, rmv)                                                            \
+  {                                                                                                                                      \
+    const __amdgpu_buffer_rsrc_t srs_ =                                                                                                  \
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>((p).rowsub) + (batch) * (p).sRow + (m0), 0, (o).rows_here * 4, 0x00020000);  \
+    const bool has_mul_ = (MUL) && (p).rowmul != nullptr;                                                                                \
+    const __amdgpu_buffer_rsrc_t mrs_ = __builtin_amdgcn_make_buffer_rsrc(                                                               \
+        const_cast<float*>(has_mul_ ? (p).rowmul : (p).rowsub) + (batch) * (p).sRow + (m0), 0, has_mul_ ? (o).rows_here * 4 : 0, 0x00020000); \
+    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; ++mt_)                                                                                  \
+      _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) {                                                                                \
+        const int row_ = (wm) * 64 + mt_ * 32 + acc_row(r_, lane);                                                                       \
+        const float d_ = -__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(srs_, row_ * 4, 0, 0));                                   \
+        (seed)[mt_][0][r_] = d_; (seed)[mt_][1][r_] = d_;                                                                                \
+        if constexpr (MUL) {                                                                                                             \
+          const float m_ = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(mrs_, row_ * 4, 0, 0));                                  \
+          (rmv)[mt_][r_] = has_mul_ ? m_ : 1.f;                                                                                          \
+        }                                                                                                                                \
+      }                                                                                                                                  \
+  }
+
+// EPI_EXPB tail: acc holds score - row bound; C = exp(alpha * acc) as exp2 of one product.  Stores only.
+#define GEMM_TILE_STORE_EXPB(o, crsrc, acc, alpha)                                                                                       \
+  {                                                                                                                                      \
+    const float a2_ = (alpha) * 1.44269504088896f;                                                                                       \
+    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; ++mt_)                                                                                  \
+      _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) {                                                                                \
+        const unsigned rb_ = (o).row_byte(mt_, r_);                                                                                      \
+        _Pragma("unroll") for (int nt_ = 0; nt_ < 2; ++nt_)                                                                              \
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(__builtin_amdgcn_exp2f((acc)[mt_][nt_][r_] * a2_)), crsrc,               \
+                                                rb_ + (o).colbyte[nt_], 0, 0);                                                           \
+      }                                                                                                                                  \
+  }
+
+// EPI_SMB tail: acc holds dP - D; C = acc * (alpha * rmv[row]) * emul (ersrc: emul's descriptor, laid out like C's).  Per 32-row half:
+// all loads of the multiplier tile first, then its stores (one half's 32 values live at a time: the kernels fit 168 registers and three
+// blocks share a CU, so that a block's epilogue runs under two others' MFMAs).  C may alias emul: a lane reads what it then writes.
+#define GEMM_TILE_STORE_SMB(o, crsrc, ersrc, acc, alpha, rmv)                                                                            \
+  {                                                                                                                                      \
+    _Pragma("unroll") for (int mt_ = 0; mt_ < 2; ++mt_) {                                                                                \
+      float pv_[2][16];                                                                                                                  \
+      _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) {                                                                                \
+        const unsigned rb_ = (o).row_byte(mt_, r_);                                                                                      \
+        _Pragma("unroll") for (int nt_ = 0; nt_ < 2; ++nt_)                                                                              \
+          pv_[nt_][r_] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ersrc, rb_ + (o).colbyte[nt_], 0, 0));                     \
+      }                                                                                                                                  \
+      _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) {                                                                                \
+        const unsigned rb_ = (o).row_byte(mt_, r_);                                                                                      \
+        _Pragma("unroll") for (int nt_ = 0; nt_ < 2; ++nt_)                                                                              \
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((acc)[mt_][nt_][r_] * ((alpha) * (rmv)[mt_][r_]) * pv_[nt_][r_]), crsrc, \
+                                                rb_ + (o).colbyte[nt_], 0, 0);                                                           \
+      }                                                                                                                                  \
+    }                                                                                                                                    \
+  }
+
+// The bf16-split form (gemm_f32_split.hip): true when this product runs there, see split_eligible (NN / TN, deep K) and
+// split_tt_eligible (the NT products with the EPI_EXPB / EPI_SMB tails)
 bool split_eligible(int staging_mode, int transB, int M, int N, int K, int batch, const float* bias, const float* residual);
-// launches it; transA selects NN / TN, rownorm the EPI_ROWNORM tail (NN only)
-int launch_split(const GemmParams& p, int transA, bool rownorm, int batch, hipStream_t st);
+bool split_tt_eligible(int staging_mode, int M, int N, int K, int batch);
+// launches it; epi = EPI_NONE (transA selects NN / TN), EPI_ROWNORM (NN), EPI_EXPB or EPI_SMB (NT)
+int launch_split(const GemmParams& p, int transA, int epi, int batch, hipStream_t st);
 
 }  // namespace gemm_tile

@@ -49,8 +49,8 @@ const char* odvae_target_arch(void);  /* "gfx950" */
 size_t odvae_gemm_f32_workspace_bytes(int M, int N, int K, int batch);
 /* operand staging of the two GEMM entry points: -1 per shape (default: LDS-DMA where A is row-contiguous), 0 through registers,
  * 1 by LDS-DMA (`buffer_load ... lds`, two stages of 32-wide steps), 2 the same with 16-wide steps (four blocks per CU); identical
- * results among 0 / 1 / 2, which always mean the f32 MFMA kernel; -1 also lets deep plain products run as bf16 splits (above); returns
- * the previous setting. */
+ * results among 0 / 1 / 2, which always mean the f32 MFMA kernel; -1 also lets deep plain products (above) and the attention's two
+ * T x T products (odvae_gemm_exp_bound_f32, odvae_gemm_softmax_bwd[_scaled]_f32) run as bf16 splits; returns the previous setting. */
 int odvae_gemm_select_staging(int mode);
 int odvae_gemm_f32(int transA, int transB, int M, int N, int K, float alpha,
                    const float* A, int lda, int64_t strideA,
@@ -207,7 +207,12 @@ int odvae_softmax_rows_f32(const float* x, float* y, int64_t rows, int cols, flo
 int odvae_softmax_rows_bwd_f32(const float* p, const float* dp, float* ds, int64_t rows, int cols, float scale, void* stream);
 /* Attention backward with the softmax backward folded into the product dP = dO V^T ([UPSTREAM] ldm AttnBlock.forward under
  * autograd): rowdot[i] = dO[i] . O[i] (= sum_j P[i][j] dP[i][j]); dS = alpha * P .* (A B^T - rowdot[row]).
- * A [M][K], B [N][K]; P, dS [M][N] (leading dimension ldc, batch stride strideC; dS may alias P); rowdot [batch][M]. */
+ * A [M][K], B [N][K]; P, dS [M][N] (leading dimension ldc, batch stride strideC; dS may alias P); rowdot [batch][M].
+ * With staging per shape, ceil(M/128) * ceil(N/128) * batch >= 512 and K >= 64 (the AttnBlocks at 4 096 tokens from batch 1 up) the
+ * product A B^T is the f32-accumulated sum of six bf16 products of exactly split operands (gemm_f32_split.hip, as odvae_gemm_f32's deep
+ * products): within 2^-22 of sum_k |a_k| |b_k| of the f32 kernel's, rowdot subtracted from the finished sum, deterministic; an Inf in A
+ * or B yields NaN.  The same holds for odvae_gemm_softmax_bwd_scaled_f32 and odvae_gemm_exp_bound_f32 below.
+ * odvae_gemm_select_staging(0 | 1 | 2) forces the f32 MFMA kernel at every shape. */
 int odvae_rowdot_f32(const float* a, const float* b, int64_t rows, int cols, float* out, void* stream);
 int odvae_gemm_softmax_bwd_f32(int M, int N, int K, float alpha, const float* A, int lda, int64_t strideA,
                                const float* B, int ldb, int64_t strideB, const float* P, const float* rowdot,
@@ -220,14 +225,16 @@ int odvae_gemm_softmax_bwd_f32(int M, int N, int K, float alpha, const float* A,
  * the caller's PREDICATED fallback launches (odvae_gemm_pred_f32, odvae_softmax_rows_pred_f32: no-ops unless *flag != 0) redo the block with
  * the row maximum -- no host synchronisation either way.
  *   odvae_attn_row_bound_f32: qkv [N][T][3C] (q | k | v per token) -> bound [N*T] (unscaled), *flag = 0; nk_scratch [N*T]
- *   odvae_gemm_exp_bound_f32: E = exp(alpha * (A B^T - rowbound[row])); A [M][K], B [N][K]
+ *   odvae_gemm_exp_bound_f32: E = exp(alpha * (A B^T - rowbound[row])); A [M][K], B [N][K]; above the gate of odvae_gemm_softmax_bwd_f32
+ *                             A B^T comes from the bf16-split kernel (E moves by at most E * alpha * 2^-22 sum_k |a_k| |b_k|; Inf gives NaN)
  *   odvae_gemm_rownorm_f32:   C = (A B) / l[row], l = row sums of A [M][K]; B [K][N]; rinv [batch][M] = 1 / l; *flag |= (some l < 1e-30 or not finite)
  *                             (under odvae_gemm_f32's rule for deep products A B is a sum of six bf16 products of split operands; l is summed from
  *                             the unsplit f32 values and the flag condition is the same)
  *   odvae_gemm_pred_f32:      odvae_gemm_f32 (unsplit shapes, no bias / residual) under the predicate
  *   odvae_softmax_rows_pred_f32: odvae_softmax_rows_f32 under the predicate, and ones[row] = 1
  * Backward with P given as (E, rinv): odvae_rowdot_scale_f32 (out[i] = a_i . b_i, a_scaled[i][:] = a[i][:] * row_scale[i]: D_i and dO_i / l_i),
- * odvae_gemm_softmax_bwd_scaled_f32 (dS = alpha * E .* rinv[row] .* (A B^T - rowdot[row])). */
+ * odvae_gemm_softmax_bwd_scaled_f32 (dS = alpha * E .* rinv[row] .* (A B^T - rowdot[row]); the same kernels and gate as
+ * odvae_gemm_softmax_bwd_f32). */
 int odvae_attn_row_bound_f32(const float* qkv, int N, int T, int C, float* bound, float* nk_scratch, int* flag, void* stream);
 int odvae_gemm_exp_bound_f32(int M, int N, int K, float alpha, const float* A, int lda, int64_t strideA, const float* B, int ldb, int64_t strideB,
                              const float* rowbound, int64_t strideRow, float* E, int ldc, int64_t strideC, int batch, void* stream);

@@ -24,3 +24,20 @@ for name, m, n, k, batch, ta, tb in cases:
     c = torch.empty(batch, m, n, device=dev)
     t = timeit(lambda: ops.gemm(ta, tb, m, n, k, 1.0, a, a.shape[2], a.shape[1] * a.shape[2], b, b.shape[2], b.shape[1] * b.shape[2], c, n, m * n, batch=batch))
     print("%-18s M%7d N%5d K%7d b%2d: %8.3f ms  %6.1f TFLOP/s" % (name, m, n, k, batch, t, 2.0 * m * n * k * batch / t / 1e9))
+
+# the two T x T products with their epilogues: default dispatch (the bf16-split kernel at these shapes) against forced staging (f32 MFMA)
+L, T, K = _lib.load(), 4096, 256
+q, kk = torch.randn(B, T, K, device=dev), torch.randn(B, T, K, device=dev)
+bound, drow, rinv = torch.full((B, T), 64.0, device=dev), torch.randn(B, T, device=dev), torch.rand(B, T, device=dev) + 0.5
+e, ds = torch.rand(B, T, T, device=dev), torch.empty(B, T, T, device=dev)
+tt = [("E=exp(QK^T-b) NT", lambda: _lib.check(L.odvae_gemm_exp_bound_f32(T, T, K, K ** -0.5, q.data_ptr(), K, T * K, kk.data_ptr(), K, T * K, bound.data_ptr(), T,
+                                                                          ds.data_ptr(), T, T * T, B, _lib.stream_ptr()), "gemm_exp_bound")),
+      ("dS=E(dOV^T-D) NT", lambda: _lib.check(L.odvae_gemm_softmax_bwd_scaled_f32(T, T, K, K ** -0.5, q.data_ptr(), K, T * K, kk.data_ptr(), K, T * K, e.data_ptr(),
+                                                                                   drow.data_ptr(), rinv.data_ptr(), T, ds.data_ptr(), T, T * T, B,
+                                                                                   _lib.stream_ptr()), "gemm_softmax_bwd_scaled"))]
+for name, fn in tt:
+    for mode, what in ((-1, "default"), (0, "f32 MFMA")):
+        prev = L.odvae_gemm_select_staging(mode)
+        t = timeit(fn)
+        L.odvae_gemm_select_staging(prev)
+        print("%-18s M%7d N%5d K%7d b%2d: %8.3f ms  %6.1f TFLOP/s  (%s)" % (name, T, T, K, B, t, 2.0 * T * T * K * B / t / 1e9, what))
