@@ -1515,7 +1515,7 @@ def _conv_b_raw(mode, x, pack, cout, bias, residual, out_f32, cin_alg=None, stat
                           2.0 * n * hi * wi * ca + esz * n * ho * wo * cout * (2 if residual is not None else 1) + 2.0 * 9 * ca * cout)
         return (y, partial) if stats else y
     per = hi * wi
-    grp = max(1, min(n, _I31 // max(per * cx * 2, per * cout * esz)))
+    grp = max(1, min(n, CONV_1X1_GROUP or _I31 // max(per * cx * 2, per * cout * esz)))
     for a in range(0, n, grp):
         b = min(n, a + grp)
         m = (b - a) * per
@@ -1646,6 +1646,7 @@ class _ConvB(Function):
 
 
 WGRAD_1X1_GROUP = 0   # tests: force the image-group split of the 1x1 weight gradient at small sizes (0 = only past 2 GiB)
+CONV_1X1_GROUP = 0    # tests: the same for the 1x1 forward / data gradient in _conv_b_raw (images per launch; 0 = only past 2 GiB)
 
 
 def cast_pad_bf16(x, cp=None):
