@@ -29,6 +29,28 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
 __device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
 
+// two floats -> two bf16 in one dword (first in bits 0..15), round to nearest even: a plain cast, which hipcc turns into
+// v_cvt_pk_bf16_f32 and schedules like any other instruction (NaN stays NaN)
+__device__ __forceinline__ unsigned cvt_pk_bf16(float first, float second) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{first, second}, bf16x2));
+}
+
+// The exact three-way split of f32 into bf16 (x = hi + mid + lo, round to nearest even, both differences exact in f32) that
+// gemm_f32_split.hip and the split form of conv3x3_wgrad_wino_f32.hip feed to the bf16 MFMA:
+// x[0..7] (consecutive k of one row) -> the 16 bytes of the planes hi (0), mid (1), lo (2)
+__device__ __forceinline__ void split8(const float (&x)[8], u32x4 (&pl)[3]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float x0 = x[2 * j], x1 = x[2 * j + 1];
+    const unsigned h = cvt_pk_bf16(x0, x1);
+    const float r0 = x0 - bf16_lo(h), r1 = x1 - bf16_hi(h);
+    const unsigned m = cvt_pk_bf16(r0, r1);
+    const float s0 = r0 - bf16_lo(m), s1 = r1 - bf16_hi(m);
+    pl[0][j] = h; pl[1][j] = m; pl[2][j] = cvt_pk_bf16(s0, s1);
+  }
+}
 // D(32x32) += A(32x16) * B(16x32), bf16 in, f32 accumulate.  lane l (r = l&31, h = l>>5) supplies A[row r][k = 8h+j] and
 // B[k = 8h+j][col r], j = 0..7; D register i of lane l is D[row (i&3) + 8(i>>2) + 4h][col r]  (tools/tr_probe.hip)
 __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {

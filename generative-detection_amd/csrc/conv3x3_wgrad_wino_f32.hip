@@ -17,7 +17,13 @@
 // two k lanes = two tiles): 64 MFMAs per wave and barrier.  The fetch of chunk k+2 is in flight during the MFMAs of
 // chunk k.  Each block writes its partial dU slab; the reduction sums the slabs in a fixed order (deterministic),
 // applies G^T . G and writes OIHW.  The bias gradient rides along: dM[xi = (1,1)] is the sum of the tile's four dy pixels.
-#include "common.h"
+//
+// Where a tile row holds whole chunks (TX % 16 == 0, tensors below 2 GiB) the main loop runs on v_mfma_f32_32x32x16_bf16 instead
+// (conv3x3_wgrad_wino_split_kernel below): every transformed value split exactly into three bf16, six products per (c, co-tile),
+// f32 accumulation -- 0.76-0.82 of this loop's time per launch, within 2^-22 of sum |V| |dM| of its error, same dbias bits.  Same
+// blocks, slabs, reduction and plan(); odvae_conv3x3_wgrad_wino_select chooses (default: by shape).
+#include "bf16_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -274,6 +280,257 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_wino_kernel(WgwParams p)
   }
 }
 
+// ---- the same products on v_mfma_f32_32x32x16_bf16, every f32 operand element split exactly into three bf16 (bf16_common.h) ----------
+// One chunk of 16 tiles is one k step of the bf16 instruction: a lane holds 8 consecutive k = 8 consecutive tiles of one channel.
+// So the loader turns round: lane = channel (a wave instruction reads 256 contiguous bytes of one pixel), waves 0-3 take x, waves
+// 4-7 dy, each thread the 8 tiles of one half of the chunk.  Neighbouring tiles of a tile row share two of their four patch columns:
+// 18 columns x 2 rows of x, 16 x (1 or 2) of dy per thread, 4-byte loads.  The transforms are the f32 loop's (same operations on
+// the same values: dM and with it dbias keep their bits), then split8 and one ds_write_b128 per (c, plane).  LDS holds
+// [operand][plane][c][channel][16 k] bf16 = 96 KB, one stage.  A fragment is one ds_read_b128; per (c, co-tile) the six products
+// of gemm_f32_split.hip in its order (smallest first), f32 accumulation.
+//
+// The four columns c of the domain row are four independent LDS images, so the loop runs in halves with one barrier each: the MFMAs of
+// images 0, 1 of chunk k beside the making of its images 2, 3, then the MFMAs of 2, 3 beside images 0, 1 of chunk k + 1; the
+// transformed row of the chunk being written (18 values) and the raw rows of the one after it (36 loads in flight for a whole chunk)
+// wait in registers.  Vector work does not hide under the bf16 MFMA on this chip (profiles/r04_mfma_valu_coexec.txt), so the interleave
+// buys no overlap of the two pipes; what it removes is the lock-step of "all split, then all multiply" with its barrier waits and
+// exposed LDS and HBM latencies (measured: 0.91 -> 0.75-0.83 of the f32 loop's time, profiles/wgrad_wino_split.md).  Both loader roles
+// run one instruction stream (x and dy differ in addresses, in which of the two fetched rows is which, and in one select per value),
+// so that stream is one basic block with the MFMAs.
+// Needs whole chunks inside one tile row (TX % 16 == 0) and tensors below 2 GiB (scalar byte offsets ride on the loads).
+constexpr unsigned SP_ROWS_B = 128 * 32;          // one (plane, c): 128 channels x 16 k bf16
+constexpr unsigned SP_PLANE_B = 4 * SP_ROWS_B;    // 16 384
+constexpr unsigned SP_OPER_B = 3 * SP_PLANE_B;    // 49 152
+constexpr unsigned SP_OOB = 0x7FFFFFF0u;
+constexpr int64_t SP_MAX_BYTES = 0x7F000000ll;
+
+// byte of (channel row, 16-byte half) inside one (plane, c).  The half is XORed with bit 2 ^ bit 3 of the row: the eight consecutive
+// rows of a ds_write_b128 lane group then fall on the eight 16-byte columns of the 128-byte bank row (rows i and i + 4 differ in
+// bit 2), and the sixteen rows of every ds_read_b128 lane group ({0-3, 12-15, 20-27}, ...: rows that meet modulo 8 differ in bit 3
+// and agree in bit 2) on the sixteen columns of the 256-byte one (MI355X_MICROARCH.md, LDS).
+__device__ __forceinline__ unsigned sp_byte(int row, int half) {
+  return (unsigned)(row * 32 + ((half ^ ((row >> 2) ^ (row >> 3)) & 1) << 4));
+}
+template <int A, int B>
+__device__ __forceinline__ float flin(float x, float y) {
+  static_assert(A >= -1 && A <= 1 && B >= -1 && B <= 1 && A != 0 && B != 0, "coefficients are -1 or 1");
+  if constexpr (A > 0 && B > 0) return x + y;
+  else if constexpr (A > 0) return x - y;
+  else if constexpr (B > 0) return y - x;
+  else return -x - y;
+}
+
+template <int R>
+__device__ __forceinline__ void wgs_body(const WgwParams& p, char* smem, const int split) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int cig = wave & 3, coh = wave >> 2;
+  const int li = lane & 31, h = lane >> 5;
+  constexpr int r = R;
+  const int cib = blockIdx.y, cob = blockIdx.z;
+  // row r of B^T d = sa * d[ra] + sb * d[rb], as in the f32 loop.  The dy loader presents its rows so that the same expression gives
+  // row r of A dY: r = 0: dy[0] - (nothing), 1: dy[0] + dy[1], 2: first = dy[1], second = dy[0] (second - first), 3: (nothing) - dy[1];
+  // a row that is "nothing" is not fetched and reads as +0 (x - 0 = x and 0 - x = -x exactly).
+  constexpr int ra = r == 0 ? 0 : 1, rb = r == 3 ? 3 : 2;
+  constexpr int sa = r == 2 ? -1 : 1, sb = (r == 0 || r == 3) ? -1 : 1;
+  constexpr int ya = r == 3 ? -1 : (r == 2 ? 1 : 0), yb = r == 0 ? -1 : (r == 2 ? 0 : 1);      // dy row of the first / second slot, -1: none
+
+  const int chunk0 = split * p.chunks_per_split;
+  const int nch = min(p.chunks_per_split, p.total_chunks - chunk0);   // >= 1 by construction of nsplit
+
+  // loader role: waves 0-3 x, waves 4-7 dy (wave-uniform); tiles 8 half .. 8 half + 7 of the chunk, one channel
+  const bool is_y = wave >= 4;
+  const int half = (tid >> 7) & 1, ch = tid & 127;
+  const int C = is_y ? p.Cout : p.Cin;
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(is_y ? p.dy : p.x), 0, (unsigned)((int64_t)p.N * p.H * p.W * C * 4), 0x00020000);
+  const unsigned c4 = (unsigned)C * 4u;
+  const unsigned chb = (unsigned)((is_y ? cob : cib) * 128 + ch) * 4u;
+  const int row0 = is_y ? ya : ra - 1, row1 = is_y ? yb : rb - 1;      // pixel rows relative to the tile's first
+  // the chunk being fetched (uniform): global tile row g (= image * TY + tile row: H = 2 TY, so pixel row 2 g is the tile's first),
+  // tile row inside the image, first tile column.  A chunk never leaves its tile row.
+  int g, tty, ttx, kf = 0;
+  {
+    const int t0 = chunk0 * CT;
+    g = t0 / p.TX; ttx = t0 - g * p.TX; tty = g % p.TY;
+  }
+  // Position j = 0..17 of a fetched row is pixel column 2 tx - 1 + j: the 18 patch columns of eight x tiles; dy's 16 columns sit at
+  // j = 1..16 (j = 0 and 17 read as 0 and are never used).  Position 1 is never left of the image, so the offsets of live rows
+  // are non-negative; positions 1..17 add a scalar offset.  Past the split's last chunk everything reads as 0 (no traffic).
+  float ld[2][18], u[18];
+  unsigned fo[2][3];      // per fetched row: offsets of position 0, of positions 1..16, of position 17
+  auto fetch_setup = [&]() {     // the next chunk; advances
+    const bool live = kf < nch;
+    ++kf;
+    const int tx = ttx + 8 * half;
+    const bool cok0 = !is_y && tx > 0, cok17 = !is_y && tx + 8 < p.TX;
+    const bool rok[2] = {live && (is_y ? ya >= 0 : (ra != 0 || tty > 0)), live && (is_y ? yb >= 0 : (rb != 3 || tty < p.TY - 1))};
+    const unsigned b0 = (unsigned)((2 * g + row0) * p.W + 2 * tx) * c4 + chb;
+    const unsigned bb[2] = {b0, b0 + (unsigned)((row1 - row0) * p.W) * c4};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      fo[i][0] = (rok[i] && cok0) ? bb[i] - c4 : SP_OOB;
+      fo[i][1] = rok[i] ? bb[i] : SP_OOB;
+      fo[i][2] = (rok[i] && cok17) ? bb[i] : SP_OOB;
+    }
+    ttx += CT;
+    if (ttx == p.TX) { ttx = 0; ++g; tty = tty + 1 == p.TY ? 0 : tty + 1; }
+  };
+  auto fetch_piece = [&](int n) {      // three of the 36 loads, n = 0..11
+#pragma unroll
+    for (int q = 3 * n; q < 3 * n + 3; ++q) {
+      const int i = q / 18, j = q % 18;
+      const unsigned vo = j == 0 ? fo[i][0] : (j == 17 ? fo[i][2] : fo[i][1]);
+      ld[i][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, vo, j == 0 ? 0u : (unsigned)(j - 1) * c4, 0));
+    }
+  };
+  auto transform = [&]() {
+#pragma unroll
+    for (int j = 0; j < 18; ++j) u[j] = flin<sa, sb>(ld[0][j], ld[1][j]);
+  };
+  const unsigned lds0 = lds_addr_of(smem);
+  const unsigned wr = lds0 + (is_y ? SP_OPER_B : 0u) + sp_byte(ch, half);
+  float bias_acc[8];
+#pragma unroll
+  for (int t = 0; t < 8; ++t) bias_acc[t] = 0.f;
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[c][nt][q] = 0.f;
+
+  // fragment of (c, plane q): V rows cig*32 + li at adrA + c * SP_ROWS_B + q * SP_PLANE_B; dM co-tile nt 1 024 bytes further
+  // (rows 32 apart share the swizzle: it looks at row bits 2 and 3)
+  const unsigned adrA = lds0 + sp_byte(cig * 32 + li, h);
+  const unsigned adrB = lds0 + SP_OPER_B + sp_byte(coh * 64 + li, h);
+
+  // Image SC of the chunk in u is made and written (x: V = (u0 - u2, u1 + u2, u2 - u1, u1 - u3) of the tile's four columns; dy, with
+  // z0 = u1, z1 = u2: dM = (z0, z0 + z1, z0 - z1, -z1)) while, where PC >= 0, the twelve MFMAs of image PC run: one third of a pair
+  // of tiles (about five vector instructions) in front of every MFMA, pinned there (the empty asm statements make each third's results
+  // exist at that point; sched_barrier alone orders only what has side effects) -- left alone hipcc issues the MFMAs in a row and the
+  // splitting after them.  FETCH spreads the 36 loads of the chunk after next over the same twelve slots.
+  auto half_phase = [&](auto pcc, auto scc, auto fetchc) {
+    constexpr int PC = decltype(pcc)::value, SC = decltype(scc)::value;
+    constexpr bool FETCH = decltype(fetchc)::value;
+    constexpr int HI = 0, MID = 1, LO = 2;
+    constexpr int ORDER[6][2] = {{LO, HI}, {HI, LO}, {MID, MID}, {MID, HI}, {HI, MID}, {HI, HI}};   // smallest first
+    bf16x8 a[3], b[2][3];
+    if constexpr (PC >= 0) {
+#pragma unroll
+      for (int q = 2; q >= 0; --q) {      // lo and hi are wanted first
+        a[q] = frag_from_u32x4(lds_ld128(adrA + PC * SP_ROWS_B + q * SP_PLANE_B));
+        b[0][HI + LO - q] = frag_from_u32x4(lds_ld128(adrB + PC * SP_ROWS_B + (HI + LO - q) * SP_PLANE_B));
+        b[1][HI + LO - q] = frag_from_u32x4(lds_ld128(adrB + PC * SP_ROWS_B + (HI + LO - q) * SP_PLANE_B + 1024u));
+      }
+    }
+    if constexpr (FETCH) { transform(); fetch_setup(); }
+    float x0[4], x1[4], r0[4], r1[4];
+    u32x4 pl[3];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      const int j = i / 3, t = 2 * j;      // tiles t, t + 1 of this thread's eight
+      if (i % 3 == 0) {
+        float v[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const float u0 = u[2 * (t + e)], u1 = u[2 * (t + e) + 1], u2 = u[2 * (t + e) + 2], u3 = u[2 * (t + e) + 3];
+          if constexpr (SC == 0) v[e] = is_y ? u1 : u0 - u2;
+          else if constexpr (SC == 1) v[e] = u1 + u2;
+          else if constexpr (SC == 2) { const float d = u2 - u1; v[e] = is_y ? -d : d; }
+          else v[e] = is_y ? -u2 : u1 - u3;
+          // dy00 + dy01 + dy10 + dy11, unsplit: the bias gradient's terms, summed as the f32 loop sums them
+          if constexpr (SC == 1 && r == 1) bias_acc[t + e] += v[e];
+        }
+        x0[j] = v[0]; x1[j] = v[1];
+        pl[HI][j] = cvt_pk_bf16(x0[j], x1[j]);
+        r0[j] = x0[j] - bf16_lo(pl[HI][j]);
+        asm volatile("" : "+v"(r0[j]), "+v"(pl[HI][j]));
+      } else if (i % 3 == 1) {
+        r1[j] = x1[j] - bf16_hi(pl[HI][j]);
+        pl[MID][j] = cvt_pk_bf16(r0[j], r1[j]);
+        r0[j] = r0[j] - bf16_lo(pl[MID][j]);
+        asm volatile("" : "+v"(r0[j]), "+v"(pl[MID][j]));
+      } else {
+        r1[j] = r1[j] - bf16_hi(pl[MID][j]);
+        pl[LO][j] = cvt_pk_bf16(r0[j], r1[j]);
+        asm volatile("" : "+v"(pl[LO][j]));
+      }
+      if constexpr (FETCH) fetch_piece(i);
+      if constexpr (PC >= 0) {
+        const int o = i >> 1, nt = i & 1;
+        acc[PC][nt] = mfma_bf16(a[ORDER[o][0]], b[nt][ORDER[o][1]], acc[PC][nt]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) lds_st128(wr + SC * SP_ROWS_B + q * SP_PLANE_B, pl[q]);
+    if constexpr (PC >= 0) __builtin_amdgcn_sched_barrier(0);
+  };
+  using IN = std::integral_constant<int, -1>;
+  using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
+  using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
+
+  fetch_setup();
+#pragma unroll
+  for (int n = 0; n < 12; ++n) fetch_piece(n);
+  half_phase(IN{}, I0{}, std::true_type{});      // transform of chunk 0, fetch of chunk 1
+  half_phase(IN{}, I1{}, std::false_type{});
+  __syncthreads();
+  for (int k = 0; k < nch; ++k) {
+    // images 0, 1 of chunk k are read while its images 2, 3 are written ...
+    half_phase(I0{}, I2{}, std::false_type{});
+    half_phase(I1{}, I3{}, std::false_type{});
+    __syncthreads();
+    // ... then images 2, 3 are read while 0, 1 of chunk k + 1 are written; the fetch of chunk k + 2 takes the registers that freed
+    half_phase(I2{}, I0{}, std::true_type{});
+    half_phase(I3{}, I1{}, std::false_type{});
+    __syncthreads();
+  }
+
+  // partial dU of this block: slabs[split][xi = 4r + c][ci][co]
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    float* sl = p.slabs + ((int64_t)(split * 16 + 4 * r + c) * p.Cin + cib * 128 + cig * 32) * p.Cout + cob * 128 + coh * 64 + li;
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) sl[(int64_t)acc_row(q, lane) * p.Cout + nt * 32] = acc[c][nt][q];
+  }
+  if constexpr (r == 1) {
+    if (cib == 0 && p.bias_part) {   // block-uniform; the loop ended on a barrier: the operand images are dead
+      float* bs = reinterpret_cast<float*>(smem);      // [16 tiles of a chunk][128]
+      if (is_y) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) bs[(8 * half + t) * 128 + ch] = bias_acc[t];
+      }
+      __syncthreads();
+      if (tid < 128) {
+        float s = 0.f;
+#pragma unroll
+        for (int t = 0; t < CT; ++t) s += bs[t * 128 + tid];
+        p.bias_part[(int64_t)split * p.Cout + cob * 128 + tid] = s;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(512, 2) void conv3x3_wgrad_wino_split_kernel(WgwParams p) {
+  extern __shared__ __attribute__((aligned(16))) char ssm[];   // V planes, then dM planes
+  const int bx = blockIdx.x;        // the four row blocks of a split on one XCD, as in conv3x3_wgrad_wino_kernel
+  const bool xcd_map = (p.nsplit & 7) == 0;
+  const int r = xcd_map ? (bx >> 3) & 3 : bx & 3;
+  const int split = xcd_map ? (bx & 7) + 8 * (bx >> 5) : bx >> 2;
+  switch (r) {      // block-uniform
+    case 0: wgs_body<0>(p, ssm, split); break;
+    case 1: wgs_body<1>(p, ssm, split); break;
+    case 2: wgs_body<2>(p, ssm, split); break;
+    default: wgs_body<3>(p, ssm, split); break;
+  }
+}
+
 // dw[co][ci][a][b] = (G^T (sum over splits of dU) G)[a][b];  G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
 __global__ __launch_bounds__(256) void conv3x3_wgrad_wino_reduce_kernel(const float* __restrict__ slabs, const float* __restrict__ bias_part,
                                                                         int nsplit, int Cin, int Cout, float* __restrict__ dw, float* __restrict__ db) {
@@ -329,9 +586,29 @@ void plan(int N, int H, int W, int Cin, int Cout, WgwParams& p) {
   p.nsplit = ceil_div(p.total_chunks, p.chunks_per_split);
 }
 
+// the split loop's own limits: whole chunks inside one tile row, tensors below 2 GiB
+bool split_supported(int N, int H, int W, int Cin, int Cout) {
+  const int64_t px = (int64_t)N * H * W;
+  return (W / 2) % CT == 0 && px * Cin * 4 < SP_MAX_BYTES && px * Cout * 4 < SP_MAX_BYTES;
+}
+// The shape rule (form -1): every shape the split loop supports.  Measured per launch at B = 32 on the step's shapes (128 -> 128 @256^2 and
+// @128^2, 256 -> 128 @128^2, 256 -> 256 and 128 -> 256 @64^2, 256 -> 256 and 512 -> 256 @32^2: TX = 128 .. 16) it takes 0.75-0.83 of the f32
+// loop's time, far outside the spread of ten launches (profiles/wgrad_wino_split.md section 1); narrower maps (TX < 16: the 16^2 layers)
+// are not supported and keep the f32 loop.
+bool split_by_shape(int N, int H, int W, int Cin, int Cout) { return split_supported(N, H, W, Cin, Cout); }
+int g_form = -1;      // set by odvae_conv3x3_wgrad_wino_select
+
 }  // namespace
 
 extern "C" {
+
+// Which main loop odvae_conv3x3_wgrad_wino_f32 runs: -1 by the shape rule (default), 0 the f32 MFMA loop everywhere, 1 the bf16-split
+// loop wherever it supports the shape (the f32 loop elsewhere).  Returns the previous setting.
+int odvae_conv3x3_wgrad_wino_select(int form) {
+  const int prev = g_form;
+  g_form = form < 0 ? -1 : (form > 1 ? 1 : form);
+  return prev;
+}
 
 // 1 when the Winograd-domain weight gradient serves this shape (otherwise use odvae_conv3x3_wgrad_f32)
 int odvae_conv3x3_wgrad_wino_supported(int N, int H, int W, int Cin, int Cout) {
@@ -365,8 +642,9 @@ int odvae_conv3x3_wgrad_wino_f32(const float* x, const float* dy, int N, int H, 
   p.x = x; p.dy = dy;
   p.slabs = static_cast<float*>(workspace);
   p.bias_part = dbias ? p.slabs + (size_t)p.nsplit * 16 * Cin * Cout : nullptr;
-  const size_t smem = (size_t)4 * OPF * sizeof(float);
-  auto kern = p.TX >= CT ? conv3x3_wgrad_wino_kernel<true> : conv3x3_wgrad_wino_kernel<false>;
+  const bool split = g_form != 0 && split_supported(N, H, W, Cin, Cout) && (g_form == 1 || split_by_shape(N, H, W, Cin, Cout));
+  const size_t smem = split ? (size_t)2 * SP_OPER_B : (size_t)4 * OPF * sizeof(float);
+  auto kern = split ? conv3x3_wgrad_wino_split_kernel : (p.TX >= CT ? conv3x3_wgrad_wino_kernel<true> : conv3x3_wgrad_wino_kernel<false>);
   const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (e != hipSuccess) {
     odvae_set_error("conv3x3_wgrad_wino: hipFuncSetAttribute failed: %s", hipGetErrorString(e));

@@ -37,26 +37,6 @@ __device__ __forceinline__ unsigned tile_byte(int row, int slot) {
   return (unsigned)(row * 64 + ((slot ^ f) << 4));
 }
 
-// two floats -> two bf16 in one dword (first in bits 0..15), round to nearest even: a plain cast, which hipcc turns into
-// v_cvt_pk_bf16_f32 and schedules like any other instruction (NaN stays NaN)
-__device__ __forceinline__ unsigned cvt_pk_bf16(float first, float second) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{first, second}, bf16x2));
-}
-
-// x[0..7] (consecutive k of one row) -> the three planes' 16 bytes
-__device__ __forceinline__ void split8(const float (&x)[8], u32x4 (&pl)[3]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float x0 = x[2 * j], x1 = x[2 * j + 1];
-    const unsigned h = cvt_pk_bf16(x0, x1);
-    const float r0 = x0 - bf16_lo(h), r1 = x1 - bf16_hi(h);
-    const unsigned m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - bf16_lo(m), s1 = r1 - bf16_hi(m);
-    pl[HI][j] = h; pl[MID][j] = m; pl[LO][j] = cvt_pk_bf16(s0, s1);
-  }
-}
 __device__ __forceinline__ void store_unit(unsigned lds_oper, int row, int slot, const float (&x)[8]) {
   u32x4 pl[3];
   split8(x, pl);

@@ -157,6 +157,11 @@ int odvae_conv3x3_wgrad_wino_supported(int N, int H, int W, int Cin, int Cout);
 size_t odvae_conv3x3_wgrad_wino_workspace_bytes(int N, int H, int W, int Cin, int Cout);
 int odvae_conv3x3_wgrad_wino_f32(const float* x, const float* dy, int N, int H, int W, int Cin, int Cout,
                                  float* dw, float* dbias, void* workspace, size_t workspace_bytes, void* stream);
+/* The main loop of odvae_conv3x3_wgrad_wino_f32: -1 by the shape rule (default), 0 the f32 MFMA loop at every shape, 1 the bf16-split
+ * loop (each transformed f32 value split exactly into three bf16, six products on v_mfma_f32_32x32x16_bf16, f32 accumulation) wherever
+ * it supports the shape (W / 2 a multiple of 16, tensors below 2 GiB; the f32 loop elsewhere).  Returns the previous setting.  dbias is
+ * the same bits under every setting; dw of the split loop is closer to the exact sum than the f32 loop's. */
+int odvae_conv3x3_wgrad_wino_select(int form);
 
 /* ---- groupnorm.hip: Normalize = GroupNorm(32, C, eps=1e-6) followed by x*sigmoid(x) -----------------
  * x,y: [N][HW][C]; mean,rstd: [N][G]; swish: 0 identity, 1 x*sigmoid(x). */

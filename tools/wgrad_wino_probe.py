@@ -1,5 +1,6 @@
 """Winograd-domain weight gradient vs the direct weight-gradient kernel (both through the C ABI) and vs torch CPU on small
-shapes; timing on the step's layer shapes.  python tools/wgrad_wino_probe.py [check|time]"""
+shapes; timing of its two main loops (f32 MFMA, bf16 split: odvae_conv3x3_wgrad_wino_select) and of the direct kernel on the layer
+shapes of the headline step.  python tools/wgrad_wino_probe.py [check|time]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from odvae_amd import lib as _lib, ops
@@ -49,22 +50,48 @@ def check():
         assert e1 < 2e-4 and eb < 2e-4
 
 
+# the stride-1 3x3 layers of the headline step (bench.py: 256^2, B = 32) that reach this kernel, and how often per step
+STEP_SHAPES = [(32, 128, 128, 256, 10), (32, 128, 128, 128, 9), (32, 256, 128, 128, 1), (32, 256, 256, 64, 9), (32, 128, 256, 64, 1),
+               (32, 256, 256, 32, 9), (32, 512, 256, 32, 1), (32, 512, 512, 16, 17), (32, 256, 512, 16, 1)]
+
+
+def launches_ms(fn, n=10):
+    """n launches, each behind its own pair of device events"""
+    ts = []
+    for _ in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return ts
+
+
 def time_():
-    for (b, cin, cout, h) in [(32, 128, 128, 256), (32, 128, 128, 128), (32, 256, 256, 64), (32, 512, 512, 16), (32, 256, 512, 32)]:
+    """Per shape: ten launches of each form (0 = f32 loop, 1 = bf16-split loop where supported) and of the direct kernel."""
+    for (b, cin, cout, h, per_step) in STEP_SHAPES:
         x = torch.randn(b, h, h, cin, device=dev)
         dy = torch.randn(b, h, h, cout, device=dev)
-        for kind in ("direct", "wino"):
-            for _ in range(30): run(kind, x, dy, cin, cout)      # clock ramp
+        gf = 2.0 * 9 * cin * cout * b * h * h / 1e9
+        res = {}
+        for form in (0, 1, "direct"):
+            def fn():
+                if form == "direct":
+                    return run("direct", x, dy, cin, cout)
+                prev = L.odvae_conv3x3_wgrad_wino_select(form)
+                try:
+                    return run("wino", x, dy, cin, cout)
+                finally:
+                    L.odvae_conv3x3_wgrad_wino_select(prev)
+            for _ in range(30): fn()      # clock ramp
             torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(40): run(kind, x, dy, cin, cout)
-            e1.record(); torch.cuda.synchronize()
-            ms = e0.elapsed_time(e1) / 40
-            gf = 2.0 * 9 * cin * cout * b * h * h / 1e9
-            print("B%d %d->%d @%d %-6s %.3f ms  %.1f TFLOP/s (direct-form FLOPs)" % (b, cin, cout, h, kind, ms, gf / ms), flush=True)
-        a, _ = run("direct", x, dy, cin, cout); c, _ = run("wino", x, dy, cin, cout); torch.cuda.synchronize()
-        print("   max |wino - direct| / max|direct| = %.2e" % ((a - c).abs().max().item() / a.abs().max().item()), flush=True)
+            ts = launches_ms(fn)
+            res[form] = (fn()[0], sum(ts) / len(ts), min(ts), max(ts))
+            print("B%d %d->%d @%d x%d per step  %-7s mean %.4f ms  min %.4f  max %.4f  %.1f TFLOP/s (direct-form FLOPs)"
+                  % (b, cin, cout, h, per_step, "form %s" % form if form != "direct" else form, res[form][1], res[form][2], res[form][3], gf / res[form][1]), flush=True)
+        torch.cuda.synchronize()
+        same = torch.equal(res[0][0], res[1][0])
+        print("   split / f32 = %.3f%s;  max |wino - direct| / max|direct| = %.2e"
+              % (res[1][1] / res[0][1], " (same bits: the split loop does not serve this shape)" if same else "",
+                 (res["direct"][0] - res[1][0]).abs().max().item() / res["direct"][0].abs().max().item()), flush=True)
 
 
 if __name__ == "__main__":
