@@ -5,6 +5,7 @@ parameters (checkpoint interchange with the reference) and are r
 torch supplies device memory, the current stream and autograd bookkeeping; every FLOP and every byte
 of the hot path moves through libodvae_hip.so.  No CPU fallback exists.
 """
+import collections
 import contextlib
 import os
 import weakref
@@ -46,6 +47,17 @@ def _new_cl(n, c, h, w, like, dtype=torch.float32):
 
 def _ws(nbytes, like):
     return _lib.workspace.get(nbytes, like.device)
+
+
+def _stamp(t):
+    """What identifies "this tensor, as it is now" for a result derived from its values: storage, version counter, shape.  Anything that
+    writes to the tensor in between (an in-place op, a hook, a checkpoint wrapper's copy) changes it."""
+    return (t.data_ptr(), t._version, tuple(t.shape))
+
+
+def _stamped(t, stamp):
+    """Is `t` still the tensor `stamp` was taken from?"""
+    return stamp == _stamp(t)
 
 
 class _KernelEvents:
@@ -152,24 +164,27 @@ class _PackCache:
             return self.epoch
         return self.epoch if id(weight) in self._trainable else -1
 
-    def get(self, weight, want_dgrad, up=False):
-        key = (id(weight), up)
+    def _tag(self, weight):
         # (a frozen weight -- the LPIPS-style VGG stack -- is in no optimizer: its packs do not go stale with the optimizer epoch, only with a
         # write to the tensor itself (load_state_dict: version counter))
-        tag = (weight.data_ptr(), weight._version, self._epoch_of(weight))
+        return (weight.data_ptr(), weight._version, self._epoch_of(weight))
+
+    def get(self, weight, want_dgrad, kind="direct"):
+        key = (id(weight), kind)
+        tag = self._tag(weight)
         hit = self.store.get(key)
         same = hit is not None and hit[0]() is weight
         if same and hit[1] == tag and (hit[3] is not None or not want_dgrad):
             return hit[2], hit[3]
         reuse = None
         if same and self.INPLACE and hit[4] == (tuple(weight.shape), weight.device) and (hit[3] is not None or not want_dgrad):
-            if self.BATCH and up in _BATCH_KINDS and self._refresh_kind(up, weight.device):
+            if self.BATCH and kind in _BATCH_KINDS and self._refresh_kind(kind, weight.device):
                 hit = self.store.get(key)
                 if hit is not None and hit[1] == tag:
                     return hit[2], hit[3]
             reuse = (hit[2], hit[3])          # refill the buffers this weight's packs already live in
             want_dgrad = hit[3] is not None
-        fwd, dgr = _pack_conv3x3_now(weight, True, want_dgrad, up, into=reuse)
+        fwd, dgr = _pack_conv3x3_now(weight, True, want_dgrad, kind, into=reuse)
         # An entry dies with its weight tensor.  AttnBlock builds its [3C, C] q/k/v weight with torch.cat on every forward: each of
         # those temporaries left its two packs behind (round 3 purged dead entries only past 4 096 of them), 14 per step in the bf16
         # path, 6-10 MB that the allocator had to find -- a few fresh hipMalloc calls per step, each a device synchronisation; the
@@ -195,7 +210,7 @@ class _PackCache:
             w = ent[0]()
             if w is None or w.device != device or ent[4] != (tuple(w.shape), w.device) or not w.is_contiguous() or w.dtype != torch.float32:
                 continue
-            tag = (w.data_ptr(), w._version, self._epoch_of(w))
+            tag = self._tag(w)
             if ent[1] == tag or not _batchable(kind, w, L):
                 continue
             live.append((key, ent, w, tag))
@@ -238,37 +253,38 @@ def _batchable(kind, w, L):
 PACK_CACHE = _PackCache()
 
 
-def _pack_conv3x3_now(weight, want_fwd=True, want_dgrad=False, up=False, into=None):
-    """up=True: the 16-tap packs of an Upsample conv (taps that hit the same low-res pixel pre-summed, modes 5 / 6);
-    up="wino": the Winograd F(2x2,3x3) packs U = G g G^T of a stride-1 conv (conv3x3_wino_f32.hip).
+def _pack_conv3x3_now(weight, want_fwd=True, want_dgrad=False, kind="direct", into=None):
+    """kind: "direct" (conv3x3_f32.hip, modes 0-3); "up": the 16-tap packs of an Upsample conv (taps that hit the same low-res pixel
+    pre-summed, modes 5 / 6); "wino" / "wino4": the Winograd F(2x2,3x3) / F(4x4,3x3) packs U = G g G^T of a stride-1 conv
+    (conv3x3_wino_f32.hip, conv3x3_wino4_f32.hip); "bf16": see below.
     into=(fwd, dgr): refill these pack tensors (of the same weight and kind) instead of allocating."""
     L = _L()
     ifwd, idgr = into if into is not None else (None, None)
     w = weight.detach().contiguous()
     _lib.require_device(w)
     cout, cin = w.shape[0], w.shape[1]
-    if up == "bf16":   # bf16 MFMA-fragment packs of a 3x3 or 1x1 conv (conv_bf16.hip); master weights stay f32
+    if kind == "bf16":   # bf16 MFMA-fragment packs of a 3x3 or 1x1 conv (conv_bf16.hip); master weights stay f32
         taps = w.shape[2] * w.shape[3]
         fwd = (ifwd if ifwd is not None else torch.empty(L.odvae_conv_bf16_pack_elems(cin, cout, taps), dtype=BF16, device=w.device)) if want_fwd else None
         dgr = (idgr if idgr is not None else torch.empty(L.odvae_conv_bf16_pack_elems(cout, cin, taps), dtype=BF16, device=w.device)) if want_dgrad else None
         _lib.check(L.odvae_conv_pack_bf16(w.data_ptr(), cout, cin, taps, _lib.ptr(fwd), _lib.ptr(dgr), _lib.stream_ptr()), "conv_pack_bf16")
         return fwd, dgr
-    floats = (L.odvae_conv3x3_wino_pack_floats if up == "wino" else L.odvae_conv3x3_wino4_pack_floats if up == "wino4" else
-              L.odvae_conv3x3_up_pack_floats if up else L.odvae_conv3x3_pack_floats)
+    floats, pack = {"direct": (L.odvae_conv3x3_pack_floats, L.odvae_conv3x3_pack_f32),
+                    "up": (L.odvae_conv3x3_up_pack_floats, L.odvae_conv3x3_pack_up_f32),
+                    "wino": (L.odvae_conv3x3_wino_pack_floats, L.odvae_conv3x3_pack_wino_f32),
+                    "wino4": (L.odvae_conv3x3_wino4_pack_floats, L.odvae_conv3x3_pack_wino4_f32)}[kind]
     fwd = dgr = None
     if want_fwd:
         fwd = ifwd if ifwd is not None else torch.empty(floats(cin, cout), dtype=torch.float32, device=w.device)
     if want_dgrad:
         dgr = idgr if idgr is not None else torch.empty(floats(cout, cin), dtype=torch.float32, device=w.device)
-    pack = (L.odvae_conv3x3_pack_wino_f32 if up == "wino" else L.odvae_conv3x3_pack_wino4_f32 if up == "wino4" else
-            L.odvae_conv3x3_pack_up_f32 if up else L.odvae_conv3x3_pack_f32)
     _lib.check(pack(w.data_ptr(), cout, cin, _lib.ptr(fwd), _lib.ptr(dgr), _lib.stream_ptr()), "conv3x3_pack")
     return fwd, dgr
 
 
-def pack_conv3x3(weight, want_fwd=True, want_dgrad=False, up=False):
-    """OIHW parameter -> kernel packs (see conv3x3_f32.hip), cached per weight update."""
-    fwd, dgr = PACK_CACHE.get(weight, want_dgrad, up)
+def pack_conv3x3(weight, want_fwd=True, want_dgrad=False, kind="direct"):
+    """OIHW parameter -> kernel packs of one kind (_pack_conv3x3_now), cached per weight update."""
+    fwd, dgr = PACK_CACHE.get(weight, want_dgrad, kind)
     return (fwd if want_fwd else None), (dgr if want_dgrad else None)
 
 
@@ -368,7 +384,7 @@ GN_FUSED_BWD_SUSPENDED = 0  # > 0 inside an activation-checkpointed unit (module
 
 class _GnBwdLink:
     """What the consumer conv's data gradient needs of the GroupNorm in front of it, and where it leaves the sums.  `out` identifies the
-    GroupNorm's output the way _gn_partials identifies a conv's: (data_ptr, version, shape).  The GroupNorm's operands are NOT held here:
+    GroupNorm's output the way _gn_partials identifies a conv's (_stamp).  The GroupNorm's operands are NOT held here:
     `node` is a weak reference to its autograd context, whose saved tensors (x, gamma, beta, mean, rstd) the conv's backward reads -- through
     the saved-tensor hooks, so an activation-checkpointed unit recomputes them instead of this link keeping the first forward's alive."""
     __slots__ = ("node", "groups", "out", "sums")
@@ -390,14 +406,14 @@ class _GnBwdLink:
         sums, self.sums = self.sums, None
         if sums is None:
             return None
-        p, ptr, version, shape = sums
-        return p if (ptr == dy.data_ptr() and version == dy._version and shape == tuple(dy.shape)) else None
+        p, stamp = sums
+        return p if _stamped(dy, stamp) else None
 
 
 def _gn_bwd_link_of(a, cin):
     """The link a swish-GroupNorm left on this very tensor (f32, 32 groups), if `a` still holds that GroupNorm's output."""
     link = getattr(a, "_gn_bwd_link", None)
-    if link is None or not GN_FUSED_BWD or link.out != (a.data_ptr(), a._version, tuple(a.shape)) or a.shape[1] != cin:
+    if link is None or not GN_FUSED_BWD or not _stamped(a, link.out) or a.shape[1] != cin:
         return None
     return link
 
@@ -407,23 +423,22 @@ def _gn_stats_ok(cout):
     return GN_FUSED_STATS and cout % GN_GROUPS == 0 and 1 <= cpg <= 32 and (cpg & (cpg - 1)) == 0
 
 
-def _conv3x3_wino_raw(x, pack, cin, cout, bias, residual, act=0, f4=False, stats=False, up=False):
+def _conv3x3_wino_raw(x, pack, cin, cout, bias, residual, act=0, f4=False, stats=False, upsample=False):
     """stats=True (F(4x4) only): returns (y, partials [N][tiles][32][2]) -- the GroupNorm statistics of y per output tile.
-    up=True (F(4x4) only): x is the low-resolution input of an Upsample conv, y has twice its height and width."""
+    upsample=True (F(4x4) only): x is the low-resolution input of an Upsample conv, y has twice its height and width."""
     L = _L()
     n, _, h, w = x.shape
-    if up:
+    if upsample:
         h, w = 2 * h, 2 * w
     y = _new_cl(n, cout, h, w, x)
     tag = KERNEL_EVENTS.begin() if cout > 32 else None
     partial = None
-    if up:
-        if stats:
-            partial = torch.empty(n, L.odvae_conv3x3_wino4_stats_chunks(h, w), GN_GROUPS, 2, dtype=torch.float32, device=x.device)
+    if stats:
+        partial = torch.empty(n, L.odvae_conv3x3_wino4_stats_chunks(h, w), GN_GROUPS, 2, dtype=torch.float32, device=x.device)
+    if upsample:
         _lib.check(L.odvae_conv3x3_wino4_up_f32(x.data_ptr(), n, h, w, cin, pack.data_ptr(), cout, _lib.ptr(bias), _lib.ptr(residual),
                                                 y.data_ptr(), _lib.ptr(partial), GN_GROUPS if stats else 0, _lib.stream_ptr()), "conv3x3_wino4_up")
     elif stats:
-        partial = torch.empty(n, L.odvae_conv3x3_wino4_stats_chunks(h, w), GN_GROUPS, 2, dtype=torch.float32, device=x.device)
         _lib.check(L.odvae_conv3x3_wino4_stats_f32(x.data_ptr(), n, h, w, cin, pack.data_ptr(), cout, _lib.ptr(bias), _lib.ptr(residual),
                                                    y.data_ptr(), partial.data_ptr(), GN_GROUPS, _lib.stream_ptr()), "conv3x3_wino4_stats")
     else:
@@ -432,10 +447,42 @@ def _conv3x3_wino_raw(x, pack, cin, cout, bias, residual, act=0, f4=False, stats
                       y.data_ptr(), int(act), _lib.stream_ptr()), "conv3x3_wino4" if f4 else "conv3x3_wino")
     # issued multiply-adds per output pixel and (ci, co): F(2x2,3x3) 16 per 2x2 tile = 4, F(4x4,3x3) 36 per 4x4 tile = 2.25
     KERNEL_EVENTS.end("conv3x3_wino4" if f4 else "conv3x3_128x128", 2.0 * 9 * cin * cout * n * h * w, tag,
-                      4.0 * (n * h * w * cin // (4 if up else 1) + n * h * w * cout * (2 if residual is not None else 1) + 9 * cin * cout),
+                      4.0 * (n * h * w * cin // (4 if upsample else 1) + n * h * w * cout * (2 if residual is not None else 1) + 9 * cin * cout),
                       issued=2.0 * (2.25 if f4 else 4.0) * cin * cout * n * h * w,
-                      variant=(("upsample" if up else "plain") + (" + GroupNorm statistics" if stats else "")) if f4 else None)
+                      variant=(("upsample" if upsample else "plain") + (" + GroupNorm statistics" if stats else "")) if f4 else None)
     return (y, partial) if stats else y
+
+
+# The kernels one f32 3x3 conv call runs, by route (_conv3x3_route picks it).  Each entry: (pack kind, forward mode, data-gradient mode,
+# weight-gradient mode) of the direct kernels odvae_conv3x3_f32 / odvae_conv3x3_wgrad_f32; None where a Winograd kernel runs instead.
+# (Stride-1 layers may take the Winograd-domain weight gradient in place of the direct one: that depends on N too, see _Conv3x3.backward.)
+CONV3X3_ROUTES = {
+    "direct":    ("direct", 0, 0, 0),
+    "down":      ("direct", 1, 3, 1),         # data gradient: the transposed stride-2 conv
+    "up_dense":  ("direct", 2, 0, 2),         # data gradient at full resolution, then odvae_upsample2x_bwd_f32 (2x2 sum-pool)
+    "up_parity": ("up", 5, 6, 5),             # 16 pre-summed taps per low-res pixel instead of 36
+    "wino2":     ("wino", None, None, 0),     # odvae_conv3x3_wino_f32, F(2x2,3x3), both ways
+    "wino4":     ("wino4", None, None, 0),    # odvae_conv3x3_wino4_f32 / _stats_f32; data gradient: _wino4_f32, or _wino4_gnbwd_f32 with a live GroupNorm link
+    "wino4_up":  ("wino4", None, None, 5),    # odvae_conv3x3_wino4_up_f32; data gradient: _wino4_pool_f32 (UPCONV_POOLED_DGRAD off: _wino4_f32, then upsample2x_bwd)
+}
+
+
+def _conv3x3_route(mode, hi, wi, cin, cout, relu):
+    """The route (a key of CONV3X3_ROUTES) of one f32 3x3 conv call; hi, wi: the INPUT height and width."""
+    if mode == 1:
+        return "down"
+    if mode == 2:
+        if not UPCONV_BY_PARITY:
+            return "up_dense"
+        # the Upsample conv on the F(4x4) kernel: the halo of the (never formed) upsampled image is read from x[iy >> 1][ix >> 1]
+        return "wino4_up" if UPCONV_WINOGRAD4 and not relu and _wino4_ok(2 * hi, 2 * wi, cin, cout) else "up_parity"
+    if mode != 0:
+        raise ValueError("conv3x3: mode %r (0: stride 1, 1: Downsample, 2: Upsample)" % (mode,))
+    if not _wino_ok(hi, wi, cin, cout):
+        return "direct"
+    # (not with a fused ReLU, i.e. not in the frozen VGG stack of the perceptual loss: F(4x4)'s ~1e-5 output error flips ten times
+    # more ReLU masks than F(2x2)'s ~1e-6, and the input gradient of LPIPS then leaves the 5e-3 the parity tests hold it to)
+    return "wino4" if not relu and _wino4_ok(hi, wi, cin, cout) else "wino2"
 
 
 class _Conv3x3(Function):
@@ -448,29 +495,20 @@ class _Conv3x3(Function):
         x = _cl(x)
         res = _cl(residual) if residual is not None else None
         cout, cin = weight.shape[0], weight.shape[1]
-        up = mode == 2 and UPCONV_BY_PARITY
-        if up and UPCONV_WINOGRAD4 and not relu and _wino4_ok(2 * x.shape[2], 2 * x.shape[3], cin, cout):
-            # the Upsample conv on the F(4x4) kernel: the halo of the (never formed) upsampled image is read from x[iy >> 1][ix >> 1]
-            up = "wino4up"
-        if mode == 0 and _wino_ok(x.shape[2], x.shape[3], cin, cout):
-            # (not with a fused ReLU, i.e. not in the frozen VGG stack of the perceptual loss: F(4x4)'s ~1e-5 output error flips ten times
-            # more ReLU masks than F(2x2)'s ~1e-6, and the input gradient of LPIPS then leaves the 5e-3 the parity tests hold it to)
-            up = "wino4" if (not relu and _wino4_ok(x.shape[2], x.shape[3], cin, cout)) else "wino"
-        fwd_pack, _ = pack_conv3x3(weight, True, bool(ctx.needs_input_grad[0]), "wino4" if up == "wino4up" else up)  # both packs in one launch
+        route = _conv3x3_route(mode, x.shape[2], x.shape[3], cin, cout, relu)
+        kind, fwd_mode, _, _ = CONV3X3_ROUTES[route]
+        fwd_pack, _ = pack_conv3x3(weight, True, bool(ctx.needs_input_grad[0]), kind)  # both packs in one launch
         b = bias.detach().contiguous() if bias is not None else None
         partial = None
-        if up == "wino4up":
-            want = bool(gn_stats and _gn_stats_ok(cout))
-            out = _conv3x3_wino_raw(x, fwd_pack, cin, cout, b, res, f4=True, stats=want, up=True)
-            y, partial = out if want else (out, None)
-        elif up == "wino4" and gn_stats and _gn_stats_ok(cout):
-            y, partial = _conv3x3_wino_raw(x, fwd_pack, cin, cout, b, res, f4=True, stats=True)
-        elif up in ("wino", "wino4"):
-            y = _conv3x3_wino_raw(x, fwd_pack, cin, cout, b, res, act=1 if relu else 0, f4=up == "wino4")
+        if fwd_mode is not None:
+            y = _conv3x3_raw(fwd_mode, x, fwd_pack, cin, cout, b, res, act=1 if relu else 0)
         else:
-            y = _conv3x3_raw(5 if up else mode, x, fwd_pack, cin, cout, b, res, act=1 if relu else 0)
-        ctx.mode, ctx.up = mode, up
-        ctx.gn_link = gn_link if (up == "wino4" and gn_link is not None and ctx.needs_input_grad[0]) else None
+            f4 = route != "wino2"
+            stats = bool(f4 and gn_stats and _gn_stats_ok(cout))
+            out = _conv3x3_wino_raw(x, fwd_pack, cin, cout, b, res, act=1 if relu else 0, f4=f4, stats=stats, upsample=route == "wino4_up")
+            y, partial = out if stats else (out, None)
+        ctx.mode, ctx.route = mode, route
+        ctx.gn_link = gn_link if (route == "wino4" and gn_link is not None and ctx.needs_input_grad[0]) else None
         ctx.pack_epoch = PACK_CACHE.epoch
         ctx.relu = bool(relu)
         ctx.has_bias = bias is not None
@@ -489,7 +527,8 @@ class _Conv3x3(Function):
         if dy is None:
             return None, None, None, None, None, None, None, None
         x, weight, y_act = ctx.saved_tensors
-        mode = ctx.mode
+        mode, route = ctx.mode, ctx.route
+        kind, _, dgrad_mode, wgrad_mode = CONV3X3_ROUTES[route]
         dy = _cl(dy)
         if ctx.relu:  # gradient through the fused ReLU: dy * (y > 0)
             g = _new_cl(*[dy.shape[i] for i in (0, 1, 2, 3)], dy)
@@ -502,8 +541,9 @@ class _Conv3x3(Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0] and not WEIGHT_GRADIENT_ONLY:
             PACK_CACHE.check_epoch(ctx.pack_epoch, "conv3x3 backward")
-            _, dgr = pack_conv3x3(weight, False, True, "wino4" if ctx.up == "wino4up" else ctx.up)
-            if ctx.up == "wino4up" and UPCONV_POOLED_DGRAD:
+            _, dgr = pack_conv3x3(weight, False, True, kind)
+            pooled = route == "wino4_up" and UPCONV_POOLED_DGRAD
+            if pooled:
                 # gradient w.r.t. the upsampled image on the F(4x4) kernel, 2x2-summed in its output transform (never stored at full size)
                 dx = _new_cl(n, cin, hi, wi, x)
                 tag = KERNEL_EVENTS.begin()
@@ -511,11 +551,7 @@ class _Conv3x3(Function):
                            "conv3x3_wino4_pool")
                 KERNEL_EVENTS.end("conv3x3_wino4", 2.0 * 9 * cin * cout * n * ho * wo, tag, 4.0 * (n * ho * wo * cout + n * hi * wi * cin + 9 * cin * cout),
                                   issued=2.0 * 2.25 * cin * cout * n * ho * wo, variant="data gradient, 2x2-summed (Upsample)")
-            elif ctx.up == "wino4up":   # the same in two steps: full-resolution gradient, then its 2x2 sum-pool
-                du = _conv3x3_wino_raw(dy, dgr, cout, cin, None, None, f4=True)
-                dx = _new_cl(n, cin, hi, wi, x)
-                _lib.check(L.odvae_upsample2x_bwd_f32(du.data_ptr(), dx.data_ptr(), n, hi, wi, cin, _lib.stream_ptr()), "upsample2x_bwd")
-            elif ctx.up == "wino4" and ctx.gn_link is not None and (gn_ops := ctx.gn_link.operands()) is not None:
+            elif route == "wino4" and ctx.gn_link is not None and (gn_ops := ctx.gn_link.operands()) is not None:
                 # da and, from the same output transform, the first pass of the backward of the GroupNorm that produced this conv's input
                 lk = ctx.gn_link
                 gx, gmean, grstd, ggamma, gbeta = gn_ops
@@ -527,24 +563,17 @@ class _Conv3x3(Function):
                                                            lk.groups, sums.data_ptr(), _lib.stream_ptr()), "conv3x3_wino4_gnbwd")
                 KERNEL_EVENTS.end("conv3x3_wino4", 2.0 * 9 * cin * cout * n * hi * wi, tag, 4.0 * (n * hi * wi * (2 * cin + cout) + 9 * cin * cout),
                                   issued=2.0 * 2.25 * cin * cout * n * hi * wi, variant="data gradient + GroupNorm-backward sums")
-                lk.sums = (sums, dx.data_ptr(), dx._version, tuple(dx.shape))
-            elif ctx.up in ("wino", "wino4"):
-                dx = _conv3x3_wino_raw(dy, dgr, cout, cin, None, None, f4=ctx.up == "wino4")
-            elif mode == 0:
-                dx = _conv3x3_raw(0, dy, dgr, cout, cin, None, None)
-            elif mode == 1:
-                dx = _conv3x3_raw(3, dy, dgr, cout, cin, None, None)
-            elif ctx.up:
-                dx = _conv3x3_raw(6, dy, dgr, cout, cin, None, None)   # 4x4-tap stride-2 conv over dy, pre-summed weights
+                lk.sums = (sums, _stamp(dx))
+            elif dgrad_mode is None:
+                dx = _conv3x3_wino_raw(dy, dgr, cout, cin, None, None, f4=route != "wino2")
             else:
-                du = _conv3x3_raw(0, dy, dgr, cout, cin, None, None)  # gradient w.r.t. the upsampled image
-                dx = _new_cl(n, cin, hi, wi, x)
-                _lib.check(L.odvae_upsample2x_bwd_f32(du.data_ptr(), dx.data_ptr(), n, hi, wi, cin, _lib.stream_ptr()),
-                           "upsample2x_bwd")
+                dx = _conv3x3_raw(dgrad_mode, dy, dgr, cout, cin, None, None)   # (mode 6: 4x4-tap stride-2 conv over dy, pre-summed weights)
+            if route in ("up_dense", "wino4_up") and not pooled:   # that was the gradient w.r.t. the upsampled image: its 2x2 sum-pool
+                du, dx = dx, _new_cl(n, cin, hi, wi, x)
+                _lib.check(L.odvae_upsample2x_bwd_f32(du.data_ptr(), dx.data_ptr(), n, hi, wi, cin, _lib.stream_ptr()), "upsample2x_bwd")
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
             db = torch.empty(cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-            wmode = 5 if ctx.up in (True, "wino4up") else mode
             if mode == 0 and WGRAD_WINOGRAD and L.odvae_conv3x3_wgrad_wino_supported(n, hi, wi, cin, cout):
                 need = L.odvae_conv3x3_wgrad_wino_workspace_bytes(n, hi, wi, cin, cout)
                 wp, wn = _ws(need, x)
@@ -556,15 +585,23 @@ class _Conv3x3(Function):
                                   4.0 * (n * hi * wi * (cin + cout) + 9 * cin * cout),
                                   issued=2.0 * 4 * cin * cout * n * hi * wi)
             else:
-                need = L.odvae_conv3x3_wgrad_workspace_bytes(wmode, n, ho, wo, cin, cout)
+                need = L.odvae_conv3x3_wgrad_workspace_bytes(wgrad_mode, n, ho, wo, cin, cout)
                 wp, wn = _ws(need, x)
-                _lib.check(L.odvae_conv3x3_wgrad_f32(wmode, x.data_ptr(), dy.data_ptr(), n, hi, wi, cin, ho, wo, cout,
+                _lib.check(L.odvae_conv3x3_wgrad_f32(wgrad_mode, x.data_ptr(), dy.data_ptr(), n, hi, wi, cin, ho, wo, cout,
                                                      dw.data_ptr(), _lib.ptr(db), wp, wn, _lib.stream_ptr()),
-                           "conv3x3_wgrad(mode=%d)" % wmode)
+                           "conv3x3_wgrad(mode=%d)" % wgrad_mode)
                 KERNEL_EVENTS.end("conv3x3_wgrad", 2.0 * 9 * cin * cout * n * ho * wo, None,
-                                  issued=_conv_issued(wmode, n, hi, wi, ho, wo, cin, cout))
+                                  issued=_conv_issued(wgrad_mode, n, hi, wi, ho, wo, cin, cout))
         dres = dy if ctx.has_res and ctx.needs_input_grad[3] else None
         return dx, dw, db, dres, None, None, None, None
+
+
+def _tag_gn_partials(y, partial):
+    """The statistics are valid for exactly these values of y: the stamp lets the consumer (_gn_partials_of) tell whether anything wrote
+    to the tensor in between."""
+    if partial is not None:
+        y._gn_partials = (partial, _stamp(y))
+    return y
 
 
 def conv3x3(x, weight, bias=None, residual=None, mode=0, relu=False, out_f32=False, gn_stats=False):
@@ -577,19 +614,11 @@ def conv3x3(x, weight, bias=None, residual=None, mode=0, relu=False, out_f32=Fal
         if relu:
             raise NotImplementedError("fused ReLU is only on the f32 path (the LPIPS-style VGG stack stays f32)")
         if gn_stats and mode == 0 and not out_f32:
-            y, partial = _ConvB.apply(x, weight, bias, residual, mode, False, True)
-            if partial is not None:
-                y._gn_partials = (partial, y.data_ptr(), y._version, tuple(y.shape))
-            return y
+            return _tag_gn_partials(*_ConvB.apply(x, weight, bias, residual, mode, False, True))
         return _ConvB.apply(x, weight, bias, residual, mode, bool(out_f32))
     link = _gn_bwd_link_of(x, weight.shape[1]) if (mode == 0 and not relu) else None
     if gn_stats and not relu and mode in (0, 2):
-        y, partial = _Conv3x3.apply(x, weight, bias, residual, mode, relu, True, link)
-        if partial is not None:
-            # the statistics are valid for exactly these values: the tag (storage, version counter, shape) lets the consumer tell
-            # whether anything wrote to the tensor in between (an in-place op, a hook, a checkpoint wrapper's copy)
-            y._gn_partials = (partial, y.data_ptr(), y._version, tuple(y.shape))
-        return y
+        return _tag_gn_partials(*_Conv3x3.apply(x, weight, bias, residual, mode, relu, True, link))
     return _Conv3x3.apply(x, weight, bias, residual, mode, relu, False, link)
 
 
@@ -677,6 +706,13 @@ ATTN_FOLDED_SOFTMAX = os.environ.get("ODVAE_ATTN_FOLDED_SOFTMAX", "1") != "0"
 _ATTN_LAST_FLAG = None
 
 
+def _qkv_views(t, c):
+    """q, k, v of a packed NHWC [N, 3C, H, W] tensor as pointer-carrying views: channel offsets 0, C, 2C of its first pixel (the kernels
+    take the pixel stride 3C as the leading dimension)."""
+    off = t.storage_offset()
+    return tuple(t.as_strided((1,), (1,), off + i * c) for i in range(3))
+
+
 class _Attention(Function):
     """Single-head attention over T = H*W tokens from a packed qkv tensor [N, 3C, H, W]:
     softmax(q k^T * C^-0.5) v  ([UPSTREAM] AttnBlock.forward).  Scores live in HBM (T x T per image)."""
@@ -691,9 +727,7 @@ class _Attention(Function):
         scale = float(c) ** -0.5
         p = torch.empty(n, t, t, dtype=torch.float32, device=qkv.device)
         o = _new_cl(n, c, h, w, qkv)
-        q = qkv.as_strided((1,), (1,), qkv.storage_offset())
-        k = qkv.as_strided((1,), (1,), qkv.storage_offset() + c)
-        v = qkv.as_strided((1,), (1,), qkv.storage_offset() + 2 * c)
+        q, k, v = _qkv_views(qkv, c)
         sq = t * c3
         rinv = None
         if ATTN_FOLDED_SOFTMAX and L.odvae_gemm_f32_workspace_bytes(t, t, c, n) == 0 and L.odvae_gemm_f32_workspace_bytes(t, c, t, n) == 0:
@@ -742,13 +776,9 @@ class _Attention(Function):
         t = h * w
         scale = float(c) ** -0.5
         sq = t * c3
-        q = qkv.as_strided((1,), (1,), qkv.storage_offset())
-        k = qkv.as_strided((1,), (1,), qkv.storage_offset() + c)
-        v = qkv.as_strided((1,), (1,), qkv.storage_offset() + 2 * c)
+        q, k, v = _qkv_views(qkv, c)
         dqkv = _new_cl(n, c3, h, w, qkv)
-        dq = dqkv.as_strided((1,), (1,), dqkv.storage_offset())
-        dk = dqkv.as_strided((1,), (1,), dqkv.storage_offset() + c)
-        dv = dqkv.as_strided((1,), (1,), dqkv.storage_offset() + 2 * c)
+        dq, dk, dv = _qkv_views(dqkv, c)
         if rinv is not None:
             # D_i = dO_i . O_i and dO_i / l_i in one pass over dO; dV = E^T (dO / l); dS = scale E rinv (dO V^T - D)
             drow = torch.empty(n * t, dtype=torch.float32, device=p.device)
@@ -800,14 +830,9 @@ class _AttentionRecompute(Function):
     """softmax(q k^T * C^-0.5) v as _Attention, with the T x T scores living in a scratch buffer of at most ATTN_SCORE_BUDGET bytes."""
 
     @staticmethod
-    def _views(t_, c):
-        off = t_.storage_offset()
-        return tuple(t_.as_strided((1,), (1,), off + i * c) for i in range(3))
-
-    @staticmethod
     def _probabilities(L, qkv, g0, g, t, c, scale, p):
         c3, sq = 3 * c, t * 3 * c
-        q, k, _ = _AttentionRecompute._views(qkv[g0:g0 + g], c)
+        q, k, _ = _qkv_views(qkv[g0:g0 + g], c)
         gemm(0, 1, t, t, c, 1.0, q, c3, sq, k, c3, sq, p, t, t * t, batch=g)
         _lib.check(L.odvae_softmax_rows_f32(p.data_ptr(), p.data_ptr(), g * t, t, scale, _lib.stream_ptr()), "softmax_rows")
 
@@ -823,7 +848,7 @@ class _AttentionRecompute(Function):
         for g0 in range(0, n, group):
             g = min(group, n - g0)
             _AttentionRecompute._probabilities(L, qkv, g0, g, t, c, scale, p)
-            v = _AttentionRecompute._views(qkv[g0:g0 + g], c)[2]
+            v = _qkv_views(qkv[g0:g0 + g], c)[2]
             gemm(0, 0, t, c, t, 1.0, p, t, t * t, v, c3, t * c3, o[g0:g0 + g], c, t * c, batch=g)
         ctx.group = group
         ctx.save_for_backward(qkv, o)
@@ -847,8 +872,8 @@ class _AttentionRecompute(Function):
         for g0 in range(0, n, group):
             g = min(group, n - g0)
             _AttentionRecompute._probabilities(L, qkv, g0, g, t, c, scale, p)
-            q, k, v = _AttentionRecompute._views(qkv[g0:g0 + g], c)
-            dq, dk, dv = _AttentionRecompute._views(dqkv[g0:g0 + g], c)
+            q, k, v = _qkv_views(qkv[g0:g0 + g], c)
+            dq, dk, dv = _qkv_views(dqkv[g0:g0 + g], c)
             dog = do[g0:g0 + g]
             gemm(1, 0, t, c, t, 1.0, p, t, t * t, dog, c, t * c, dv, c3, sq, batch=g)                       # dV = P^T dO
             tag = KERNEL_EVENTS.begin(secondary=True)
@@ -881,75 +906,104 @@ def attention_qkv(qkv):
 # ------------------------------------------------------------------------------------------------------
 # GroupNorm (+ swish)
 # ------------------------------------------------------------------------------------------------------
+# Per-dtype description of the GroupNorm Functions: dtype, bytes per element, entry points (by name), the suffix of their error labels
+_GnKind = collections.namedtuple("_GnKind", "dtype esz fwd fwd_partials bwd bwd_partials workspace suffix")
+_GN_F32 = _GnKind(torch.float32, 4.0, "odvae_groupnorm_fwd_f32", "odvae_groupnorm_fwd_partials_f32", "odvae_groupnorm_bwd_f32",
+                  "odvae_groupnorm_bwd_partials_f32", "odvae_groupnorm_workspace_bytes", "")
+# (statistics and arithmetic in f32, one rounding on the way out; no GroupNorm-backward link: bwd_partials is f32 only)
+_GN_BF16 = _GnKind(BF16, 2.0, "odvae_groupnorm_fwd_bf16", "odvae_groupnorm_fwd_partials_bf16", "odvae_groupnorm_bwd_bf16",
+                   None, "odvae_groupnorm_bf16_workspace_bytes", "_bf16")
+
+
+def _gn_forward(kind, ctx, x, gamma, beta, groups, eps, swish, with_skip, partials, link=None):
+    """partials [N][chunks][groups][2]: the statistics of x as the conv that produced it left them (ops.conv3x3(gn_stats=True)):
+    no statistics pass.  link (_GnBwdLink, f32 with swish only): filled here for the conv that reads the result (GN_FUSED_BWD)."""
+    L = _L()
+    x = _cl(x, kind.dtype)
+    n, c, h, w = x.shape
+    g = gamma.detach().contiguous()
+    b = beta.detach().contiguous()
+    y = _new_cl(n, c, h, w, x, dtype=kind.dtype)
+    mean = torch.empty(n, groups, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(n, groups, dtype=torch.float32, device=x.device)
+    tag = KERNEL_EVENTS.begin(secondary=True)
+    if partials is not None and partials.shape[0] == n and partials.shape[2] == groups:
+        _lib.check(getattr(L, kind.fwd_partials)(x.data_ptr(), n, h * w, c, groups, g.data_ptr(), b.data_ptr(), float(eps), int(swish),
+                                                 y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), partials.data_ptr(),
+                                                 int(partials.shape[1]), _lib.stream_ptr()), "groupnorm_fwd_partials" + kind.suffix)
+    else:
+        wp, wn = _ws(getattr(L, kind.workspace)(n, h * w, c, groups), x)
+        _lib.check(getattr(L, kind.fwd)(x.data_ptr(), n, h * w, c, groups, g.data_ptr(), b.data_ptr(), float(eps), int(swish),
+                                        y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wp, wn, _lib.stream_ptr()), "groupnorm_fwd" + kind.suffix)
+    # algorithmic traffic (SURVEY.md 8(d)): x read once, y written once
+    KERNEL_EVENTS.end("groupnorm", 0.0, tag, kind.esz * 2 * n * h * w * c, issued=0.0)
+    ctx.groups, ctx.swish = groups, int(swish)
+    ctx.save_for_backward(x, gamma, beta, mean, rstd)
+    ctx.set_materialize_grads(False)   # an unused output's gradient stays None instead of a tensor of zeros
+    ctx.link = None
+    if link is not None and swish:
+        link.node, link.groups = weakref.ref(ctx), groups
+        ctx.link = link
+    if with_skip:
+        return y, x.view_as(x)   # the skip connection's handle on x: its gradient comes back into this node
+    return y
+
+
+def _gn_backward(kind, ctx, dy, dskip):
+    """(dx, dgamma, dbeta)."""
+    L = _L()
+    x, gamma, beta, mean, rstd = ctx.saved_tensors
+    if dy is None:               # only the skip branch carried a gradient
+        return dskip, None, None
+    dy = _cl(dy, kind.dtype)
+    sums = ctx.link.take_sums(dy) if ctx.link is not None else None
+    if dskip is not None:
+        dskip = _cl(dskip, kind.dtype)
+    n, c, h, w = x.shape
+    dx = _new_cl(n, c, h, w, x, dtype=kind.dtype)
+    dg = torch.empty(c, dtype=torch.float32, device=x.device)
+    db = torch.empty(c, dtype=torch.float32, device=x.device)
+    g = gamma.detach().contiguous()
+    b = beta.detach().contiguous()
+    wp, wn = _ws(getattr(L, kind.workspace)(n, h * w, c, ctx.groups), x)
+    tag = KERNEL_EVENTS.begin(secondary=True)
+    if sums is not None:         # the data-gradient launch that made dy left the first pass's sums: finalize + apply only
+        global GN_FUSED_BWD_HITS
+        GN_FUSED_BWD_HITS += 1
+        _lib.check(getattr(L, kind.bwd_partials)(x.data_ptr(), dy.data_ptr(), n, h * w, c, ctx.groups, g.data_ptr(),
+                                                 b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ctx.swish, dx.data_ptr(),
+                                                 dg.data_ptr(), db.data_ptr(), _lib.ptr(dskip), sums.data_ptr(), int(sums.shape[1]),
+                                                 wp, wn, _lib.stream_ptr()), "groupnorm_bwd_partials")
+    else:
+        _lib.check(getattr(L, kind.bwd)(x.data_ptr(), dy.data_ptr(), n, h * w, c, ctx.groups, g.data_ptr(),
+                                        b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ctx.swish, dx.data_ptr(),
+                                        dg.data_ptr(), db.data_ptr(), _lib.ptr(dskip), wp, wn, _lib.stream_ptr()),
+                   "groupnorm_bwd" + kind.suffix)
+    # algorithmic traffic: x, dy (and the folded skip gradient) read once, dx written once
+    KERNEL_EVENTS.end("groupnorm", 0.0, tag, kind.esz * (3 + (dskip is not None)) * n * h * w * c, issued=0.0)
+    return dx, dg, db
+
+
 class _GroupNorm(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, groups, eps, swish, with_skip=False, partials=None, link=None):
-        """partials [N][chunks][groups][2]: the statistics of x as the conv that produced it left them (ops.conv3x3(gn_stats=True)):
-        no statistics pass.  link (_GnBwdLink, swish only): filled here for the conv that reads the result (GN_FUSED_BWD)."""
-        L = _L()
-        x = _cl(x)
-        n, c, h, w = x.shape
-        g = gamma.detach().contiguous()
-        b = beta.detach().contiguous()
-        y = _new_cl(n, c, h, w, x)
-        mean = torch.empty(n, groups, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(n, groups, dtype=torch.float32, device=x.device)
-        tag = KERNEL_EVENTS.begin(secondary=True)
-        if partials is not None and partials.shape[0] == n and partials.shape[2] == groups:
-            _lib.check(L.odvae_groupnorm_fwd_partials_f32(x.data_ptr(), n, h * w, c, groups, g.data_ptr(), b.data_ptr(), float(eps),
-                                                          int(swish), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                          partials.data_ptr(), int(partials.shape[1]), _lib.stream_ptr()), "groupnorm_fwd_partials")
-        else:
-            wp, wn = _ws(L.odvae_groupnorm_workspace_bytes(n, h * w, c, groups), x)
-            _lib.check(L.odvae_groupnorm_fwd_f32(x.data_ptr(), n, h * w, c, groups, g.data_ptr(), b.data_ptr(), float(eps),
-                                                 int(swish), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wp, wn,
-                                                 _lib.stream_ptr()), "groupnorm_fwd")
-        # algorithmic traffic (SURVEY.md 8(d)): x read once, y written once
-        KERNEL_EVENTS.end("groupnorm", 0.0, tag, 4.0 * 2 * n * h * w * c, issued=0.0)
-        ctx.groups, ctx.swish = groups, int(swish)
-        ctx.save_for_backward(x, gamma, beta, mean, rstd)
-        ctx.set_materialize_grads(False)   # an unused output's gradient stays None instead of a tensor of zeros
-        ctx.link = None
-        if link is not None and swish:
-            link.node, link.groups = weakref.ref(ctx), groups
-            ctx.link = link
-        if with_skip:
-            return y, x.view_as(x)   # the skip connection's handle on x: its gradient comes back into this node
-        return y
+        return _gn_forward(_GN_F32, ctx, x, gamma, beta, groups, eps, swish, with_skip, partials, link)
 
     @staticmethod
     def backward(ctx, dy, dskip=None):
-        L = _L()
-        x, gamma, beta, mean, rstd = ctx.saved_tensors
-        if dy is None:               # only the skip branch carried a gradient
-            return dskip, None, None, None, None, None, None, None, None
-        dy = _cl(dy)
-        sums = ctx.link.take_sums(dy) if ctx.link is not None else None
-        if dskip is not None:
-            dskip = _cl(dskip)
-        n, c, h, w = x.shape
-        dx = _new_cl(n, c, h, w, x)
-        dg = torch.empty(c, dtype=torch.float32, device=x.device)
-        db = torch.empty(c, dtype=torch.float32, device=x.device)
-        g = gamma.detach().contiguous()
-        b = beta.detach().contiguous()
-        wp, wn = _ws(L.odvae_groupnorm_workspace_bytes(n, h * w, c, ctx.groups), x)
-        tag = KERNEL_EVENTS.begin(secondary=True)
-        if sums is not None:         # the data-gradient launch that made dy left the first pass's sums: finalize + apply only
-            global GN_FUSED_BWD_HITS
-            GN_FUSED_BWD_HITS += 1
-            _lib.check(L.odvae_groupnorm_bwd_partials_f32(x.data_ptr(), dy.data_ptr(), n, h * w, c, ctx.groups, g.data_ptr(),
-                                                          b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ctx.swish, dx.data_ptr(),
-                                                          dg.data_ptr(), db.data_ptr(), _lib.ptr(dskip), sums.data_ptr(), int(sums.shape[1]),
-                                                          wp, wn, _lib.stream_ptr()), "groupnorm_bwd_partials")
-        else:
-            _lib.check(L.odvae_groupnorm_bwd_f32(x.data_ptr(), dy.data_ptr(), n, h * w, c, ctx.groups, g.data_ptr(),
-                                                 b.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ctx.swish, dx.data_ptr(),
-                                                 dg.data_ptr(), db.data_ptr(), _lib.ptr(dskip), wp, wn, _lib.stream_ptr()),
-                       "groupnorm_bwd")
-        # algorithmic traffic: x, dy (and the folded skip gradient) read once, dx written once
-        KERNEL_EVENTS.end("groupnorm", 0.0, tag, 4.0 * (3 + (dskip is not None)) * n * h * w * c, issued=0.0)
-        return dx, dg, db, None, None, None, None, None, None
+        return _gn_backward(_GN_F32, ctx, dy, dskip) + (None,) * 6
+
+
+class _GroupNormB(Function):
+    """GroupNorm(+swish) on bf16 activations: statistics and arithmetic in f32, one rounding on the way out."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, groups, eps, swish, with_skip=False, partials=None):
+        return _gn_forward(_GN_BF16, ctx, x, gamma, beta, groups, eps, swish, with_skip, partials)
+
+    @staticmethod
+    def backward(ctx, dy, dskip=None):
+        return _gn_backward(_GN_BF16, ctx, dy, dskip) + (None,) * 5
 
 
 def _gn_partials_of(x, groups):
@@ -957,8 +1011,8 @@ def _gn_partials_of(x, groups):
     tagged = getattr(x, "_gn_partials", None)
     if tagged is None or not GN_FUSED_STATS or groups != GN_GROUPS:
         return None
-    p, ptr, version, shape = tagged
-    if ptr != x.data_ptr() or version != x._version or shape != tuple(x.shape) or p.device != x.device:
+    p, stamp = tagged
+    if not _stamped(x, stamp) or p.device != x.device:
         return None      # the tensor was written to (or is not the conv's output any more): take the statistics pass
     n, _, h, w = x.shape
     chunks = _L().odvae_conv_bf16_stats_chunks(h, w) if x.dtype == BF16 else _L().odvae_conv3x3_wino4_stats_chunks(h, w)
@@ -987,7 +1041,7 @@ class gn_fused_bwd_suspended:
 
 def _tag_gn_output(y, link):
     if link is not None and link.node is not None:
-        link.out = (y.data_ptr(), y._version, tuple(y.shape))
+        link.out = _stamp(y)
         y._gn_bwd_link = link
     return y
 
@@ -1687,56 +1741,53 @@ def to_bf16(x, pad_channels_to=None):
     return _ToBF16.apply(x, cp)
 
 
-class _GroupNormB(Function):
-    """GroupNorm(+swish) on bf16 activations: statistics and arithmetic in f32, one rounding on the way out."""
+def _aligned_cl(t):
+    """_cl(t) with a 16-byte aligned base (the fused f32 kernels load float4 rows)."""
+    t = _cl(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=CL)
 
-    @staticmethod
-    def forward(ctx, x, gamma, beta, groups, eps, swish, with_skip=False, partials=None):
-        L = _L()
-        x = _cl(x, BF16)
-        n, c, h, w = x.shape
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        y = _new_cl(n, c, h, w, x, dtype=BF16)
-        mean = torch.empty(n, groups, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(n, groups, dtype=torch.float32, device=x.device)
-        tag = KERNEL_EVENTS.begin(secondary=True)
-        if partials is not None and partials.shape[0] == n and partials.shape[2] == groups:
-            _lib.check(L.odvae_groupnorm_fwd_partials_bf16(x.data_ptr(), n, h * w, c, groups, g.data_ptr(), b.data_ptr(), float(eps), int(swish),
-                                                           y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), partials.data_ptr(),
-                                                           int(partials.shape[1]), _lib.stream_ptr()), "groupnorm_fwd_partials_bf16")
-        else:
-            wp, wn = _ws(L.odvae_groupnorm_bf16_workspace_bytes(n, h * w, c, groups), x)
-            _lib.check(L.odvae_groupnorm_fwd_bf16(x.data_ptr(), n, h * w, c, groups, g.data_ptr(), b.data_ptr(), float(eps), int(swish),
-                                                  y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), wp, wn, _lib.stream_ptr()), "groupnorm_fwd_bf16")
-        KERNEL_EVENTS.end("groupnorm", 0.0, tag, 2.0 * 2 * n * h * w * c, issued=0.0)
-        ctx.groups, ctx.swish = groups, int(swish)
-        ctx.save_for_backward(x, gamma, beta, mean, rstd)
-        ctx.set_materialize_grads(False)
-        if with_skip:
-            return y, x.view_as(x)
-        return y
 
-    @staticmethod
-    def backward(ctx, dy, dskip=None):
-        L = _L()
-        x, gamma, beta, mean, rstd = ctx.saved_tensors
-        if dy is None:
-            return dskip, None, None, None, None, None, None, None
-        dy = _cl(dy, BF16)
-        if dskip is not None:
-            dskip = _cl(dskip, BF16)
-        n, c, h, w = x.shape
-        dx = _new_cl(n, c, h, w, x, dtype=BF16)
-        dg = torch.empty(c, dtype=torch.float32, device=x.device)
-        db = torch.empty(c, dtype=torch.float32, device=x.device)
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        wp, wn = _ws(L.odvae_groupnorm_bf16_workspace_bytes(n, h * w, c, ctx.groups), x)
-        tag = KERNEL_EVENTS.begin(secondary=True)
-        _lib.check(L.odvae_groupnorm_bwd_bf16(x.data_ptr(), dy.data_ptr(), n, h * w, c, ctx.groups, g.data_ptr(), b.data_ptr(),
-                                              mean.data_ptr(), rstd.data_ptr(), ctx.swish, dx.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                                              _lib.ptr(dskip), wp, wn, _lib.stream_ptr()), "groupnorm_bwd_bf16")
-        KERNEL_EVENTS.end("groupnorm", 0.0, tag, 2.0 * (3 + (dskip is not None)) * n * h * w * c, issued=0.0)
-        return dx, dg, db, None, None, None, None, None
+# Per-dtype description of the fused-attention Functions: dtype, bytes per element, input preparation, entry points (by name), the name in
+# error messages and the suffix of the launch labels, and the issued-FLOP factor of a backward as a function of C:
+# seven products (S and dP are formed in both backward kernels); f32 at C = 512: eight, the dK and dV launches each form S
+_FlashKind = collections.namedtuple("_FlashKind", "dtype esz prep supported fwd bwd what suffix issued")
+_FLASH_BF16 = _FlashKind(BF16, 2.0, lambda t: _cl(t, BF16), "odvae_flash_attn_supported", "odvae_flash_attn_fwd_bf16",
+                         "odvae_flash_attn_bwd_bf16", "flash attention", "", lambda c: 14.0)
+_FLASH_F32 = _FlashKind(torch.float32, 4.0, _aligned_cl, "odvae_flash_attn_f32_supported", "odvae_flash_attn_fwd_f32",
+                        "odvae_flash_attn_bwd_f32", "flash attention f32", "_f32", lambda c: 16.0 if c == 512 else 14.0)
+
+
+def _flash_forward(kind, ctx, qkv):
+    L = _L()
+    qkv = kind.prep(qkv)
+    n, c3, h, w = qkv.shape
+    c, t = c3 // 3, h * w
+    if not getattr(L, kind.supported)(n, t, c):
+        raise _lib.HipLibraryError("%s: unsupported shape N=%d T=%d C=%d" % (kind.what, n, t, c))
+    o = _new_cl(n, c, h, w, qkv, dtype=kind.dtype)
+    lse = torch.empty(n, t, dtype=torch.float32, device=qkv.device)
+    tag = KERNEL_EVENTS.begin(secondary=True)
+    _lib.check(getattr(L, kind.fwd)(qkv.data_ptr(), n, t, c, float(c) ** -0.5, o.data_ptr(), lse.data_ptr(), _lib.stream_ptr()),
+               "flash_attn_fwd" + kind.suffix)
+    KERNEL_EVENTS.end("flash_attn", 4.0 * t * t * c * n, tag, kind.esz * n * t * 4 * c)
+    ctx.save_for_backward(qkv, o, lse)
+    return o
+
+
+def _flash_backward(kind, ctx, do):
+    L = _L()
+    qkv, o, lse = ctx.saved_tensors
+    do = kind.prep(do)
+    n, c3, h, w = qkv.shape
+    c, t = c3 // 3, h * w
+    dqkv = _new_cl(n, c3, h, w, qkv, dtype=kind.dtype)
+    delta = torch.empty(n * t, dtype=torch.float32, device=qkv.device)
+    tag = KERNEL_EVENTS.begin(secondary=True)
+    _lib.check(getattr(L, kind.bwd)(qkv.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), n, t, c, float(c) ** -0.5,
+                                    dqkv.data_ptr(), delta.data_ptr(), _lib.stream_ptr()), "flash_attn_bwd" + kind.suffix)
+    # algorithmic: the five products of the backward (S, dP, dV, dK, dQ)
+    KERNEL_EVENTS.end("flash_attn", 10.0 * t * t * c * n, tag, kind.esz * n * t * 8 * c, issued=kind.issued(c) * t * t * c * n)
+    return dqkv
 
 
 class _FlashAttention(Function):
@@ -1745,42 +1796,11 @@ class _FlashAttention(Function):
 
     @staticmethod
     def forward(ctx, qkv):
-        L = _L()
-        qkv = _cl(qkv, BF16)
-        n, c3, h, w = qkv.shape
-        c, t = c3 // 3, h * w
-        if not L.odvae_flash_attn_supported(n, t, c):
-            raise _lib.HipLibraryError("flash attention: unsupported shape N=%d T=%d C=%d" % (n, t, c))
-        o = _new_cl(n, c, h, w, qkv, dtype=BF16)
-        lse = torch.empty(n, t, dtype=torch.float32, device=qkv.device)
-        tag = KERNEL_EVENTS.begin(secondary=True)
-        _lib.check(L.odvae_flash_attn_fwd_bf16(qkv.data_ptr(), n, t, c, float(c) ** -0.5, o.data_ptr(), lse.data_ptr(), _lib.stream_ptr()),
-                   "flash_attn_fwd")
-        KERNEL_EVENTS.end("flash_attn", 4.0 * t * t * c * n, tag, 2.0 * n * t * 4 * c)
-        ctx.save_for_backward(qkv, o, lse)
-        return o
+        return _flash_forward(_FLASH_BF16, ctx, qkv)
 
     @staticmethod
     def backward(ctx, do):
-        L = _L()
-        qkv, o, lse = ctx.saved_tensors
-        do = _cl(do, BF16)
-        n, c3, h, w = qkv.shape
-        c, t = c3 // 3, h * w
-        dqkv = _new_cl(n, c3, h, w, qkv, dtype=BF16)
-        delta = torch.empty(n * t, dtype=torch.float32, device=qkv.device)
-        tag = KERNEL_EVENTS.begin(secondary=True)
-        _lib.check(L.odvae_flash_attn_bwd_bf16(qkv.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), n, t, c, float(c) ** -0.5,
-                                               dqkv.data_ptr(), delta.data_ptr(), _lib.stream_ptr()), "flash_attn_bwd")
-        # algorithmic: the five products of the backward (S, dP, dV, dK, dQ); issued: seven (S and dP are formed in both kernels)
-        KERNEL_EVENTS.end("flash_attn", 10.0 * t * t * c * n, tag, 2.0 * n * t * 8 * c, issued=14.0 * t * t * c * n)
-        return dqkv
-
-
-def _aligned_cl(t):
-    """_cl(t) with a 16-byte aligned base (the fused f32 kernels load float4 rows)."""
-    t = _cl(t)
-    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=CL)
+        return _flash_backward(_FLASH_BF16, ctx, do)
 
 
 class _FlashAttentionF32(Function):
@@ -1789,37 +1809,11 @@ class _FlashAttentionF32(Function):
 
     @staticmethod
     def forward(ctx, qkv):
-        L = _L()
-        qkv = _aligned_cl(qkv)
-        n, c3, h, w = qkv.shape
-        c, t = c3 // 3, h * w
-        if not L.odvae_flash_attn_f32_supported(n, t, c):
-            raise _lib.HipLibraryError("flash attention f32: unsupported shape N=%d T=%d C=%d" % (n, t, c))
-        o = _new_cl(n, c, h, w, qkv)
-        lse = torch.empty(n, t, dtype=torch.float32, device=qkv.device)
-        tag = KERNEL_EVENTS.begin(secondary=True)
-        _lib.check(L.odvae_flash_attn_fwd_f32(qkv.data_ptr(), n, t, c, float(c) ** -0.5, o.data_ptr(), lse.data_ptr(), _lib.stream_ptr()),
-                   "flash_attn_fwd_f32")
-        KERNEL_EVENTS.end("flash_attn", 4.0 * t * t * c * n, tag, 4.0 * n * t * 4 * c)
-        ctx.save_for_backward(qkv, o, lse)
-        return o
+        return _flash_forward(_FLASH_F32, ctx, qkv)
 
     @staticmethod
     def backward(ctx, do):
-        L = _L()
-        qkv, o, lse = ctx.saved_tensors
-        do = _aligned_cl(do)
-        n, c3, h, w = qkv.shape
-        c, t = c3 // 3, h * w
-        dqkv = _new_cl(n, c3, h, w, qkv)
-        delta = torch.empty(n * t, dtype=torch.float32, device=qkv.device)
-        tag = KERNEL_EVENTS.begin(secondary=True)
-        _lib.check(L.odvae_flash_attn_bwd_f32(qkv.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), n, t, c, float(c) ** -0.5,
-                                              dqkv.data_ptr(), delta.data_ptr(), _lib.stream_ptr()), "flash_attn_bwd_f32")
-        # algorithmic: the five products of the backward; issued: seven (S and dP are formed in both kernels; C = 512: eight, the
-        # dK and dV launches each form S)
-        KERNEL_EVENTS.end("flash_attn", 10.0 * t * t * c * n, tag, 4.0 * n * t * 8 * c, issued=(16.0 if c == 512 else 14.0) * t * t * c * n)
-        return dqkv
+        return _flash_backward(_FLASH_F32, ctx, do)
 
 
 # ------------------------------------------------------------------------------------------------------
