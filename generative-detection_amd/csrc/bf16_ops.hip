@@ -321,10 +321,12 @@ int odvae_groupnorm_fwd_bf16(const void* x, int N, int HW, int C, int G, const f
     odvae_set_error("groupnorm_fwd_bf16: needs %zu workspace bytes, got %zu", need, workspace_bytes);
     return ODVAE_ERR_WORKSPACE;
   }
+  unsigned* recentred = odvae_gn_recentred_counter();
+  ODVAE_CHECK_ARG(recentred, "groupnorm_fwd_bf16: cannot find the recentring counter on the device");
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(workspace);
   hipLaunchKernelGGL(gnb_stats_kernel, dim3(s.chunks, N), dim3(256), 0, st, static_cast<const bf16_t*>(x), s, partial);
-  hipLaunchKernelGGL(gn_finalize_kernel<GnB>, dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, s, eps, mean, rstd);
+  hipLaunchKernelGGL((gn_finalize_kernel<GnB, bf16_t>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, static_cast<const bf16_t*>(x), s, eps, mean, rstd, recentred);
   hipLaunchKernelGGL(gnb_apply_kernel, dim3(apply_blocks(s), N), dim3(256), 0, st, static_cast<const bf16_t*>(x), s, gamma, beta, mean, rstd,
                      swish, static_cast<bf16_t*>(y));
   ODVAE_LAUNCH_CHECK("groupnorm_fwd_bf16");
@@ -339,10 +341,12 @@ int odvae_groupnorm_fwd_partials_bf16(const void* x, int N, int HW, int C, int G
   ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "groupnorm_fwd_partials_bf16: unsupported shape N=%d HW=%d C=%d G=%d", N, HW, C, G);
   ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd && partial && chunks > 0, "groupnorm_fwd_partials_bf16: null operand");
   ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)partial & 7) == 0, "groupnorm_fwd_partials_bf16: misaligned operand");
+  unsigned* recentred = odvae_gn_recentred_counter();
+  ODVAE_CHECK_ARG(recentred, "groupnorm_fwd_partials_bf16: cannot find the recentring counter on the device");
   hipStream_t st = static_cast<hipStream_t>(stream);
   GnB sf = s;
   sf.chunks = chunks;
-  hipLaunchKernelGGL(gn_finalize_kernel<GnB>, dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, sf, eps, mean, rstd);
+  hipLaunchKernelGGL((gn_finalize_kernel<GnB, bf16_t>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, static_cast<const bf16_t*>(x), sf, eps, mean, rstd, recentred);
   hipLaunchKernelGGL(gnb_apply_kernel, dim3(apply_blocks(s), N), dim3(256), 0, st, static_cast<const bf16_t*>(x), s, gamma, beta, mean, rstd,
                      swish, static_cast<bf16_t*>(y));
   ODVAE_LAUNCH_CHECK("groupnorm_fwd_partials_bf16");

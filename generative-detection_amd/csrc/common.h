@@ -18,6 +18,9 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // last error text, readable through odvae_last_error()
 extern "C" void odvae_set_error(const char* fmt, ...);
 
+// device address of the counter gn_finalize_kernel (gn_finalize.h) adds to when it recentres a group's statistics (groupnorm.hip)
+unsigned* odvae_gn_recentred_counter();
+
 #define ODVAE_CHECK_ARG(cond, ...)                 \
   do {                                             \
     if (!(cond)) {                                 \

@@ -5,11 +5,25 @@
 // launches per step); lane- / wavefront-strided partial sums bring them to a few microseconds.
 #pragma once
 
+// var = E[x^2] - E[x]^2 from f32 partials loses ~ 2^-24 r^2 of the variance, r = |mean| / std of the (sample, group): as good as a centred
+// evaluation while r is small, useless at r = 1000.  Measured on the device (profiles/gn_offset.md), relative error of rstd: <= 4e-6 at
+// r = 4; up to 7e-5 at r = 16, where the smallest groups (64 values) leave the 5e-5 that tests/test_groupnorm_offset_gpu.py allows;
+// up to 1.4e-3 at r = 64.  With the r^2 law the worst producer crosses 5e-5 at r = 13.8; above the ratio below -- the next power of
+// two under that, a factor 3 in error away from it -- the finalize kernel re-reads the group and takes centred sums.
+constexpr double GN_RECENTRE_RATIO = 8.0;
+
+__device__ __forceinline__ double gn_elem_f64(const float* x, int64_t i) { return (double)x[i]; }
+__device__ __forceinline__ double gn_elem_f64(const unsigned short* x, int64_t i) { return (double)__uint_as_float((unsigned)x[i] << 16); }   // bf16 bits
+
 // one wavefront per (n, g): the chunk partials are summed in f64, lane-strided then by a fixed butterfly (deterministic);
-// a serial loop per thread took 14 us per launch for 64 chunks, 67 launches per step
-template <typename S>
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partial, S s, float eps,
-                                                          float* __restrict__ mean, float* __restrict__ rstd) {
+// a serial loop per thread took 14 us per launch for 64 chunks, 67 launches per step.
+// x [N][HW][C] (f32 or bf16 bits) is the tensor the partials were taken from.  It is read only where mu^2 > GN_RECENTRE_RATIO^2 var: the
+// wavefront then walks its group (lanes over the group's channels of 64 / cpg pixels at a time), sums d = x - mu and d^2 in f64 in a fixed
+// order, and takes mean = mu + sum d / m, var = sum d^2 / m - (sum d / m)^2 -- no cancellation left -- and adds one to *recentred
+// (odvae_groupnorm_recentred).  No flag, no second launch, no host round trip; nothing but the comparison where no group is that far out.
+template <typename S, typename X>
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partial, const X* __restrict__ x, S s, float eps,
+                                                          float* __restrict__ mean, float* __restrict__ rstd, unsigned* __restrict__ recentred) {
   const int lane = threadIdx.x & 63;
   const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (idx >= s.N * s.G) return;
@@ -19,12 +33,30 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
     const float2 o = *reinterpret_cast<const float2*>(partial + (((int64_t)n * s.chunks + ch) * s.G + g) * 2);
     a += (double)o.x; b += (double)o.y;
   }
-  a = wave_sum_f64(a); b = wave_sum_f64(b);
-  if (lane == 0) {
-    const double m = (double)s.HW * s.cpg;
-    const double mu = a / m;
-    double var = b / m - mu * mu;
+  a = wave_sum_f64(a); b = wave_sum_f64(b);      // the same bits in every lane: the branch below is uniform
+  const double m = (double)s.HW * s.cpg;
+  double mu = a / m;
+  double var = b / m - mu * mu;
+  if (var < 0.0) var = 0.0;
+  if (mu * mu > GN_RECENTRE_RATIO * GN_RECENTRE_RATIO * var) {
+    const int jw = s.cpg < 64 ? s.cpg : 64, ppw = 64 / jw;      // lanes: jw channels x ppw pixels (the rest idle where cpg does not divide 64)
+    const int jl = lane % jw, pl = lane / jw;
+    const X* xg = x + (int64_t)n * s.HW * s.C + g * s.cpg;
+    double sd = 0.0, sq = 0.0;
+    if (pl < ppw)
+      for (int p = pl; p < s.HW; p += ppw)
+        for (int j = jl; j < s.cpg; j += jw) {
+          const double d = gn_elem_f64(xg, (int64_t)p * s.C + j) - mu;
+          sd += d; sq += d * d;
+        }
+    sd = wave_sum_f64(sd); sq = wave_sum_f64(sq);
+    const double dm = sd / m;
+    mu += dm;
+    var = sq / m - dm * dm;
     if (var < 0.0) var = 0.0;
+    if (lane == 0) atomicAdd(recentred, 1u);
+  }
+  if (lane == 0) {
     mean[idx] = (float)mu;
     rstd[idx] = (float)(1.0 / sqrt(var + (double)eps));
   }

@@ -271,6 +271,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
 constexpr int GF_THREADS = 256, GF_SLAB = 32, GF_PMAX = 256, GF_HSLOTS = 8;
 
 __device__ unsigned g_gn_fused_timeouts = 0;
+__device__ unsigned g_gn_recentred = 0;       // (sample, group) statistics that gn_finalize_kernel took from centred sums (f32 and bf16 callers)
 
 struct GnFusedParams {
   const float* x; const float* dy; const float* dskip; float* dx;
@@ -523,6 +524,15 @@ int apply_blocks(const GnShape& s) { return (int)std::min<int64_t>(std::max<int6
 
 }  // namespace
 
+// device address of the recentring counter, for every launcher of gn_finalize_kernel (bf16_ops.hip too); nullptr if it cannot be found
+unsigned* odvae_gn_recentred_counter() {
+  static unsigned* const p = [] {
+    void* q = nullptr;
+    return hipGetSymbolAddress(&q, HIP_SYMBOL(g_gn_recentred)) == hipSuccess ? static_cast<unsigned*>(q) : nullptr;
+  }();
+  return p;
+}
+
 extern "C" {
 
 // scratch for forward (stats partials) and backward (channel partials + chan + grp)
@@ -551,6 +561,19 @@ int odvae_groupnorm_select_backward(int mode) {
 int odvae_groupnorm_fused_timeouts(void) {
   unsigned v = 0;
   if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_gn_fused_timeouts), sizeof(v)) != hipSuccess) return -1;
+  return (int)v;
+}
+
+// (sample, group) statistics recomputed from centred sums since the library was loaded (synchronises the device): a group whose
+// |mean| / std exceeded GN_RECENTRE_RATIO (gn_finalize.h).  Correct, and slower: the finalize wavefront re-reads its group.  add > 0
+// bumps the counter first (test hook).  -1 if the counter cannot be read.
+int odvae_groupnorm_recentred(int add) {
+  unsigned v = 0;
+  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_gn_recentred), sizeof(v)) != hipSuccess) return -1;
+  if (add > 0) {
+    v += (unsigned)add;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_gn_recentred), &v, sizeof(v)) != hipSuccess) return -1;
+  }
   return (int)v;
 }
 
@@ -596,11 +619,13 @@ int odvae_groupnorm_fwd_f32(const float* x, int N, int HW, int C, int G, const f
     odvae_set_error("groupnorm_fwd: needs %zu workspace bytes, got %zu", need, workspace_bytes);
     return ODVAE_ERR_WORKSPACE;
   }
+  unsigned* recentred = odvae_gn_recentred_counter();
+  ODVAE_CHECK_ARG(recentred, "groupnorm_fwd: cannot find the recentring counter on the device");
   hipStream_t st = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(workspace);
   hipLaunchKernelGGL(gn_stats_kernel, dim3(s.chunks, N), dim3(256), 0, st, x, s, partial);
   ODVAE_LAUNCH_CHECK("groupnorm stats");
-  hipLaunchKernelGGL(gn_finalize_kernel<GnShape>, dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, s, eps, mean, rstd);
+  hipLaunchKernelGGL((gn_finalize_kernel<GnShape, float>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, x, s, eps, mean, rstd, recentred);
   ODVAE_LAUNCH_CHECK("groupnorm finalize");
   const dim3 grid(apply_blocks(s), N);
   if (swish) hipLaunchKernelGGL((gn_apply_kernel<true>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y);
@@ -637,10 +662,12 @@ int odvae_groupnorm_fwd_partials_f32(const float* x, int N, int HW, int C, int G
   ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd && partial && chunks > 0, "groupnorm_fwd_partials: null operand");
   ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0 &&
                   ((uintptr_t)partial & 7) == 0, "groupnorm_fwd_partials: operands must be 16-byte aligned (partial: 8)");
+  unsigned* recentred = odvae_gn_recentred_counter();
+  ODVAE_CHECK_ARG(recentred, "groupnorm_fwd_partials: cannot find the recentring counter on the device");
   hipStream_t st = static_cast<hipStream_t>(stream);
   GnShape sf = s;
   sf.chunks = chunks;
-  hipLaunchKernelGGL(gn_finalize_kernel<GnShape>, dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, sf, eps, mean, rstd);
+  hipLaunchKernelGGL((gn_finalize_kernel<GnShape, float>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, x, sf, eps, mean, rstd, recentred);
   ODVAE_LAUNCH_CHECK("groupnorm finalize (partials)");
   const dim3 grid(apply_blocks(s), N);
   if (swish) hipLaunchKernelGGL((gn_apply_kernel<true>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y);

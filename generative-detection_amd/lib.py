@@ -74,6 +74,7 @@ PROTOTYPES = {
     "odvae_groupnorm_fused_timeouts": (_I, []),
     "odvae_device_health": (_I, [_P, _P, _I, _I]),
     "odvae_attn_softmax_fallbacks": (_I, [_I]),
+    "odvae_groupnorm_recentred": (_I, [_I]),
     "odvae_softmax_rows_f32": (_I, [_P, _P, _L, _I, _F, _P]),
     "odvae_softmax_rows_bwd_f32": (_I, [_P, _P, _P, _L, _I, _F, _P]),
     "odvae_upsample2x_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),

@@ -70,7 +70,7 @@ class Trainer:
         self.current_epoch = 0            # completed passes over the training loader (PL: trainer.current_epoch)
         # device-side health counters as of the last check_device_health(): GroupNorm team-barrier timeouts (fatal) and exact-softmax
         # fallbacks of the folded attention softmax (correct, slower; reported)
-        self.device_health = {"gn_barrier_timeouts": 0, "attn_softmax_fallbacks": 0}
+        self.device_health = {"gn_barrier_timeouts": 0, "attn_softmax_fallbacks": 0, "gn_recentred": 0}
         self.callback_metrics = {}        # name -> 0-d CPU tensor: the last validate()'s epoch means (what ModelCheckpoint monitors)
         self.reducers = None
         if distributed is None:
@@ -164,11 +164,12 @@ class Trainer:
                            node=name, output_index=index, module=module, optimizer_idx=idx, global_step=gs, rank=rank)
 
     def check_device_health(self, where=""):
-        """Reads the library's two device-side counters (odvae_device_health: one device synchronisation, so it is called only where the
+        """Reads the library's device-side counters (odvae_device_health, odvae_groupnorm_recentred: device synchronisations, so it is called only where the
         host waits anyway -- validation, checkpoint save, the end of fit).  A GroupNorm backward whose team barrier gave up has written
         WRONG gradients (csrc/groupnorm.hip: the opt-in team mode, odvae_groupnorm_select_backward(1)): DeviceHealthError, and no
         checkpoint is written from such a state.  Fallbacks of the folded attention softmax are exact; new ones since the last check are
-        reported once through `warnings` and to the logger's `log_metrics` when it has one.  Returns the counters."""
+        reported once through `warnings` and to the logger's `log_metrics` when it has one; so are GroupNorm statistics that had to be
+        recentred (csrc/gn_finalize.h), through `warnings`.  Returns the counters."""
         import ctypes
         import warnings
         from . import lib as _lib
@@ -178,7 +179,10 @@ class Trainer:
         gn, at = ctypes.c_int(0), ctypes.c_int(0)
         _lib.check(L.odvae_device_health(ctypes.byref(gn), ctypes.byref(at), 0, 0), "device_health")
         prev = self.device_health
-        self.device_health = {"gn_barrier_timeouts": int(gn.value), "attn_softmax_fallbacks": int(at.value)}
+        rc = int(L.odvae_groupnorm_recentred(0))
+        if rc < 0:
+            raise _lib.HipLibraryError("device_health: cannot read the GroupNorm recentring counter")
+        self.device_health = {"gn_barrier_timeouts": int(gn.value), "attn_softmax_fallbacks": int(at.value), "gn_recentred": rc}
         if gn.value > prev["gn_barrier_timeouts"]:
             raise DeviceHealthError(
                 "%d GroupNorm team-barrier wait(s) gave up on the device%s (global_step %d): the gradients of those launches are wrong. "
@@ -193,6 +197,10 @@ class Trainer:
             log = getattr(logger, "log_metrics", None)
             if log is not None:
                 log({"device/attn_softmax_fallbacks": float(at.value)}, step=int(self.model.global_step))
+        if rc > prev.get("gn_recentred", 0):
+            warnings.warn("%d GroupNorm (sample, group) statistics were taken from centred sums since the last check (global_step %d): "
+                          "|mean| / std of those groups exceeded 8; results are exact, each one costs a second read of its group by one wavefront"
+                          % (rc - prev.get("gn_recentred", 0), int(self.model.global_step)), RuntimeWarning, stacklevel=2)
         return dict(self.device_health)
 
     def fit(self, batches, max_batches=None, val_batches=None, max_epochs=1):

@@ -203,6 +203,12 @@ int odvae_groupnorm_fused_timeouts(void);
  * counters first (inject_gn_timeouts < 0 clears that counter).  Mirrors nothing in the reference (its torch ops cannot fail this way); generative-detection_amd/trainer.py reads it. */
 int odvae_device_health(int* gn_timeouts, int* attn_fallbacks, int inject_gn_timeouts, int inject_attn_fallbacks);
 int odvae_attn_softmax_fallbacks(int add);
+/* (sample, group) statistics that the finalize step of a GroupNorm forward (f32 or bf16, own statistics pass or a conv's epilogue sums) took
+ * from centred sums since the library was loaded, because |mean| / std of the group exceeded 8 and E[x^2] - E[x]^2 from f32 sums would
+ * have lost the variance: correct results, one more read of that group by one wavefront.  0 in a healthy run; synchronises the device.
+ * add > 0: test hook that bumps the counter first.  -1 if the counter cannot be read.  generative-detection_amd/trainer.py reads it beside
+ * the two counters above. */
+int odvae_groupnorm_recentred(int add);
 /* dx_add (nullable, same shape as x): a second gradient reaching x (the ResnetBlock / AttnBlock skip connection,
    [UPSTREAM] model.py `return x + h`), summed into dx in the same pass instead of autograd's separate add kernel */
 

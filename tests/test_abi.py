@@ -18,6 +18,7 @@ def test_library_exports_every_header_symbol(built_lib):
     handle = built_lib.load()
     names = built_lib.header_symbols()
     assert len(names) >= 30
+    assert "odvae_groupnorm_recentred" in names and "odvae_device_health" in names
     for name in names:
         assert hasattr(handle, name), name
 

@@ -4,7 +4,9 @@ Two kernels can report trouble only through a word in device memory: the opt-in 
 (csrc/groupnorm.hip: a team barrier that gives up after 0.2 s lets the block run on with partial sums -- wrong gradients) and the folded
 attention softmax (ops._Attention: a row whose Cauchy-Schwarz bound underflows takes an exact fallback -- correct, slower).  The Trainer
 reads both through odvae_device_health wherever the host already waits: after validation, before a checkpoint is written, at the end of
-fit.  A barrier timeout raises DeviceHealthError and no checkpoint is written; softmax fallbacks are reported once per new count."""
+fit.  A barrier timeout raises DeviceHealthError and no checkpoint is written; softmax fallbacks are reported once per new count.
+A third word counts the (sample, group) statistics that a GroupNorm's finalize step took from centred sums because the group's mean lay more
+than 8 standard deviations from zero (csrc/gn_finalize.h, `odvae_groupnorm_recentred`): correct, slower, reported like the fallbacks."""
 import ctypes
 import os
 import warnings
@@ -80,3 +82,36 @@ def test_trainer_reports_softmax_fallbacks_once_and_raises_on_a_barrier_timeout(
     assert hip_lib.odvae_groupnorm_fused_timeouts() == trainer.device_health["gn_barrier_timeouts"]
     assert hip_lib.odvae_device_health(None, None, -1, 0) == 0               # leave the device counter as other tests expect it: 0
     assert hip_lib.odvae_groupnorm_fused_timeouts() == 0
+
+
+def test_a_real_groupnorm_recentring_is_counted_on_the_device(hip_lib):
+    """Every group 1000 standard deviations from zero: E[x^2] - E[x]^2 from f32 sums holds no variance any more, the finalize kernel
+    re-reads each of the 2 x 32 groups -- and counts them; an ordinary input right after counts nothing."""
+    from odvae_amd import ops
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn(2, 64, 8, 8, generator=g)
+    ones, zeros = torch.ones(64, device="cuda:0"), torch.zeros(64, device="cuda:0")
+    before = hip_lib.odvae_groupnorm_recentred(0)
+    y = ops.group_norm((x + 1000.0).to("cuda:0"), ones, zeros, 32, 1e-6, swish=False)
+    assert hip_lib.odvae_groupnorm_recentred(0) == before + 64
+    want = torch.nn.functional.group_norm((x + 1000.0).double(), 32, eps=1e-6)
+    assert (y.cpu().double() - want).abs().max().item() < 2e-4          # 1000 has an f32 ulp of 6e-5: the mean cannot be held finer
+    ops.group_norm((x * 2 + 0.5).to("cuda:0"), ones, zeros, 32, 1e-6, swish=False)
+    assert hip_lib.odvae_groupnorm_recentred(0) == before + 64
+
+
+def test_trainer_reports_groupnorm_recentrings_once(hip_lib):
+    trainer, batch = _trainer()
+    dev = {k: (v.to("cuda:0") if torch.is_tensor(v) else v) for k, v in batch.items()}
+    base = trainer.check_device_health()
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        trainer.validate([dev])                                               # the model at initialisation recentres nothing
+    assert trainer.device_health == base
+    assert hip_lib.odvae_groupnorm_recentred(3) == base["gn_recentred"] + 3   # test hook: three groups "were recentred"
+    with pytest.warns(RuntimeWarning, match="3 GroupNorm"):
+        trainer.validate([dev])
+    assert trainer.device_health["gn_recentred"] == base["gn_recentred"] + 3
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")                                        # ... and are not reported a second time
+        trainer.validate([dev])
