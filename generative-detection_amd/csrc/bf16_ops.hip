@@ -3,6 +3,7 @@
 // "read bf16, compute f32, round once on the way out" is the same arithmetic), dtype hand-offs at the f32 ends of the network
 // (input image, latent, reconstruction), the 2x2 sum-pool of the Upsample data gradient and the bias-gradient column sum.
 #include "bf16_common.h"
+#include "dropout_mask.h"
 
 namespace {
 
@@ -97,16 +98,35 @@ typedef unsigned int gnb_u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u32x4 ldnt(const u32x4* p) { return __builtin_nontemporal_load(reinterpret_cast<const gnb_u4*>(p)); }
 __device__ __forceinline__ void stnt(u32x4* p, u32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<gnb_u4*>(p)); }
 
+// ResnetBlock dropout (dropout_mask.h): a 16-byte load is exactly one octet, so a thread makes one Philox call per load.  The DROP = false
+// instantiations of the three kernels (D = GnNoDrop, an empty last argument) have the instruction streams they had before the dropout existed.
+struct GnNoDrop {};
+template <bool DROP, typename D>
+__device__ __forceinline__ void drop8(float (&a)[8], const D& d, int64_t oct) {
+  if constexpr (DROP) {
+    // contract(off): products of their own, rounded to f32 -- never contracted into an fma with the sum they feed (the identity form's
+    // `b += du`), so that the backward on dy equals the plain backward on a rounded dy * keep * scale
+#pragma clang fp contract(off)
+    float m[8];
+    gn_drop_octet(d, oct, m);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] *= m[j];
+  }
+}
+
+// DROP: y = keep * scale * act(u), multiplied in f32 before the single rounding
+template <bool DROP = false, typename D = GnNoDrop>
 __global__ __launch_bounds__(256) void gnb_apply_kernel(const bf16_t* __restrict__ x, GnB s, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, const float* __restrict__ mean,
-                                                        const float* __restrict__ rstd, int swish, bf16_t* __restrict__ y) {
+                                                        const float* __restrict__ rstd, int swish, bf16_t* __restrict__ y, D d) {
   const int n = blockIdx.y, per_n = s.HW * s.octs;
+  const int64_t o0 = (int64_t)n * per_n;      // index of the sample's first octet in the tensor
   const u32x4* xn = reinterpret_cast<const u32x4*>(x) + (int64_t)n * per_n;
   u32x4* yn = reinterpret_cast<u32x4*>(y) + (int64_t)n * per_n;
   const int stride = gridDim.x * 256;
   Oct k;
   load_oct(s, n, threadIdx.x % s.octs, gamma, beta, mean, rstd, nullptr, k);
-  auto f = [&](const u32x4 v) {
+  auto f = [&](const u32x4 v, int at) {
     float a[8];
     unpack8(v, a);
 #pragma unroll
@@ -114,21 +134,24 @@ __global__ __launch_bounds__(256) void gnb_apply_kernel(const bf16_t* __restrict
       const float u = (a[j] - k.mu[j]) * k.rs[j] * k.g[j] + k.b[j];
       a[j] = swish ? swish_f(u) : u;
     }
+    drop8<DROP>(a, d, o0 + at);
     return pack8(a);
   };
   int i = blockIdx.x * 256 + threadIdx.x;
   for (; i + 3 * stride < per_n; i += 4 * stride) {
     const u32x4 v0 = ldnt(xn + i), v1 = ldnt(xn + i + stride), v2 = ldnt(xn + i + 2 * stride), v3 = ldnt(xn + i + 3 * stride);
-    stnt(yn + i, f(v0)); stnt(yn + i + stride, f(v1)); stnt(yn + i + 2 * stride, f(v2)); stnt(yn + i + 3 * stride, f(v3));
+    stnt(yn + i, f(v0, i)); stnt(yn + i + stride, f(v1, i + stride)); stnt(yn + i + 2 * stride, f(v2, i + 2 * stride)); stnt(yn + i + 3 * stride, f(v3, i + 3 * stride));
   }
-  for (; i < per_n; i += stride) stnt(yn + i, f(ldnt(xn + i)));
+  for (; i < per_n; i += stride) stnt(yn + i, f(ldnt(xn + i), i));
 }
 
-// partial [N][chunks][2][C]: per channel sums of du*xhat and du over the chunk's pixels
+// partial [N][chunks][2][C]: per channel sums of du*xhat and du over the chunk's pixels.  DROP: dy_eff = dy * keep * scale first (f32, not
+// rounded), the rest runs on it unchanged
+template <bool DROP = false, typename D = GnNoDrop>
 __global__ __launch_bounds__(256) void gnb_bwd_reduce_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, GnB s,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
                                                              const float* __restrict__ mean, const float* __restrict__ rstd, int swish,
-                                                             float* __restrict__ partial) {
+                                                             float* __restrict__ partial, D d) {
   __shared__ float red[2][256 * 8];
   const int tid = threadIdx.x, q = tid % s.octs, psub = tid / s.octs;
   const int n = blockIdx.y, chunk = blockIdx.x;
@@ -138,9 +161,10 @@ __global__ __launch_bounds__(256) void gnb_bwd_reduce_kernel(const bf16_t* __res
     load_oct(s, n, q, gamma, beta, mean, rstd, nullptr, k);
     float a[8] = {0, 0, 0, 0, 0, 0, 0, 0}, b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const int64_t base = (int64_t)n * s.HW * s.C + 8 * q;
-    auto accum = [&](const u32x4 xv, const u32x4 dv) {
+    auto accum = [&](const u32x4 xv, const u32x4 dv, int px) {
       float xi[8], di[8];
       unpack8(xv, xi); unpack8(dv, di);
+      drop8<DROP>(di, d, ((int64_t)n * s.HW + px) * s.octs + q);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float xh = (xi[j] - k.mu[j]) * k.rs[j];
@@ -154,11 +178,11 @@ __global__ __launch_bounds__(256) void gnb_bwd_reduce_kernel(const bf16_t* __res
       const u32x4 d0 = ldnt(reinterpret_cast<const u32x4*>(dy + base + (int64_t)px * s.C));
       const u32x4 x1 = ldnt(reinterpret_cast<const u32x4*>(x + base + (int64_t)(px + s.pix_per_pass) * s.C));
       const u32x4 d1 = ldnt(reinterpret_cast<const u32x4*>(dy + base + (int64_t)(px + s.pix_per_pass) * s.C));
-      accum(x0, d0);
-      accum(x1, d1);
+      accum(x0, d0, px);
+      accum(x1, d1, px + s.pix_per_pass);
     }
     for (; px < p_end; px += s.pix_per_pass)
-      accum(*reinterpret_cast<const u32x4*>(x + base + (int64_t)px * s.C), *reinterpret_cast<const u32x4*>(dy + base + (int64_t)px * s.C));
+      accum(*reinterpret_cast<const u32x4*>(x + base + (int64_t)px * s.C), *reinterpret_cast<const u32x4*>(dy + base + (int64_t)px * s.C), px);
 #pragma unroll
     for (int j = 0; j < 8; ++j) { red[0][psub * s.C + 8 * q + j] = a[j]; red[1][psub * s.C + 8 * q + j] = b[j]; }
   }
@@ -172,12 +196,14 @@ __global__ __launch_bounds__(256) void gnb_bwd_reduce_kernel(const bf16_t* __res
 }
 
 // dx = rstd * (du*gamma - (ds2 + xhat*ds1)/m) (+ the skip connection's gradient, folded in)
+template <bool DROP = false, typename D = GnNoDrop>
 __global__ __launch_bounds__(256) void gnb_bwd_apply_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy, GnB s,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
                                                             const float* __restrict__ grp, int swish, const bf16_t* __restrict__ dx_add,
-                                                            bf16_t* __restrict__ dx) {
+                                                            bf16_t* __restrict__ dx, D d) {
   const int n = blockIdx.y, per_n = s.HW * s.octs;
+  const int64_t o0 = (int64_t)n * per_n;
   const u32x4* xn = reinterpret_cast<const u32x4*>(x) + (int64_t)n * per_n;
   const u32x4* dn = reinterpret_cast<const u32x4*>(dy) + (int64_t)n * per_n;
   const u32x4* an = dx_add ? reinterpret_cast<const u32x4*>(dx_add) + (int64_t)n * per_n : nullptr;
@@ -190,6 +216,7 @@ __global__ __launch_bounds__(256) void gnb_bwd_apply_kernel(const bf16_t* __rest
     float xi[8], di[8], ad[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unpack8(xv, xi); unpack8(dv, di);
     if (an) unpack8(ldnt(an + at), ad);
+    drop8<DROP>(di, d, o0 + at);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float xh = (xi[j] - k.mu[j]) * k.rs[j];
@@ -220,6 +247,68 @@ bool make_shape(int N, int HW, int C, int G, GnB& s) {
   return true;
 }
 int apply_blocks(const GnB& s) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div64((int64_t)s.HW * s.octs, 256 * 8), 1), 65535); }
+
+// drop == nullptr launches exactly what the plain entry points always launched
+void launch_gnb_apply(const GnB& s, hipStream_t st, const bf16_t* x, const float* gamma, const float* beta, const float* mean,
+                      const float* rstd, int swish, bf16_t* y, const GnDrop* drop) {
+  if (drop) hipLaunchKernelGGL((gnb_apply_kernel<true, GnDrop>), dim3(apply_blocks(s), s.N), dim3(256), 0, st, x, s, gamma, beta, mean, rstd, swish, y, *drop);
+  else      hipLaunchKernelGGL((gnb_apply_kernel<>), dim3(apply_blocks(s), s.N), dim3(256), 0, st, x, s, gamma, beta, mean, rstd, swish, y, GnNoDrop{});
+}
+
+int gnb_drop_args(const char* who, double p) {      // (C % 8 == 0 is part of every bf16 GroupNorm shape)
+  ODVAE_CHECK_ARG(p >= 0.0 && p <= 1.0, "%s: dropout probability has to be between 0 and 1, got %g", who, p);
+  return ODVAE_OK;
+}
+
+int gnb_fwd_impl(const char* who, const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
+                 void* y, float* mean, float* rstd, void* workspace, size_t workspace_bytes, void* stream, const GnDrop* drop) {
+  GnB s;
+  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "%s: unsupported shape N=%d HW=%d C=%d G=%d (need C%%G==0, C%%8==0, 256%%(C/8)==0)", who, N, HW, C, G);
+  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd, "%s: null operand", who);
+  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "%s: operands must be 16-byte aligned", who);
+  const size_t need = (size_t)N * s.chunks * G * 2 * sizeof(float);
+  if (!workspace || workspace_bytes < need) {
+    odvae_set_error("%s: needs %zu workspace bytes, got %zu", who, need, workspace_bytes);
+    return ODVAE_ERR_WORKSPACE;
+  }
+  unsigned* recentred = odvae_gn_recentred_counter();
+  ODVAE_CHECK_ARG(recentred, "%s: cannot find the recentring counter on the device", who);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* partial = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(gnb_stats_kernel, dim3(s.chunks, N), dim3(256), 0, st, static_cast<const bf16_t*>(x), s, partial);
+  hipLaunchKernelGGL((gn_finalize_kernel<GnB, bf16_t>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, static_cast<const bf16_t*>(x), s, eps, mean, rstd, recentred);
+  launch_gnb_apply(s, st, static_cast<const bf16_t*>(x), gamma, beta, mean, rstd, swish, static_cast<bf16_t*>(y), drop);
+  ODVAE_LAUNCH_CHECK(who);
+  return ODVAE_OK;
+}
+
+int gnb_fwd_partials_impl(const char* who, const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
+                          void* y, float* mean, float* rstd, const float* partial, int chunks, void* stream, const GnDrop* drop) {
+  GnB s;
+  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "%s: unsupported shape N=%d HW=%d C=%d G=%d", who, N, HW, C, G);
+  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd && partial && chunks > 0, "%s: null operand", who);
+  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)partial & 7) == 0, "%s: misaligned operand", who);
+  unsigned* recentred = odvae_gn_recentred_counter();
+  ODVAE_CHECK_ARG(recentred, "%s: cannot find the recentring counter on the device", who);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  GnB sf = s;
+  sf.chunks = chunks;
+  hipLaunchKernelGGL((gn_finalize_kernel<GnB, bf16_t>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, static_cast<const bf16_t*>(x), sf, eps, mean, rstd, recentred);
+  launch_gnb_apply(s, st, static_cast<const bf16_t*>(x), gamma, beta, mean, rstd, swish, static_cast<bf16_t*>(y), drop);
+  ODVAE_LAUNCH_CHECK(who);
+  return ODVAE_OK;
+}
+
+int gnb_apply_impl(const char* who, const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                   const float* mean, const float* rstd, int swish, void* y, void* stream, const GnDrop* drop) {
+  GnB s;
+  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "%s: unsupported shape N=%d HW=%d C=%d G=%d", who, N, HW, C, G);
+  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd, "%s: null operand", who);
+  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "%s: misaligned operand", who);
+  launch_gnb_apply(s, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(x), gamma, beta, mean, rstd, swish, static_cast<bf16_t*>(y), drop);
+  ODVAE_LAUNCH_CHECK(who);
+  return ODVAE_OK;
+}
 
 // ---- dtype hand-offs ---------------------------------------------------------------------------------------------------------
 // y[row][0..CP) bf16 = x[row][0..C) f32, zero for c >= C   (CP % 8 == 0)
@@ -312,64 +401,50 @@ size_t odvae_groupnorm_bf16_workspace_bytes(int N, int HW, int C, int G) {
 // y = act(GroupNorm(x)), x / y bf16 [N][HW][C]; gamma / beta f32; mean / rstd f32 [N][G] saved for the backward
 int odvae_groupnorm_fwd_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
                              void* y, float* mean, float* rstd, void* workspace, size_t workspace_bytes, void* stream) {
-  GnB s;
-  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "groupnorm_fwd_bf16: unsupported shape N=%d HW=%d C=%d G=%d (need C%%G==0, C%%8==0, 256%%(C/8)==0)", N, HW, C, G);
-  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd, "groupnorm_fwd_bf16: null operand");
-  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "groupnorm_fwd_bf16: operands must be 16-byte aligned");
-  const size_t need = (size_t)N * s.chunks * G * 2 * sizeof(float);
-  if (!workspace || workspace_bytes < need) {
-    odvae_set_error("groupnorm_fwd_bf16: needs %zu workspace bytes, got %zu", need, workspace_bytes);
-    return ODVAE_ERR_WORKSPACE;
-  }
-  unsigned* recentred = odvae_gn_recentred_counter();
-  ODVAE_CHECK_ARG(recentred, "groupnorm_fwd_bf16: cannot find the recentring counter on the device");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  float* partial = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(gnb_stats_kernel, dim3(s.chunks, N), dim3(256), 0, st, static_cast<const bf16_t*>(x), s, partial);
-  hipLaunchKernelGGL((gn_finalize_kernel<GnB, bf16_t>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, static_cast<const bf16_t*>(x), s, eps, mean, rstd, recentred);
-  hipLaunchKernelGGL(gnb_apply_kernel, dim3(apply_blocks(s), N), dim3(256), 0, st, static_cast<const bf16_t*>(x), s, gamma, beta, mean, rstd,
-                     swish, static_cast<bf16_t*>(y));
-  ODVAE_LAUNCH_CHECK("groupnorm_fwd_bf16");
-  return ODVAE_OK;
+  return gnb_fwd_impl("groupnorm_fwd_bf16", x, N, HW, C, G, gamma, beta, eps, swish, y, mean, rstd, workspace, workspace_bytes, stream, nullptr);
+}
+
+// The dropout form (odvae_groupnorm_fwd_drop_f32's twin): y = round(keep * scale * act(GroupNorm(x))), the mask of dropout_mask.h from (seed, p)
+int odvae_groupnorm_fwd_drop_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
+                                  double p, unsigned long long seed, void* y, float* mean, float* rstd,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (const int rc = gnb_drop_args("groupnorm_fwd_drop_bf16", p)) return rc;
+  const GnDrop d = make_gn_drop(p, seed);
+  return gnb_fwd_impl("groupnorm_fwd_drop_bf16", x, N, HW, C, G, gamma, beta, eps, swish, y, mean, rstd, workspace, workspace_bytes, stream, &d);
 }
 
 // The same without the statistics pass: partial [N][chunks][G][2] = (sum, sum of squares) of x per chunk and channel group as the conv
 // that produced x left them (odvae_conv_bf16_stats: one chunk per output tile).  finalize (f64, fixed order over the chunks) + apply.
 int odvae_groupnorm_fwd_partials_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
                                       void* y, float* mean, float* rstd, const float* partial, int chunks, void* stream) {
-  GnB s;
-  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "groupnorm_fwd_partials_bf16: unsupported shape N=%d HW=%d C=%d G=%d", N, HW, C, G);
-  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd && partial && chunks > 0, "groupnorm_fwd_partials_bf16: null operand");
-  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)partial & 7) == 0, "groupnorm_fwd_partials_bf16: misaligned operand");
-  unsigned* recentred = odvae_gn_recentred_counter();
-  ODVAE_CHECK_ARG(recentred, "groupnorm_fwd_partials_bf16: cannot find the recentring counter on the device");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  GnB sf = s;
-  sf.chunks = chunks;
-  hipLaunchKernelGGL((gn_finalize_kernel<GnB, bf16_t>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, static_cast<const bf16_t*>(x), sf, eps, mean, rstd, recentred);
-  hipLaunchKernelGGL(gnb_apply_kernel, dim3(apply_blocks(s), N), dim3(256), 0, st, static_cast<const bf16_t*>(x), s, gamma, beta, mean, rstd,
-                     swish, static_cast<bf16_t*>(y));
-  ODVAE_LAUNCH_CHECK("groupnorm_fwd_partials_bf16");
-  return ODVAE_OK;
+  return gnb_fwd_partials_impl("groupnorm_fwd_partials_bf16", x, N, HW, C, G, gamma, beta, eps, swish, y, mean, rstd, partial, chunks, stream, nullptr);
+}
+
+int odvae_groupnorm_fwd_partials_drop_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
+                                           double p, unsigned long long seed, void* y, float* mean, float* rstd,
+                                           const float* partial, int chunks, void* stream) {
+  if (const int rc = gnb_drop_args("groupnorm_fwd_partials_drop_bf16", p)) return rc;
+  const GnDrop d = make_gn_drop(p, seed);
+  return gnb_fwd_partials_impl("groupnorm_fwd_partials_drop_bf16", x, N, HW, C, G, gamma, beta, eps, swish, y, mean, rstd, partial, chunks, stream, &d);
 }
 
 // The apply pass alone with mean / rstd given (odvae_groupnorm_apply_f32's bf16 twin)
 int odvae_groupnorm_apply_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
                                const float* mean, const float* rstd, int swish, void* y, void* stream) {
-  GnB s;
-  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "groupnorm_apply_bf16: unsupported shape N=%d HW=%d C=%d G=%d", N, HW, C, G);
-  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd, "groupnorm_apply_bf16: null operand");
-  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "groupnorm_apply_bf16: misaligned operand");
-  hipLaunchKernelGGL(gnb_apply_kernel, dim3(apply_blocks(s), N), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(x), s,
-                     gamma, beta, mean, rstd, swish, static_cast<bf16_t*>(y));
-  ODVAE_LAUNCH_CHECK("groupnorm_apply_bf16");
-  return ODVAE_OK;
+  return gnb_apply_impl("groupnorm_apply_bf16", x, N, HW, C, G, gamma, beta, mean, rstd, swish, y, stream, nullptr);
+}
+
+int odvae_groupnorm_apply_drop_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                                    const float* mean, const float* rstd, int swish, double p, unsigned long long seed, void* y, void* stream) {
+  if (const int rc = gnb_drop_args("groupnorm_apply_drop_bf16", p)) return rc;
+  const GnDrop d = make_gn_drop(p, seed);
+  return gnb_apply_impl("groupnorm_apply_drop_bf16", x, N, HW, C, G, gamma, beta, mean, rstd, swish, y, stream, &d);
 }
 
 // dx bf16 (+ dx_add bf16, the folded skip gradient, or NULL), dgamma / dbeta f32 [C]
-int odvae_groupnorm_bwd_bf16(const void* x, const void* dy, int N, int HW, int C, int G, const float* gamma, const float* beta,
-                             const float* mean, const float* rstd, int swish, void* dx, float* dgamma, float* dbeta, const void* dx_add,
-                             void* workspace, size_t workspace_bytes, void* stream) {
+static int gnb_bwd_impl(const void* x, const void* dy, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                        const float* mean, const float* rstd, int swish, void* dx, float* dgamma, float* dbeta, const void* dx_add,
+                        void* workspace, size_t workspace_bytes, void* stream, const GnDrop* drop) {
   GnB s;
   ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "groupnorm_bwd_bf16: unsupported shape N=%d HW=%d C=%d G=%d", N, HW, C, G);
   ODVAE_CHECK_ARG(x && dy && gamma && beta && mean && rstd && dx && dgamma && dbeta, "groupnorm_bwd_bf16: null operand");
@@ -386,14 +461,34 @@ int odvae_groupnorm_bwd_bf16(const void* x, const void* dy, int N, int HW, int C
   float* grp = chan + (size_t)N * 2 * C;
   const bf16_t* xb = static_cast<const bf16_t*>(x);
   const bf16_t* db = static_cast<const bf16_t*>(dy);
-  hipLaunchKernelGGL(gnb_bwd_reduce_kernel, dim3(s.chunks, N), dim3(256), 0, st, xb, db, s, gamma, beta, mean, rstd, swish, partial);
+  if (drop) hipLaunchKernelGGL((gnb_bwd_reduce_kernel<true, GnDrop>), dim3(s.chunks, N), dim3(256), 0, st, xb, db, s, gamma, beta, mean, rstd, swish, partial, *drop);
+  else      hipLaunchKernelGGL((gnb_bwd_reduce_kernel<>), dim3(s.chunks, N), dim3(256), 0, st, xb, db, s, gamma, beta, mean, rstd, swish, partial, GnNoDrop{});
   if (s.cpg <= 64) hipLaunchKernelGGL(gn_bwd_finalize_kernel<GnB>, dim3(N, ceil_div(C, (64 / s.cpg) * s.cpg)), dim3(256), 0, st, partial, s, gamma, chan, grp);
   else hipLaunchKernelGGL(gn_bwd_finalize_wide_kernel<GnB>, dim3(N), dim3(256), 2 * C * sizeof(float), st, partial, s, gamma, chan, grp);
   hipLaunchKernelGGL(gn_bwd_param_kernel, dim3(ceil_div(C, 64)), dim3(256), 0, st, chan, N, C, dgamma, dbeta);
-  hipLaunchKernelGGL(gnb_bwd_apply_kernel, dim3(apply_blocks(s), N), dim3(256), 0, st, xb, db, s, gamma, beta, mean, rstd, grp, swish,
-                     static_cast<const bf16_t*>(dx_add), static_cast<bf16_t*>(dx));
+  if (drop) hipLaunchKernelGGL((gnb_bwd_apply_kernel<true, GnDrop>), dim3(apply_blocks(s), N), dim3(256), 0, st, xb, db, s, gamma, beta, mean, rstd, grp, swish,
+                               static_cast<const bf16_t*>(dx_add), static_cast<bf16_t*>(dx), *drop);
+  else      hipLaunchKernelGGL((gnb_bwd_apply_kernel<>), dim3(apply_blocks(s), N), dim3(256), 0, st, xb, db, s, gamma, beta, mean, rstd, grp, swish,
+                               static_cast<const bf16_t*>(dx_add), static_cast<bf16_t*>(dx), GnNoDrop{});
   ODVAE_LAUNCH_CHECK("groupnorm_bwd_bf16");
   return ODVAE_OK;
+}
+
+int odvae_groupnorm_bwd_bf16(const void* x, const void* dy, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                             const float* mean, const float* rstd, int swish, void* dx, float* dgamma, float* dbeta, const void* dx_add,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  return gnb_bwd_impl(x, dy, N, HW, C, G, gamma, beta, mean, rstd, swish, dx, dgamma, dbeta, dx_add, workspace, workspace_bytes, stream, nullptr);
+}
+
+// Backward of the dropout forms: dy_eff = dy * keep * scale in f32 (the mask re-made from the forward call's seed and p), then
+// odvae_groupnorm_bwd_bf16's arithmetic on dy_eff
+int odvae_groupnorm_bwd_drop_bf16(const void* x, const void* dy, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                                  const float* mean, const float* rstd, int swish, double p, unsigned long long seed,
+                                  void* dx, float* dgamma, float* dbeta, const void* dx_add,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (const int rc = gnb_drop_args("groupnorm_bwd_drop_bf16", p)) return rc;
+  const GnDrop d = make_gn_drop(p, seed);
+  return gnb_bwd_impl(x, dy, N, HW, C, G, gamma, beta, mean, rstd, swish, dx, dgamma, dbeta, dx_add, workspace, workspace_bytes, stream, &d);
 }
 
 // y bf16 [rows][CP] = x f32 [rows][C], zero-padded channels (CP >= C, CP % 8 == 0): the f32 -> bf16 hand-off (input image,

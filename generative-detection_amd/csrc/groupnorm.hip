@@ -10,6 +10,7 @@
 // f64 (fixed order => deterministic) into mean / rstd.  Apply is a pure streaming float4 pass.
 // Backward recomputes xhat and the swish derivative from x (nothing but x, mean, rstd is saved).
 #include "common.h"
+#include "dropout_mask.h"
 #include <type_traits>
 
 namespace {
@@ -113,13 +114,33 @@ __device__ __forceinline__ float4 gn_apply_quad(const float4 v, const GnQuad& k)
   return make_float4(out[0], out[1], out[2], out[3]);
 }
 
-template <bool SWISH>
+// ResnetBlock dropout (dropout_mask.h) on a channel quad: v * keep * scale, the mask re-made from (seed, p) and the quad's index in the
+// whole tensor.  A thread computes the Philox call of its quad's octet and uses half of it (profiles/resnet_dropout.md).
+struct GnNoDrop {};      // what a DROP = false kernel takes in GnDrop's place
+template <bool DROP, typename D>
+__device__ __forceinline__ float4 gn_drop4(const float4 v, const D& d, int64_t quad) {
+  if constexpr (DROP) {
+    // contract(off): a product of its own, rounded to f32 -- never contracted into an fma with the sum it feeds (the identity form's `b += du`),
+    // so that the backward on dy equals the plain backward on a rounded dy * keep * scale bit for bit
+#pragma clang fp contract(off)
+    float m[4];
+    gn_drop_quad(d, quad, m);
+    return make_float4(v.x * m[0], v.y * m[1], v.z * m[2], v.w * m[3]);
+  } else {
+    return v;
+  }
+}
+
+// DROP: y = keep * scale * act(u), one multiply after the activation.  The DROP = false instantiations (D = GnNoDrop, an empty last
+// argument) have the instruction streams these kernels had before the dropout existed.
+template <bool SWISH, bool DROP = false, typename D = GnNoDrop>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x, GnShape s,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                       float* __restrict__ y) {
+                                                       float* __restrict__ y, D d) {
   const int n = blockIdx.y;
   const int per_n = s.HW * s.quads;
+  const int64_t q0 = (int64_t)n * per_n;      // index of the sample's first quad in the tensor
   const float4* xn = reinterpret_cast<const float4*>(x) + (int64_t)n * per_n;
   float4* yn = reinterpret_cast<float4*>(y) + (int64_t)n * per_n;
   const int stride = gridDim.x * 256;
@@ -129,14 +150,16 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
     gn_load_quad(s, n, threadIdx.x % s.quads, gamma, beta, mean, rstd, nullptr, k);
     for (; i + 3 * stride < per_n; i += 4 * stride) {
       const float4 v0 = ld_stream(xn + i), v1 = ld_stream(xn + i + stride), v2 = ld_stream(xn + i + 2 * stride), v3 = ld_stream(xn + i + 3 * stride);
-      st_stream(yn + i, gn_apply_quad<SWISH>(v0, k)); st_stream(yn + i + stride, gn_apply_quad<SWISH>(v1, k));
-      st_stream(yn + i + 2 * stride, gn_apply_quad<SWISH>(v2, k)); st_stream(yn + i + 3 * stride, gn_apply_quad<SWISH>(v3, k));
+      st_stream(yn + i, gn_drop4<DROP>(gn_apply_quad<SWISH>(v0, k), d, q0 + i));
+      st_stream(yn + i + stride, gn_drop4<DROP>(gn_apply_quad<SWISH>(v1, k), d, q0 + i + stride));
+      st_stream(yn + i + 2 * stride, gn_drop4<DROP>(gn_apply_quad<SWISH>(v2, k), d, q0 + i + 2 * stride));
+      st_stream(yn + i + 3 * stride, gn_drop4<DROP>(gn_apply_quad<SWISH>(v3, k), d, q0 + i + 3 * stride));
     }
-    for (; i < per_n; i += stride) st_stream(yn + i, gn_apply_quad<SWISH>(ld_stream(xn + i), k));
+    for (; i < per_n; i += stride) st_stream(yn + i, gn_drop4<DROP>(gn_apply_quad<SWISH>(ld_stream(xn + i), k), d, q0 + i));
   } else {
     for (; i < per_n; i += stride) {
       gn_load_quad(s, n, i % s.quads, gamma, beta, mean, rstd, nullptr, k);
-      yn[i] = gn_apply_quad<SWISH>(xn[i], k);
+      yn[i] = gn_drop4<DROP>(gn_apply_quad<SWISH>(xn[i], k), d, q0 + i);
     }
   }
 }
@@ -150,12 +173,12 @@ __device__ __forceinline__ float act_grad(float u) {
   return sg * (1.f + u * (1.f - sg));
 }
 
-// partial: [N][chunks][2][C]
-template <bool SWISH>
+// partial: [N][chunks][2][C].  DROP: dy_eff = dy * keep * scale is formed first, the rest runs on it unchanged.
+template <bool SWISH, bool DROP = false, typename D = GnNoDrop>
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy, GnShape s,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                            float* __restrict__ partial) {
+                                                            float* __restrict__ partial, D d) {
   __shared__ float red[2][256 * 4];
   const int tid = threadIdx.x;
   const int q = tid % s.quads, psub = tid / s.quads;
@@ -174,7 +197,8 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const float* __restr
     const int64_t base = (int64_t)n * s.HW * s.C + c;
     for (int px = p_beg + psub; px < p_end; px += s.pix_per_pass) {
       const float4 xv = ld_stream(reinterpret_cast<const float4*>(x + base + (int64_t)px * s.C));
-      const float4 dv = ld_stream(reinterpret_cast<const float4*>(dy + base + (int64_t)px * s.C));
+      const float4 dv = gn_drop4<DROP>(ld_stream(reinterpret_cast<const float4*>(dy + base + (int64_t)px * s.C)), d,
+                                       ((int64_t)n * s.HW + px) * s.quads + q);
       const float xi[4] = {xv.x, xv.y, xv.z, xv.w}, di[4] = {dv.x, dv.y, dv.z, dv.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -209,14 +233,16 @@ __device__ __forceinline__ float4 gn_bwd_quad(const float4 xv, const float4 dv, 
   return make_float4(out[0], out[1], out[2], out[3]);
 }
 
-template <bool SWISH>
+template <bool SWISH, bool DROP = false, typename D = GnNoDrop>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy, GnShape s,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
                                                            const float* __restrict__ grp, const float* __restrict__ dx_add,
-                                                           float* __restrict__ dx) {
+                                                           float* __restrict__ dx, D d) {
   const int n = blockIdx.y;
   const int per_n = s.HW * s.quads;
+  const int64_t q0 = (int64_t)n * per_n;
+  auto eff = [&](const float4 dv, int at) { return gn_drop4<DROP>(dv, d, q0 + at); };      // dy_eff of quad `at` of the sample
   const float4* xn = reinterpret_cast<const float4*>(x) + (int64_t)n * per_n;
   const float4* dn = reinterpret_cast<const float4*>(dy) + (int64_t)n * per_n;
   const float4* an = dx_add ? reinterpret_cast<const float4*>(dx_add) + (int64_t)n * per_n : nullptr;
@@ -233,13 +259,14 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
     gn_load_quad(s, n, threadIdx.x % s.quads, gamma, beta, mean, rstd, grp, k);
     for (; i + stride < per_n; i += 2 * stride) {
       const float4 x0 = ld_stream(xn + i), x1 = ld_stream(xn + i + stride), d0 = ld_stream(dn + i), d1 = ld_stream(dn + i + stride);
-      st_stream(on + i, plus(gn_bwd_quad<SWISH>(x0, d0, k, inv_m), i)); st_stream(on + i + stride, plus(gn_bwd_quad<SWISH>(x1, d1, k, inv_m), i + stride));
+      st_stream(on + i, plus(gn_bwd_quad<SWISH>(x0, eff(d0, i), k, inv_m), i));
+      st_stream(on + i + stride, plus(gn_bwd_quad<SWISH>(x1, eff(d1, i + stride), k, inv_m), i + stride));
     }
-    for (; i < per_n; i += stride) st_stream(on + i, plus(gn_bwd_quad<SWISH>(ld_stream(xn + i), ld_stream(dn + i), k, inv_m), i));
+    for (; i < per_n; i += stride) st_stream(on + i, plus(gn_bwd_quad<SWISH>(ld_stream(xn + i), eff(ld_stream(dn + i), i), k, inv_m), i));
   } else {
     for (; i < per_n; i += stride) {
       gn_load_quad(s, n, i % s.quads, gamma, beta, mean, rstd, grp, k);
-      on[i] = plus(gn_bwd_quad<SWISH>(xn[i], dn[i], k, inv_m), i);
+      on[i] = plus(gn_bwd_quad<SWISH>(xn[i], eff(dn[i], i), k, inv_m), i);
     }
   }
 }
@@ -522,6 +549,108 @@ bool make_shape(int N, int HW, int C, int G, GnShape& s) {
 // x-dimension of the (blocks, N) apply grids: about eight float4 per thread
 int apply_blocks(const GnShape& s) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div64((int64_t)s.HW * s.quads, 256 * 8), 1), 65535); }
 
+// the three streaming passes that have a dropout form: drop == nullptr launches exactly what the plain entry points always launched
+void launch_gn_apply(const GnShape& s, hipStream_t st, const float* x, const float* gamma, const float* beta, const float* mean,
+                     const float* rstd, int swish, float* y, const GnDrop* drop) {
+  const dim3 grid(apply_blocks(s), s.N);
+  if (drop) {
+    if (swish) hipLaunchKernelGGL((gn_apply_kernel<true, true, GnDrop>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y, *drop);
+    else       hipLaunchKernelGGL((gn_apply_kernel<false, true, GnDrop>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y, *drop);
+    return;
+  }
+  if (swish) hipLaunchKernelGGL((gn_apply_kernel<true>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y, GnNoDrop{});
+  else       hipLaunchKernelGGL((gn_apply_kernel<false>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y, GnNoDrop{});
+}
+
+void launch_gn_bwd_reduce(const GnShape& s, hipStream_t st, const float* x, const float* dy, const float* gamma, const float* beta,
+                          const float* mean, const float* rstd, int swish, float* partial, const GnDrop* drop) {
+  const dim3 grid(s.chunks, s.N);
+  if (drop) {
+    if (swish) hipLaunchKernelGGL((gn_bwd_reduce_kernel<true, true, GnDrop>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, partial, *drop);
+    else       hipLaunchKernelGGL((gn_bwd_reduce_kernel<false, true, GnDrop>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, partial, *drop);
+    return;
+  }
+  if (swish) hipLaunchKernelGGL((gn_bwd_reduce_kernel<true>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, partial, GnNoDrop{});
+  else       hipLaunchKernelGGL((gn_bwd_reduce_kernel<false>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, partial, GnNoDrop{});
+}
+
+void launch_gn_bwd_apply(const GnShape& s, hipStream_t st, const float* x, const float* dy, const float* gamma, const float* beta,
+                         const float* mean, const float* rstd, const float* grp, int swish, const float* dx_add, float* dx, const GnDrop* drop) {
+  const dim3 grid(apply_blocks(s), s.N);
+  if (drop) {
+    if (swish) hipLaunchKernelGGL((gn_bwd_apply_kernel<true, true, GnDrop>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, grp, dx_add, dx, *drop);
+    else       hipLaunchKernelGGL((gn_bwd_apply_kernel<false, true, GnDrop>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, grp, dx_add, dx, *drop);
+    return;
+  }
+  if (swish) hipLaunchKernelGGL((gn_bwd_apply_kernel<true>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, grp, dx_add, dx, GnNoDrop{});
+  else       hipLaunchKernelGGL((gn_bwd_apply_kernel<false>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, grp, dx_add, dx, GnNoDrop{});
+}
+
+// argument checks of the dropout forms (the octet of dropout_mask.h needs C % 8 == 0)
+int gn_drop_args(const char* who, double p, int C) {
+  ODVAE_CHECK_ARG(p >= 0.0 && p <= 1.0, "%s: dropout probability has to be between 0 and 1, got %g", who, p);
+  ODVAE_CHECK_ARG(C % 8 == 0, "%s: the dropout mask needs C %% 8 == 0, got C=%d", who, C);
+  return ODVAE_OK;
+}
+
+int gn_fwd_impl(const char* who, const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                float eps, int swish, float* y, float* mean, float* rstd,
+                void* workspace, size_t workspace_bytes, void* stream, const GnDrop* drop) {
+  GnShape s;
+  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "%s: unsupported shape N=%d HW=%d C=%d G=%d (need C%%G==0, C%%4==0, C<=1024)", who, N, HW, C, G);
+  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd, "%s: null operand", who);
+  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0,
+                  "%s: operands must be 16-byte aligned", who);
+  const size_t need = (size_t)N * s.chunks * G * 2 * sizeof(float);
+  if (!workspace || workspace_bytes < need) {
+    odvae_set_error("%s: needs %zu workspace bytes, got %zu", who, need, workspace_bytes);
+    return ODVAE_ERR_WORKSPACE;
+  }
+  unsigned* recentred = odvae_gn_recentred_counter();
+  ODVAE_CHECK_ARG(recentred, "%s: cannot find the recentring counter on the device", who);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* partial = static_cast<float*>(workspace);
+  hipLaunchKernelGGL(gn_stats_kernel, dim3(s.chunks, N), dim3(256), 0, st, x, s, partial);
+  ODVAE_LAUNCH_CHECK("groupnorm stats");
+  hipLaunchKernelGGL((gn_finalize_kernel<GnShape, float>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, x, s, eps, mean, rstd, recentred);
+  ODVAE_LAUNCH_CHECK("groupnorm finalize");
+  launch_gn_apply(s, st, x, gamma, beta, mean, rstd, swish, y, drop);
+  ODVAE_LAUNCH_CHECK("groupnorm apply");
+  return ODVAE_OK;
+}
+
+int gn_apply_impl(const char* who, const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                  const float* mean, const float* rstd, int swish, float* y, void* stream, const GnDrop* drop) {
+  GnShape s;
+  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "%s: unsupported shape N=%d HW=%d C=%d G=%d", who, N, HW, C, G);
+  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd, "%s: null operand", who);
+  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0,
+                  "%s: operands must be 16-byte aligned", who);
+  launch_gn_apply(s, static_cast<hipStream_t>(stream), x, gamma, beta, mean, rstd, swish, y, drop);
+  ODVAE_LAUNCH_CHECK("groupnorm apply");
+  return ODVAE_OK;
+}
+
+int gn_fwd_partials_impl(const char* who, const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                         float eps, int swish, float* y, float* mean, float* rstd,
+                         const float* partial, int chunks, void* stream, const GnDrop* drop) {
+  GnShape s;
+  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "%s: unsupported shape N=%d HW=%d C=%d G=%d (need C%%G==0, C%%4==0, C<=1024)", who, N, HW, C, G);
+  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd && partial && chunks > 0, "%s: null operand", who);
+  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0 &&
+                  ((uintptr_t)partial & 7) == 0, "%s: operands must be 16-byte aligned (partial: 8)", who);
+  unsigned* recentred = odvae_gn_recentred_counter();
+  ODVAE_CHECK_ARG(recentred, "%s: cannot find the recentring counter on the device", who);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  GnShape sf = s;
+  sf.chunks = chunks;
+  hipLaunchKernelGGL((gn_finalize_kernel<GnShape, float>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, x, sf, eps, mean, rstd, recentred);
+  ODVAE_LAUNCH_CHECK("groupnorm finalize (partials)");
+  launch_gn_apply(s, st, x, gamma, beta, mean, rstd, swish, y, drop);
+  ODVAE_LAUNCH_CHECK("groupnorm apply");
+  return ODVAE_OK;
+}
+
 }  // namespace
 
 // device address of the recentring counter, for every launcher of gn_finalize_kernel (bf16_ops.hip too); nullptr if it cannot be found
@@ -609,46 +738,32 @@ int odvae_device_health(int* gn_timeouts, int* attn_fallbacks, int inject_gn_tim
 int odvae_groupnorm_fwd_f32(const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
                             float eps, int swish, float* y, float* mean, float* rstd,
                             void* workspace, size_t workspace_bytes, void* stream) {
-  GnShape s;
-  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "groupnorm_fwd: unsupported shape N=%d HW=%d C=%d G=%d (need C%%G==0, C%%4==0, C<=1024)", N, HW, C, G);
-  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd, "groupnorm_fwd: null operand");
-  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0,
-                  "groupnorm_fwd: operands must be 16-byte aligned");
-  const size_t need = (size_t)N * s.chunks * G * 2 * sizeof(float);
-  if (!workspace || workspace_bytes < need) {
-    odvae_set_error("groupnorm_fwd: needs %zu workspace bytes, got %zu", need, workspace_bytes);
-    return ODVAE_ERR_WORKSPACE;
-  }
-  unsigned* recentred = odvae_gn_recentred_counter();
-  ODVAE_CHECK_ARG(recentred, "groupnorm_fwd: cannot find the recentring counter on the device");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  float* partial = static_cast<float*>(workspace);
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(s.chunks, N), dim3(256), 0, st, x, s, partial);
-  ODVAE_LAUNCH_CHECK("groupnorm stats");
-  hipLaunchKernelGGL((gn_finalize_kernel<GnShape, float>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, x, s, eps, mean, rstd, recentred);
-  ODVAE_LAUNCH_CHECK("groupnorm finalize");
-  const dim3 grid(apply_blocks(s), N);
-  if (swish) hipLaunchKernelGGL((gn_apply_kernel<true>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y);
-  else       hipLaunchKernelGGL((gn_apply_kernel<false>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y);
-  ODVAE_LAUNCH_CHECK("groupnorm apply");
-  return ODVAE_OK;
+  return gn_fwd_impl("groupnorm_fwd", x, N, HW, C, G, gamma, beta, eps, swish, y, mean, rstd, workspace, workspace_bytes, stream, nullptr);
+}
+
+// The dropout form (ResnetBlock.norm2 in training, ddconfig.dropout > 0): y = keep * scale * act(GroupNorm(x)) with the mask of
+// dropout_mask.h made from (seed, p) inside the apply pass -- no mask tensor; mean / rstd are those of x (statistics come before the dropout)
+int odvae_groupnorm_fwd_drop_f32(const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                                 float eps, int swish, double p, unsigned long long seed, float* y, float* mean, float* rstd,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  if (const int rc = gn_drop_args("groupnorm_fwd_drop", p, C)) return rc;
+  const GnDrop d = make_gn_drop(p, seed);
+  return gn_fwd_impl("groupnorm_fwd_drop", x, N, HW, C, G, gamma, beta, eps, swish, y, mean, rstd, workspace, workspace_bytes, stream, &d);
 }
 
 // The apply pass alone, with mean / rstd given (as a forward call left them): y = act(GroupNorm(x)) re-made from x -- the recompute of
 // the "norm" activation-checkpoint policy (modules.py: the conv that consumed y keeps (x, mean, rstd) instead of y).
 int odvae_groupnorm_apply_f32(const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
                               const float* mean, const float* rstd, int swish, float* y, void* stream) {
-  GnShape s;
-  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "groupnorm_apply: unsupported shape N=%d HW=%d C=%d G=%d", N, HW, C, G);
-  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd, "groupnorm_apply: null operand");
-  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0,
-                  "groupnorm_apply: operands must be 16-byte aligned");
-  const dim3 grid(apply_blocks(s), N);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (swish) hipLaunchKernelGGL((gn_apply_kernel<true>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y);
-  else       hipLaunchKernelGGL((gn_apply_kernel<false>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y);
-  ODVAE_LAUNCH_CHECK("groupnorm apply");
-  return ODVAE_OK;
+  return gn_apply_impl("groupnorm_apply", x, N, HW, C, G, gamma, beta, mean, rstd, swish, y, stream, nullptr);
+}
+
+// ... of a dropout-form forward call: the same (seed, p) re-make the same mask
+int odvae_groupnorm_apply_drop_f32(const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                                   const float* mean, const float* rstd, int swish, double p, unsigned long long seed, float* y, void* stream) {
+  if (const int rc = gn_drop_args("groupnorm_apply_drop", p, C)) return rc;
+  const GnDrop d = make_gn_drop(p, seed);
+  return gn_apply_impl("groupnorm_apply_drop", x, N, HW, C, G, gamma, beta, mean, rstd, swish, y, stream, &d);
 }
 
 // The same with the statistics pass already done by the kernel that produced x: partial [N][chunks][G][2] = (sum, sum of squares) of x
@@ -657,30 +772,23 @@ int odvae_groupnorm_apply_f32(const float* x, int N, int HW, int C, int G, const
 int odvae_groupnorm_fwd_partials_f32(const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
                                      float eps, int swish, float* y, float* mean, float* rstd,
                                      const float* partial, int chunks, void* stream) {
-  GnShape s;
-  ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "groupnorm_fwd_partials: unsupported shape N=%d HW=%d C=%d G=%d (need C%%G==0, C%%4==0, C<=1024)", N, HW, C, G);
-  ODVAE_CHECK_ARG(x && gamma && beta && y && mean && rstd && partial && chunks > 0, "groupnorm_fwd_partials: null operand");
-  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0 &&
-                  ((uintptr_t)partial & 7) == 0, "groupnorm_fwd_partials: operands must be 16-byte aligned (partial: 8)");
-  unsigned* recentred = odvae_gn_recentred_counter();
-  ODVAE_CHECK_ARG(recentred, "groupnorm_fwd_partials: cannot find the recentring counter on the device");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  GnShape sf = s;
-  sf.chunks = chunks;
-  hipLaunchKernelGGL((gn_finalize_kernel<GnShape, float>), dim3(ceil_div(N * G, 4)), dim3(256), 0, st, partial, x, sf, eps, mean, rstd, recentred);
-  ODVAE_LAUNCH_CHECK("groupnorm finalize (partials)");
-  const dim3 grid(apply_blocks(s), N);
-  if (swish) hipLaunchKernelGGL((gn_apply_kernel<true>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y);
-  else       hipLaunchKernelGGL((gn_apply_kernel<false>), grid, dim3(256), 0, st, x, s, gamma, beta, mean, rstd, y);
-  ODVAE_LAUNCH_CHECK("groupnorm apply");
-  return ODVAE_OK;
+  return gn_fwd_partials_impl("groupnorm_fwd_partials", x, N, HW, C, G, gamma, beta, eps, swish, y, mean, rstd, partial, chunks, stream, nullptr);
+}
+
+int odvae_groupnorm_fwd_partials_drop_f32(const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                                          float eps, int swish, double p, unsigned long long seed, float* y, float* mean, float* rstd,
+                                          const float* partial, int chunks, void* stream) {
+  if (const int rc = gn_drop_args("groupnorm_fwd_partials_drop", p, C)) return rc;
+  const GnDrop d = make_gn_drop(p, seed);
+  return gn_fwd_partials_impl("groupnorm_fwd_partials_drop", x, N, HW, C, G, gamma, beta, eps, swish, y, mean, rstd, partial, chunks, stream, &d);
 }
 
 // dx, dgamma[C], dbeta[C] from dy (gradient w.r.t. the activated output), x and the saved mean/rstd
-int odvae_groupnorm_bwd_f32(const float* x, const float* dy, int N, int HW, int C, int G,
-                            const float* gamma, const float* beta, const float* mean, const float* rstd, int swish,
-                            float* dx, float* dgamma, float* dbeta, const float* dx_add,
-                            void* workspace, size_t workspace_bytes, void* stream) {
+// (drop != nullptr: the dropout form -- always reduce + apply, the mask re-made in both; never the read-once kernel)
+static int gn_bwd_impl(const float* x, const float* dy, int N, int HW, int C, int G,
+                       const float* gamma, const float* beta, const float* mean, const float* rstd, int swish,
+                       float* dx, float* dgamma, float* dbeta, const float* dx_add,
+                       void* workspace, size_t workspace_bytes, void* stream, const GnDrop* drop) {
   GnShape s;
   ODVAE_CHECK_ARG(make_shape(N, HW, C, G, s), "groupnorm_bwd: unsupported shape N=%d HW=%d C=%d G=%d", N, HW, C, G);
   ODVAE_CHECK_ARG(x && dy && gamma && beta && mean && rstd && dx && dgamma && dbeta, "groupnorm_bwd: null operand");
@@ -692,8 +800,8 @@ int odvae_groupnorm_bwd_f32(const float* x, const float* dy, int N, int HW, int 
     return ODVAE_ERR_WORKSPACE;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const GnFusedPlan pl = g_gn_bwd_mode != 0 ? gn_fused_plan(s, swish != 0) : GnFusedPlan{};
-  ODVAE_CHECK_ARG(g_gn_bwd_mode != 1 || pl.ok, "groupnorm_bwd: the fused form does not take N=%d HW=%d C=%d G=%d", N, HW, C, G);
+  const GnFusedPlan pl = (g_gn_bwd_mode != 0 && !drop) ? gn_fused_plan(s, swish != 0) : GnFusedPlan{};
+  ODVAE_CHECK_ARG(g_gn_bwd_mode != 1 || pl.ok || drop, "groupnorm_bwd: the fused form does not take N=%d HW=%d C=%d G=%d", N, HW, C, G);
   // Default (-1): the read-once kernel only where ONE block holds an item (HW <= 256: no barrier between blocks at all; measured 1.2x
   // the two-kernel form at 512 ch @16x16).  With teams it LOSES on this chip: 0.53-0.8x on the 64x64 .. 256x256 levels (B = 32) -- a
   // block can hold 128 KB, which streams in ~12 us, and every team barrier costs ~25 us of store drain, counter round trip, acquire,
@@ -721,19 +829,34 @@ int odvae_groupnorm_bwd_f32(const float* x, const float* dy, int N, int HW, int 
   float* partial = static_cast<float*>(workspace);
   float* chan = partial + (size_t)N * s.chunks * 2 * C;
   float* grp = chan + (size_t)N * 2 * C;
-  if (swish) hipLaunchKernelGGL((gn_bwd_reduce_kernel<true>), dim3(s.chunks, N), dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, partial);
-  else       hipLaunchKernelGGL((gn_bwd_reduce_kernel<false>), dim3(s.chunks, N), dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, partial);
+  launch_gn_bwd_reduce(s, st, x, dy, gamma, beta, mean, rstd, swish, partial, drop);
   ODVAE_LAUNCH_CHECK("groupnorm bwd reduce");
   if (s.cpg <= 64) hipLaunchKernelGGL(gn_bwd_finalize_kernel<GnShape>, dim3(N, ceil_div(C, (64 / s.cpg) * s.cpg)), dim3(256), 0, st, partial, s, gamma, chan, grp);
   else hipLaunchKernelGGL(gn_bwd_finalize_wide_kernel<GnShape>, dim3(N), dim3(256), 2 * C * sizeof(float), st, partial, s, gamma, chan, grp);
   ODVAE_LAUNCH_CHECK("groupnorm bwd finalize");
   hipLaunchKernelGGL(gn_bwd_param_kernel, dim3(ceil_div(C, 64)), dim3(256), 0, st, chan, N, C, dgamma, dbeta);
   ODVAE_LAUNCH_CHECK("groupnorm bwd param");
-  const dim3 grid(apply_blocks(s), N);
-  if (swish) hipLaunchKernelGGL((gn_bwd_apply_kernel<true>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, grp, dx_add, dx);
-  else       hipLaunchKernelGGL((gn_bwd_apply_kernel<false>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, grp, dx_add, dx);
+  launch_gn_bwd_apply(s, st, x, dy, gamma, beta, mean, rstd, grp, swish, dx_add, dx, drop);
   ODVAE_LAUNCH_CHECK("groupnorm bwd apply");
   return ODVAE_OK;
+}
+
+int odvae_groupnorm_bwd_f32(const float* x, const float* dy, int N, int HW, int C, int G,
+                            const float* gamma, const float* beta, const float* mean, const float* rstd, int swish,
+                            float* dx, float* dgamma, float* dbeta, const float* dx_add,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  return gn_bwd_impl(x, dy, N, HW, C, G, gamma, beta, mean, rstd, swish, dx, dgamma, dbeta, dx_add, workspace, workspace_bytes, stream, nullptr);
+}
+
+// Backward of the dropout forms: dy_eff = dy * keep * scale (the mask re-made from the forward call's seed and p), then the arithmetic of
+// odvae_groupnorm_bwd_f32's two-kernel form on dy_eff
+int odvae_groupnorm_bwd_drop_f32(const float* x, const float* dy, int N, int HW, int C, int G,
+                                 const float* gamma, const float* beta, const float* mean, const float* rstd, int swish,
+                                 double p, unsigned long long seed, float* dx, float* dgamma, float* dbeta, const float* dx_add,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  if (const int rc = gn_drop_args("groupnorm_bwd_drop", p, C)) return rc;
+  const GnDrop d = make_gn_drop(p, seed);
+  return gn_bwd_impl(x, dy, N, HW, C, G, gamma, beta, mean, rstd, swish, dx, dgamma, dbeta, dx_add, workspace, workspace_bytes, stream, &d);
 }
 
 // The same with the first pass already done: partial [N][chunks][2][C] = per chunk of pixels and channel (sum du * xhat, sum du), as the
@@ -763,8 +886,8 @@ int odvae_groupnorm_bwd_partials_f32(const float* x, const float* dy, int N, int
   hipLaunchKernelGGL(gn_bwd_param_kernel, dim3(ceil_div(C, 64)), dim3(256), 0, st, chan, N, C, dgamma, dbeta);
   ODVAE_LAUNCH_CHECK("groupnorm bwd param (partials)");
   const dim3 grid(apply_blocks(s), N);
-  if (swish) hipLaunchKernelGGL((gn_bwd_apply_kernel<true>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, grp, dx_add, dx);
-  else       hipLaunchKernelGGL((gn_bwd_apply_kernel<false>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, grp, dx_add, dx);
+  if (swish) hipLaunchKernelGGL((gn_bwd_apply_kernel<true>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, grp, dx_add, dx, GnNoDrop{});
+  else       hipLaunchKernelGGL((gn_bwd_apply_kernel<false>), grid, dim3(256), 0, st, x, dy, s, gamma, beta, mean, rstd, grp, dx_add, dx, GnNoDrop{});
   ODVAE_LAUNCH_CHECK("groupnorm bwd apply (partials)");
   return ODVAE_OK;
 }

@@ -12,6 +12,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "odvae_hip.h")
 
 _c = ctypes
 _P, _I, _L, _F, _Z = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_size_t
+_D, _U64 = _c.c_double, _c.c_uint64      # (p, seed) of the GroupNorm dropout forms
 
 ABI_VERSION = 4   # == ODVAE_ABI_VERSION in include/odvae_hip.h; bumped whenever the exported surface changes
 
@@ -70,6 +71,10 @@ PROTOTYPES = {
     "odvae_groupnorm_apply_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
     "odvae_groupnorm_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "odvae_groupnorm_bwd_partials_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
+    "odvae_groupnorm_fwd_drop_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _D, _U64, _P, _P, _P, _P, _Z, _P]),
+    "odvae_groupnorm_fwd_partials_drop_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _D, _U64, _P, _P, _P, _P, _I, _P]),
+    "odvae_groupnorm_apply_drop_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _D, _U64, _P, _P]),
+    "odvae_groupnorm_bwd_drop_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _D, _U64, _P, _P, _P, _P, _P, _Z, _P]),
     "odvae_groupnorm_select_backward": (_I, [_I]),
     "odvae_groupnorm_fused_timeouts": (_I, []),
     "odvae_device_health": (_I, [_P, _P, _I, _I]),
@@ -130,6 +135,10 @@ PROTOTYPES = {
     "odvae_groupnorm_fwd_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _Z, _P]),
     "odvae_groupnorm_fwd_partials_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _I, _P]),
     "odvae_groupnorm_bwd_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "odvae_groupnorm_fwd_drop_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _D, _U64, _P, _P, _P, _P, _Z, _P]),
+    "odvae_groupnorm_fwd_partials_drop_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _D, _U64, _P, _P, _P, _P, _I, _P]),
+    "odvae_groupnorm_apply_drop_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _D, _U64, _P, _P]),
+    "odvae_groupnorm_bwd_drop_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _D, _U64, _P, _P, _P, _P, _P, _Z, _P]),
     "odvae_cast_pad_bf16": (_I, [_P, _L, _I, _I, _P, _P]),
     "odvae_cast_f32_from_bf16": (_I, [_P, _L, _P, _P]),
     "odvae_upsample2x_bwd_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),

@@ -22,11 +22,14 @@ class Normalize(nn.GroupNorm):
     def __init__(self, channels, num_groups=32):
         super().__init__(num_groups=num_groups, num_channels=channels, eps=1e-6, affine=True)
 
-    def forward(self, x, swish=False, skip=False):
+    def forward(self, x, swish=False, skip=False, drop_p=0.0, drop_seed=None):
         """skip=True also returns x for the block's skip connection; its gradient is then summed inside this node's
-        backward pass (ops.group_norm_skip)."""
+        backward pass (ops.group_norm_skip).  drop_p > 0 (not with skip): the ResnetBlock dropout on the result, its mask made
+        from (drop_seed, element index, drop_p) inside the kernel (ops.group_norm)."""
         if skip:
             return ops.group_norm_skip(x, self.weight, self.bias, self.num_groups, self.eps, swish)
+        if drop_p > 0.0:
+            return ops.group_norm(x, self.weight, self.bias, self.num_groups, self.eps, swish, drop_p=drop_p, drop_seed=drop_seed)
         return ops.group_norm(x, self.weight, self.bias, self.num_groups, self.eps, swish)
 
 
@@ -89,8 +92,6 @@ class ResnetBlock(nn.Module):
     def __init__(self, *, in_channels, out_channels=None, conv_shortcut=False, dropout=0.0, temb_channels=512):
         super().__init__()
         out_channels = in_channels if out_channels is None else out_channels
-        if dropout != 0.0:
-            raise NotImplementedError("ResnetBlock dropout > 0 is not used by the OD-VAE configs (ddconfig.dropout: 0.0)")
         if temb_channels > 0:
             raise NotImplementedError("timestep embedding is not part of the autoencoder path (temb_ch = 0)")
         self.in_channels, self.out_channels = in_channels, out_channels
@@ -101,7 +102,10 @@ class ResnetBlock(nn.Module):
         self.norm1 = Normalize(in_channels)
         self.conv1 = Conv3x3(in_channels, out_channels)
         self.norm2 = Normalize(out_channels)
+        # ddconfig.dropout.  nn.Dropout validates 0 <= p <= 1 (ValueError) and keeps the module tree / state_dict of the reference; its
+        # forward is never called: in training with p > 0 norm2's kernels apply the mask (forward below)
         self.dropout = nn.Dropout(dropout)
+        self.last_dropout_seed = None      # the seed of the latest training forward with dropout (tests, debugging; nothing reads it)
         self.conv2 = Conv3x3(out_channels, out_channels)
         if in_channels != out_channels:
             if conv_shortcut:
@@ -115,7 +119,14 @@ class ResnetBlock(nn.Module):
         h, x = self.norm1(x, swish=True, skip=True)
         with _remake(self, h):
             h1 = self.conv1(h, gn_stats=True)
-        h = self.norm2(h1, swish=True)
+        if self.training and self.dropout.p > 0:
+            # conv2(dropout(swish(norm2(h)))): the seed comes from torch's default CPU generator (no device work, no sync), so
+            # torch.manual_seed reproduces a run and torch.utils.checkpoint's restored generator state re-draws it in a recompute
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+            self.last_dropout_seed = seed
+            h = self.norm2(h1, swish=True, drop_p=float(self.dropout.p), drop_seed=seed)
+        else:
+            h = self.norm2(h1, swish=True)
         del h1
         if self.in_channels != self.out_channels:
             x = self.conv_shortcut(x) if self.use_conv_shortcut else self.nin_shortcut(x)

@@ -190,6 +190,31 @@ int odvae_groupnorm_bwd_partials_f32(const float* x, const float* dy, int N, int
                                      const float* gamma, const float* beta, const float* mean, const float* rstd, int swish,
                                      float* dx, float* dgamma, float* dbeta, const float* dx_add, const float* partial, int chunks,
                                      void* workspace, size_t workspace_bytes, void* stream);
+/* ---- ResnetBlock dropout inside GroupNorm (+ swish): y = keep * scale * act(GroupNorm(x)), ddconfig.dropout of the reference's yaml
+ * ([UPSTREAM] model.py ResnetBlock: conv2(dropout(nonlinearity(norm2(h))))).  The mask is a pure function of (seed, element index, p),
+ * re-made inside every kernel -- no mask tensor, nothing but (p, seed) to keep for the backward (csrc/dropout_mask.h; the package's
+ * dropout_mask.py restates it in numpy, bit for bit):
+ *   one Philox4x32-10 call (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments 0x9E3779B9 / 0xBB67AE85) per 8 consecutive channels of
+ *   a pixel: octet g = ((n * HW + px) * C + c) / 8 (64-bit), counter = (lo32(g), hi32(g), 0, 0), key = (lo32(seed), hi32(seed)); the four
+ *   output words are eight 16-bit lanes, channel 8g + 2j the low half of word j and channel 8g + 2j + 1 the high half; an element is
+ *   dropped iff lane < thr = round-half-even(p * 65536) (so p = 1 drops everything); kept elements are multiplied by
+ *   scale = (float)(1 / (1 - p)), 0 at p = 1.
+ * Needs 0 <= p <= 1 and C % 8 == 0 (ODVAE_ERR_ARG otherwise); every other argument as in the plain form of the same name.  The statistics
+ * (mean, rstd, the conv epilogue's partials) are those of x: they come before the dropout.  The backward forms dy_eff = dy * keep * scale and
+ * runs the reduce + apply kernels on it (never the read-once kernel; there is no bwd_partials form: the sums of
+ * odvae_conv3x3_wino4_gnbwd_f32 know nothing of the mask). */
+int odvae_groupnorm_fwd_drop_f32(const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                                 float eps, int swish, double p, unsigned long long seed, float* y, float* mean, float* rstd,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int odvae_groupnorm_fwd_partials_drop_f32(const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                                          float eps, int swish, double p, unsigned long long seed, float* y, float* mean, float* rstd,
+                                          const float* partial, int chunks, void* stream);
+int odvae_groupnorm_apply_drop_f32(const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                                   const float* mean, const float* rstd, int swish, double p, unsigned long long seed, float* y, void* stream);
+int odvae_groupnorm_bwd_drop_f32(const float* x, const float* dy, int N, int HW, int C, int G,
+                                 const float* gamma, const float* beta, const float* mean, const float* rstd, int swish,
+                                 double p, unsigned long long seed, float* dx, float* dgamma, float* dbeta, const float* dx_add,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 /* backward form of odvae_groupnorm_bwd_f32: -1 (default) the read-once kernel where ONE block holds a (sample, 32-channel slab) in its
  * registers (HW <= 256; C % 32 == 0, whole groups per slab), reduce + apply (x and dy read twice) elsewhere; 0 always reduce + apply;
  * 1 the read-once kernel on every shape it takes (teams of ceil(HW / 256) resident blocks that meet at a per-item barrier in L2 --
@@ -403,6 +428,19 @@ int odvae_groupnorm_fwd_partials_bf16(const void* x, int N, int HW, int C, int G
 int odvae_groupnorm_bwd_bf16(const void* x, const void* dy, int N, int HW, int C, int G, const float* gamma, const float* beta,
                              const float* mean, const float* rstd, int swish, void* dx, float* dgamma, float* dbeta, const void* dx_add,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* the dropout forms (see odvae_groupnorm_fwd_drop_f32): the multiply is in f32 before the single rounding of y; dy_eff is not rounded */
+int odvae_groupnorm_fwd_drop_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
+                                  double p, unsigned long long seed, void* y, float* mean, float* rstd,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int odvae_groupnorm_fwd_partials_drop_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
+                                           double p, unsigned long long seed, void* y, float* mean, float* rstd,
+                                           const float* partial, int chunks, void* stream);
+int odvae_groupnorm_apply_drop_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                                    const float* mean, const float* rstd, int swish, double p, unsigned long long seed, void* y, void* stream);
+int odvae_groupnorm_bwd_drop_bf16(const void* x, const void* dy, int N, int HW, int C, int G, const float* gamma, const float* beta,
+                                  const float* mean, const float* rstd, int swish, double p, unsigned long long seed,
+                                  void* dx, float* dgamma, float* dbeta, const void* dx_add,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 /* y bf16 [rows][CP] = x f32 [rows][C], channels C..CP-1 zero (CP % 8 == 0) */
 int odvae_cast_pad_bf16(const float* x, int64_t rows, int C, int CP, void* y, void* stream);
 int odvae_cast_f32_from_bf16(const void* x, int64_t n, float* y, void* stream);
