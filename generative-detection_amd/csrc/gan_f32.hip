@@ -79,8 +79,15 @@ __global__ void weight4x4_reorder_kernel(const float* __restrict__ src, float* _
 }
 
 // ---- per-channel statistics over rows of an [M][C] matrix (shared by BN forward and backward) ---------------
-// part[blk][2][C]: sums of f1 and f2 per channel, where (f1,f2) = (x, x^2) for MODE 0 and
-// (g, g*xhat) for MODE 1 with g = dy * lrelu'(u), u = xhat*gamma+beta
+// part[blk][2][C]: sums of f1 and f2 per channel, where (f1,f2) = (d, d^2), d = x - x[0][c], for MODE 0 and
+// (g, g*xhat) for MODE 1 with g = dy * lrelu'(u), u = xhat*gamma+beta.
+// MODE 0 sums about a pivot, the channel's value in row 0: the PatchGAN convolutions have no bias and read LeakyReLU outputs, so a
+// channel's mean can lie many standard deviations from zero, and var = E[x^2] - E[x]^2 from f32 sums of x and x^2 loses ~ 2^-24 r^2 of
+// the variance, r = |mean| / std (from r = 64 on rstd was outside the tests' rule at every shape; at r >= 256 no variance was left).
+// d is of the size of the spread whatever the mean is, and x - pivot is exact for neighbouring values.  The pivot is one sample: if it
+// lies k standard deviations from the channel's mean the sums lose ~ 2^-24 k^2 again, so this holds for channels whose row 0 is no far
+// outlier (k of a few, as for any light-tailed activation), not for a value planted hundreds of deviations out
+// (tests/test_batchnorm_offset_gpu.py, profiles/bn_offset.md).
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_colstats_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                           const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -96,11 +103,12 @@ __global__ __launch_bounds__(256) void bn_colstats_kernel(const float* __restric
     const int c = cbase + threadIdx.x % cw, rl = threadIdx.x / cw;
     float a = 0.f, b = 0.f;
     if (rl < lanes) {
-      float mu = 0.f, rs = 0.f, ga = 0.f, be = 0.f;
+      float mu = 0.f, rs = 0.f, ga = 0.f, be = 0.f, pivot = 0.f;
       if (MODE == 1) { mu = mean[c]; rs = rstd[c]; ga = gamma[c]; be = beta[c]; }
+      else pivot = x[c];
       for (int64_t r = r0 + rl; r < r1; r += lanes) {
         const float v = x[r * C + c];
-        if (MODE == 0) { a += v; b += v * v; }
+        if (MODE == 0) { const float d = v - pivot; a += d; b += d * d; }
         else {
           const float xh = (v - mu) * rs;
           const float u = xh * ga + be;
@@ -121,8 +129,9 @@ __global__ __launch_bounds__(256) void bn_colstats_kernel(const float* __restric
   }
 }
 
-// training-mode forward statistics: mean, rstd and the running estimates (momentum update, unbiased variance)
-__global__ void bn_finalize_kernel(const float* __restrict__ part, int nblk, int C, int64_t rows, float eps, float momentum,
+// training-mode forward statistics: mean, rstd and the running estimates (momentum update, unbiased variance) from the sums about
+// the pivot x[0][c]: mean = pivot + E[d], var = E[d^2] - E[d]^2
+__global__ void bn_finalize_kernel(const float* __restrict__ part, const float* __restrict__ x, int nblk, int C, int64_t rows, float eps, float momentum,
                                    float* __restrict__ mean, float* __restrict__ rstd,
                                    float* __restrict__ running_mean, float* __restrict__ running_var) {
   // one wavefront per channel: the partials are summed lane-strided in f64, then by a fixed butterfly (deterministic).  One thread per
@@ -135,8 +144,9 @@ __global__ void bn_finalize_kernel(const float* __restrict__ part, int nblk, int
   a = wave_sum_f64(a); b = wave_sum_f64(b);
   if (lane != 0) return;
   const double m = (double)rows;
-  const double mu = a / m;
-  double var = b / m - mu * mu;
+  const double dm = a / m;
+  const double mu = (double)x[c] + dm;
+  double var = b / m - dm * dm;
   if (var < 0.0) var = 0.0;
   mean[c] = (float)mu;
   rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
@@ -252,7 +262,7 @@ int odvae_batchnorm_lrelu_fwd_f32(const float* x, int64_t rows, int C, const flo
     const int rpb = (int)ceil_div64(rows, nblk);
     const int nb = (int)ceil_div64(rows, rpb);
     hipLaunchKernelGGL((bn_colstats_kernel<0>), dim3(nb), dim3(256), 0, st, x, nullptr, nullptr, nullptr, nullptr, nullptr, slope, rows, C, rpb, part);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nb, C, rows, eps, momentum, mean, rstd, running_mean, running_var);
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, x, nb, C, rows, eps, momentum, mean, rstd, running_mean, running_var);
   }
   hipLaunchKernelGGL(bn_lrelu_apply_kernel, dim3(grid_1d(rows * C)), dim3(256), 0, st, x, mean, rstd, gamma, beta, slope, rows * C, C, y);
   ODVAE_LAUNCH_CHECK("batchnorm_lrelu_fwd");

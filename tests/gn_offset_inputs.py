@@ -1,8 +1,9 @@
 """GroupNorm inputs whose group means lie far from zero: generators, references, host models, the acceptance rule.
 
-Every statistics kernel of the library forms var = E[x^2] - E[x]^2 from f32 partial sums.  The subtraction cancels: the relative error
+The GroupNorm statistics kernels of the library form var = E[x^2] - E[x]^2 from f32 partial sums (the BatchNorm one sums about a
+per-channel pivot instead: tests/bn_offset_inputs.py).  The subtraction cancels: the relative error
 of the variance grows like u (1 + r^2) with r = |mean| / std of a (sample, group) and u = 2^-24, where a centred (two-pass, Welford)
-evaluation grows like u r.  `torch.nn.GroupNorm`, which the reference model runs, is of the second kind.  This module makes inputs
+evaluation grows like u r; `gn_finalize_kernel` therefore recentres the groups whose mean is far from zero.  `torch.nn.GroupNorm`, which the reference model runs, is of the second kind.  This module makes inputs
 with a chosen r (`make_input`: x = s (randn + r sign_g), sign_g alternating from one group to the next), the two references every GPU
 test of tests/test_groupnorm_offset_gpu.py compares against (`ref64`: float64; `ref32`: torch f32 on the host, what the reference
 project computes), two host stand-ins for kernels (`two_pass_f32`: centred; `one_pass_model`: the uncentred design with sequential f32

@@ -118,24 +118,41 @@ def test_small_ops(hip_lib):
     close(xcd.grad, xcr.grad, 5e-4, "conv+relu dx")
 
 
-@pytest.mark.parametrize("c", [64, 128, 512])
-def test_lpips_layer_distance(hip_lib, c):
-    from odvae_amd import ops
-    g = torch.Generator().manual_seed(c)
-    f0 = torch.relu(torch.randn(2, c, 6, 5, generator=g))
-    f1 = torch.relu(torch.randn(2, c, 6, 5, generator=g))
-    w = torch.rand(1, c, 1, 1, generator=g) / c
-    f1r = f1.clone().requires_grad_(True)
+def _lpips_reference(f0, f1, w, gw, dt):
+    f0, w, gw = f0.to(dt), w.to(dt), gw.to(dt)
+    f1r = f1.to(dt).clone().requires_grad_(True)
     n0 = f0 / (torch.sqrt(torch.sum(f0 ** 2, dim=1, keepdim=True)) + 1e-10)
     n1 = f1r / (torch.sqrt(torch.sum(f1r ** 2, dim=1, keepdim=True)) + 1e-10)
     ref = F.conv2d((n0 - n1) ** 2, w).mean([1, 2, 3])
-    gw = torch.randn(2, generator=g)
     (ref * gw).sum().backward()
+    return ref.detach(), f1r.grad
+
+
+# the last two: one pixel per image (the mean over pixels is the pixel itself), and a pixel count that is no multiple of any block size
+@pytest.mark.parametrize("c,h,w", [(64, 6, 5), (128, 6, 5), (512, 6, 5), (256, 1, 1), (64, 1, 1031)], ids=["64", "128", "512", "256-hw1", "64-hw1031"])
+def test_lpips_layer_distance(hip_lib, c, h, w):
+    """Against torch f32 at the per-op tolerances, and against float64 under the acceptance rule of gn_offset_inputs with the
+    distances in units of their float64 values (they are of size 1e-2) and the gradient in units of its largest float64 entry.
+    relu(randn) over >= 64 channels leaves no pixel whose feature vector is all zero (torch's own gradient there is NaN)."""
+    import gn_offset_inputs as G
+    from odvae_amd import ops
+    g = torch.Generator().manual_seed(c + 7 * (h * w - 30))
+    f0 = torch.relu(torch.randn(2, c, h, w, generator=g))
+    f1 = torch.relu(torch.randn(2, c, h, w, generator=g))
+    assert (f0.sum(1) > 0).all() and (f1.sum(1) > 0).all()
+    wt = torch.rand(1, c, 1, 1, generator=g) / c
+    gw = torch.randn(2, generator=g)
+    ref, grad = _lpips_reference(f0, f1, wt, gw, torch.float32)
+    ref64, grad64 = _lpips_reference(f0, f1, wt, gw, torch.float64)
     f1d = f1.to(DEV).requires_grad_(True)
-    out = ops.lpips_layer_distance(f0.to(DEV), f1d, w.to(DEV))
+    out = ops.lpips_layer_distance(f0.to(DEV), f1d, wt.to(DEV))
     close(out, ref, 2e-5, "lpips dist")
     (out * gw.to(DEV)).sum().backward()
-    close(f1d.grad, f1r.grad, 2e-4, "lpips dist bwd")
+    close(f1d.grad, grad, 2e-4, "lpips dist bwd")
+    gmax = grad64.abs().max()
+    G.check([G.figure("distance / d64", out.cpu().double() / ref64, torch.ones_like(ref64), ref.double() / ref64, G.FLOOR_FWD),
+             G.figure("gradient / max |g64|", f1d.grad.cpu().double() / gmax, grad64 / gmax, grad.double() / gmax, G.FLOOR_DX)],
+            "lpips layer distance C=%d HW=%d" % (c, h * w))
 
 
 def test_discriminator_matches_oracle(hip_lib):
