@@ -131,6 +131,12 @@ PROTOTYPES = {
     "odvae_flash_attn_f32_supported": (_I, [_I, _I, _I]),
     "odvae_flash_attn_fwd_f32": (_I, [_P, _I, _I, _I, _F, _P, _P, _P]),
     "odvae_flash_attn_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
+    "odvae_linattn_ctx_split": (_I, []),
+    "odvae_linattn_colstats_workspace_bytes": (_Z, [_I, _I, _I]),
+    "odvae_linattn_colstats_f32": (_I, [_P, _I, _L, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "odvae_linattn_ctx_workspace_bytes": (_Z, [_I, _I, _I]),
+    "odvae_linattn_ctx_f32": (_I, [_P, _P, _I, _L, _P, _P, _I, _I, _I, _P, _P, _Z, _P]),
+    "odvae_linattn_dkv_f32": (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _L, _P]),
     "odvae_groupnorm_bf16_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "odvae_groupnorm_fwd_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _Z, _P]),
     "odvae_groupnorm_fwd_partials_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _I, _P]),

@@ -48,8 +48,8 @@ class Conv3x3(nn.Conv2d):
 
 
 class Conv1x1(nn.Conv2d):
-    def __init__(self, cin, cout):
-        super().__init__(cin, cout, kernel_size=1, stride=1, padding=0)
+    def __init__(self, cin, cout, bias=True):
+        super().__init__(cin, cout, kernel_size=1, stride=1, padding=0, bias=bias)
 
     def forward(self, x, residual=None):
         return ops.conv1x1(x, self.weight, self.bias, residual)
@@ -159,11 +159,32 @@ class AttnBlock(nn.Module):
         return self.proj_out(o, residual=x)
 
 
+class LinAttnBlock(nn.Module):
+    """[UPSTREAM] LinAttnBlock(in_channels) = LinearAttention(dim=C, heads=1, dim_head=C): to_out(q ctx) with ctx = softmax(k over the
+    tokens)^T v.  No GroupNorm, no residual add, no softmax over q, no C^-0.5 scale; state_dict: to_qkv.weight, to_out.weight, to_out.bias.
+    Under compute_dtype = bfloat16 the two 1x1 convs run on the bf16 kernels; the projection leaves its conv in f32 (its f32-output
+    form), the attention core runs in f32 (ops.linear_attention_qkv) and one ops.to_bf16 hands the result to to_out."""
+
+    def __init__(self, in_channels):
+        super().__init__()
+        self.in_channels = in_channels
+        self.to_qkv = Conv1x1(in_channels, 3 * in_channels, bias=False)
+        self.to_out = Conv1x1(in_channels, in_channels)
+
+    def forward(self, x):
+        if x.dtype == torch.bfloat16:
+            qkv = ops.conv1x1(x, self.to_qkv.weight, None, out_f32=True)
+            return self.to_out(ops.to_bf16(ops.linear_attention_qkv(qkv)))
+        return self.to_out(ops.linear_attention_qkv(self.to_qkv(x)))
+
+
 def make_attn(in_channels, attn_type="vanilla"):
     if attn_type == "none":
         return nn.Identity()
+    if attn_type == "linear":
+        return LinAttnBlock(in_channels)
     if attn_type != "vanilla":
-        raise NotImplementedError("attn_type %r: only 'vanilla' is on the OD-VAE path" % attn_type)
+        raise NotImplementedError("attn_type %r: 'vanilla', 'linear' and 'none' are on the OD-VAE path" % attn_type)
     return AttnBlock(in_channels)
 
 
@@ -281,7 +302,7 @@ class Decoder(nn.Module):
         h = self.conv_in(z)
         norm_policy = self.activation_checkpoint == "norm"
         for m in self.modules():
-            if isinstance(m, (ResnetBlock, AttnBlock)):
+            if isinstance(m, (ResnetBlock, AttnBlock)):      # (a LinAttnBlock has no norm to re-make)
                 m.recompute_norm = norm_policy
         recompute = bool(self.activation_checkpoint) and not norm_policy and torch.is_grad_enabled() and h.requires_grad
         def ckpt(f, t):      # (no GroupNorm-backward links inside a checkpointed unit: ops.GN_FUSED_BWD_SUSPENDED)

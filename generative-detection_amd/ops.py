@@ -687,9 +687,10 @@ class _Conv1x1(Function):
         return dx, dw, db, dres
 
 
-def conv1x1(x, weight, bias=None, residual=None):
+def conv1x1(x, weight, bias=None, residual=None, out_f32=False):
+    """out_f32: bf16 input only -- the result leaves the conv in f32 (no residual then)."""
     if x.dtype == BF16:
-        return _ConvB.apply(x, weight, bias, residual, 4, False)
+        return _ConvB.apply(x, weight, bias, residual, 4, bool(out_f32))
     return _Conv1x1.apply(x, weight, bias, residual)
 
 
@@ -901,6 +902,74 @@ def attention_qkv(qkv):
     if n * per_image > ATTN_SCORE_BUDGET:
         return _AttentionRecompute.apply(qkv, max(1, ATTN_SCORE_BUDGET // per_image))
     return _Attention.apply(qkv)
+
+
+class _LinearAttention(Function):
+    """Linear attention over T = H*W tokens from a packed projection [N, 3C, H, W] ([UPSTREAM] LinearAttention, heads = 1):
+    k' = softmax(k over the tokens, per image and channel), ctx = k'^T v [N, C, C], out = q ctx.  No scale, no softmax over q.
+    Work 4 T C^2 per image (the vanilla block: 4 T^2 C).  Kept for the backward: qkv, ctx and the column statistics (max, 1 / sum)
+    of k -- neither out nor k' (linattn_f32.hip re-makes k' from k and the statistics in its loaders)."""
+
+    @staticmethod
+    def forward(ctx_, qkv):
+        L = _L()
+        qkv = _aligned_cl(qkv)
+        n, c3, h, w = qkv.shape
+        c, t = c3 // 3, h * w
+        if c3 != 3 * c or c % 32 != 0 or t < 1:
+            raise _lib.HipLibraryError("linear attention: needs [N, 3C, H, W] with C a multiple of 32, got %s" % (tuple(qkv.shape),))
+        q, k, v = _qkv_views(qkv, c)
+        sq, st = t * c3, _lib.stream_ptr()
+        stats = torch.empty(2, n, c, dtype=torch.float32, device=qkv.device)       # [0]: column maxima of k, [1]: 1 / sum exp(k - max)
+        cx = torch.empty(n, c, c, dtype=torch.float32, device=qkv.device)
+        wp, wn = _ws(L.odvae_linattn_colstats_workspace_bytes(n, t, c), qkv)
+        tag = KERNEL_EVENTS.begin(secondary=True)
+        _lib.check(L.odvae_linattn_colstats_f32(k.data_ptr(), c3, sq, n, t, c, stats[0].data_ptr(), stats[1].data_ptr(), wp, wn, st),
+                   "linattn_colstats")
+        KERNEL_EVENTS.end("linattn_colstats", 0.0, tag, 4.0 * n * t * c, issued=0.0)
+        wp, wn = _ws(L.odvae_linattn_ctx_workspace_bytes(n, t, c), qkv)
+        tag = KERNEL_EVENTS.begin(secondary=True)
+        _lib.check(L.odvae_linattn_ctx_f32(k.data_ptr(), v.data_ptr(), c3, sq, stats[0].data_ptr(), stats[1].data_ptr(), n, t, c,
+                                           cx.data_ptr(), wp, wn, st), "linattn_ctx")
+        KERNEL_EVENTS.end("linattn_ctx", 2.0 * t * c * c * n, tag, 4.0 * n * (2 * t * c + c * c))
+        o = _new_cl(n, c, h, w, qkv)
+        gemm(0, 0, t, c, c, 1.0, q, c3, sq, cx, c, c * c, o, c, t * c, batch=n)                           # out = q ctx
+        ctx_.save_for_backward(qkv, cx, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx_, do):
+        L = _L()
+        qkv, cx, stats = ctx_.saved_tensors
+        do = _cl(do)
+        n, c3, h, w = qkv.shape
+        c, t = c3 // 3, h * w
+        sq = t * c3
+        q, k, v = _qkv_views(qkv, c)
+        dqkv = _new_cl(n, c3, h, w, qkv)
+        dq, dk, dv = _qkv_views(dqkv, c)
+        dcx = torch.empty_like(cx)
+        gemm(1, 0, c, c, t, 1.0, q, c3, sq, do, c, t * c, dcx, c, c * c, batch=n)                         # dctx = q^T dOut
+        gemm(0, 1, t, c, c, 1.0, do, c, t * c, cx, c, c * c, dq, c3, sq, batch=n)                         # dq = dOut ctx^T
+        # g[d] = ctx[d] . dctx[d] = sum_n k'[n][d] dk'[n][d]: the softmax backward's reduction over the tokens, from two C x C tensors
+        g = torch.empty(n, c, dtype=torch.float32, device=qkv.device)
+        _lib.check(L.odvae_rowdot_f32(cx.data_ptr(), dcx.data_ptr(), n * c, c, g.data_ptr(), _lib.stream_ptr()), "rowdot")
+        tag = KERNEL_EVENTS.begin(secondary=True)
+        _lib.check(L.odvae_linattn_dkv_f32(k.data_ptr(), v.data_ptr(), c3, sq, stats[0].data_ptr(), stats[1].data_ptr(), dcx.data_ptr(),
+                                           g.data_ptr(), n, t, c, dk.data_ptr(), dv.data_ptr(), c3, sq, _lib.stream_ptr()), "linattn_dkv")
+        KERNEL_EVENTS.end("linattn_dkv", 4.0 * t * c * c * n, tag, 4.0 * n * (4 * t * c + c * c))
+        return dqkv
+
+
+def linear_attention_qkv(qkv):
+    """out [N, C, H, W] f32 of the linear attention on a packed f32 projection [N, 3C, H, W] (q | k | v channel thirds); any strides."""
+    _lib.require_device(qkv)
+    return _LinearAttention.apply(qkv)
+
+
+# Tokens per workgroup of the context product (CTX_SPLIT of linattn_f32.hip, odvae_linattn_ctx_split()): from T = this + 1 on the product
+# adds partial tiles from workspace.  Named here so that tests can place T around it; tests/test_linattn_gpu.py holds it to the library's.
+LINATTN_CTX_SPLIT = 1024
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -418,6 +418,26 @@ int odvae_flash_attn_fwd_f32(const float* qkv, int N, int T, int C, float scale,
 /* dqkv f32 [N][T][3C] from d_o, o, lse2; delta f32 [N*T] receives rowsum(d_o * o).  No atomics: bit-reproducible */
 int odvae_flash_attn_bwd_f32(const float* qkv, const float* o, const float* d_o, const float* lse2, int N, int T, int C, float scale,
                              float* dqkv, float* delta, void* stream);
+/* ---- linattn_f32.hip: linear attention ([UPSTREAM] LinAttnBlock = LinearAttention(dim C, heads 1, dim_head C)) ------------------
+ * q, k, v are the channel thirds of the packed projection [N][T][3C]: pointers to the first token's channels, ld = floats between
+ * tokens (3C), stride = floats between images.  k' = softmax(k over the T tokens, per image and channel); ctx [N][C][C],
+ * ctx[d][e] = sum_n k'[n][d] v[n][e]; out = q ctx is odvae_gemm_f32.  Softmaxed k is never written; nothing of size T x T exists.
+ * Every entry point: ODVAE_ERR_ARG for C not a positive multiple of 32, T < 1, N outside 1..65535 or a null pointer (no launch).
+ * All reductions run in a fixed order without atomics: results are bit-reproducible. */
+int odvae_linattn_ctx_split(void);     /* tokens per workgroup of the context product: the depth at which it starts to split T */
+size_t odvae_linattn_colstats_workspace_bytes(int N, int T, int C);
+/* mx [N][C] = max_n k[n][c], rinv [N][C] = 1 / sum_n exp(k[n][c] - mx[c]) */
+int odvae_linattn_colstats_f32(const float* k, int ld, int64_t stride, int N, int T, int C, float* mx, float* rinv,
+                               void* workspace, size_t workspace_bytes, void* stream);
+size_t odvae_linattn_ctx_workspace_bytes(int N, int T, int C);
+/* ctx[d][e] = rinv[d] sum_n exp(k[n][d] - mx[d]) v[n][e] on v_mfma_f32_32x32x2_f32, exp applied as k is loaded, T split across workgroups */
+int odvae_linattn_ctx_f32(const float* k, const float* v, int ld, int64_t stride, const float* mx, const float* rinv, int N, int T, int C,
+                          float* ctx, void* workspace, size_t workspace_bytes, void* stream);
+/* backward for k and v from dctx [N][C][C] and g [N][C], g[d] = sum_e ctx[d][e] dctx[d][e]; with s = exp(k - mx) rinv:
+ * dv[n][e] = sum_d s[n][d] dctx[d][e], dk[n][d] = s[n][d] (sum_e v[n][e] dctx[d][e] - g[d]); dk, dv: leading dimension ldo, image stride
+ * stride_o (the k and v thirds of a packed dqkv).  k, v, mx, rinv, dctx 16-byte aligned, ld and stride multiples of 4. */
+int odvae_linattn_dkv_f32(const float* k, const float* v, int ld, int64_t stride, const float* mx, const float* rinv, const float* dctx,
+                          const float* g, int N, int T, int C, float* dk, float* dv, int ldo, int64_t stride_o, void* stream);
 /* ---- bf16_ops.hip: GroupNorm(32, eps 1e-6) + swish with bf16 activations / f32 statistics, dtype hand-offs ---------------------- */
 size_t odvae_groupnorm_bf16_workspace_bytes(int N, int HW, int C, int G);
 int odvae_groupnorm_fwd_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
