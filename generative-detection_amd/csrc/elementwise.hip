@@ -457,6 +457,59 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     }
 }
 
+// ---- gradient accumulation: arena[dst_off[i] + j] += src[i][j] over up to kGradAccSegs tensors per launch (Trainer(accumulate_grad_batches=N),
+// optim.FusedAdam.gather_grads(accumulate=True)).  The segment table is a by-value kernel argument: no upload, no device allocation.  A segment is
+// cut into chunks of kGradAccChunk floats; chunk_prefix[i] = chunks in front of segment i, so a block finds the segment of its chunk by a
+// (block-uniform) binary search.  Every element is read and written by exactly one thread: plain f32 adds, no atomics, the same bits on any grid.
+constexpr int kGradAccSegs = 128;
+constexpr int kGradAccChunk = 4096;      // floats: four float4 per thread of a 256-thread block
+struct GradAccTable {
+  float* dst[kGradAccSegs];
+  const float* src[kGradAccSegs];
+  int64_t numel[kGradAccSegs];
+  unsigned chunk_prefix[kGradAccSegs + 1];
+  int count;
+};
+static_assert(sizeof(GradAccTable) <= 4000, "the segment table travels in the kernel arguments (4 KiB)");
+
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(const GradAccTable t) {
+  const unsigned total = t.chunk_prefix[t.count];
+  for (unsigned c = blockIdx.x; c < total; c += gridDim.x) {
+    int lo = 0, hi = t.count - 1;            // last segment whose prefix <= c
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (t.chunk_prefix[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    const int64_t base = (int64_t)(c - t.chunk_prefix[lo]) * kGradAccChunk;
+    float* __restrict__ d = t.dst[lo] + base;
+    const float* __restrict__ s = t.src[lo] + base;
+    const int64_t left = t.numel[lo] - base;
+    const int n = left < kGradAccChunk ? (int)left : kGradAccChunk;
+    if ((((uintptr_t)d | (uintptr_t)s) & 15) == 0) {
+      const int n4 = n >> 2;
+      if (n4 == kGradAccChunk / 4) {         // full chunk: all eight loads in flight before the first add
+        float4 a[4], b[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          a[k] = reinterpret_cast<const float4*>(d)[threadIdx.x + 256 * k];
+          b[k] = reinterpret_cast<const float4*>(s)[threadIdx.x + 256 * k];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          reinterpret_cast<float4*>(d)[threadIdx.x + 256 * k] = make_float4(a[k].x + b[k].x, a[k].y + b[k].y, a[k].z + b[k].z, a[k].w + b[k].w);
+      } else {
+        for (int i = threadIdx.x; i < n4; i += 256) {
+          const float4 a = reinterpret_cast<const float4*>(d)[i], b = reinterpret_cast<const float4*>(s)[i];
+          reinterpret_cast<float4*>(d)[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+        }
+        for (int i = n4 * 4 + threadIdx.x; i < n; i += 256) d[i] += s[i];
+      }
+    } else {
+      for (int i = threadIdx.x; i < n; i += 256) d[i] += s[i];
+    }
+  }
+}
+
 // ---- layout: NHWC -> NCHW copy (reconstructions handed back to NCHW callers) ---------------------------
 __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int C, int HW) {
   const int64_t total = (int64_t)N * C * HW;
@@ -780,6 +833,47 @@ int odvae_adam_step_f32(float* p, const float* g, float* m, float* v, int64_t n,
   const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   hipLaunchKernelGGL(adam_kernel, dim3(grid_1d(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, n, lr, beta1, beta2, eps, bc1, bc2_sqrt, clip);
   ODVAE_LAUNCH_CHECK("adam_step");
+  return ODVAE_OK;
+}
+
+int odvae_grad_accumulate_segments_per_launch(void) { return kGradAccSegs; }
+
+// arena[dst_off[i] + j] += src[i][j] for count disjoint segments (dst_off / numel: host arrays, src: host array of device pointers);
+// ceil(count / K) launches, K = odvae_grad_accumulate_segments_per_launch(); nothing is launched unless every segment is valid
+int odvae_grad_accumulate_f32(float* arena, int64_t arena_numel, const int64_t* dst_off, const float* const* src, const int64_t* numel,
+                              int count, void* stream) {
+  ODVAE_CHECK_ARG(count >= 0, "grad_accumulate: count %d < 0", count);
+  if (count == 0) return ODVAE_OK;
+  ODVAE_CHECK_ARG(arena && arena_numel > 0 && dst_off && src && numel, "grad_accumulate: null arena / table");
+  for (int i = 0; i < count; ++i) {
+    ODVAE_CHECK_ARG(src[i] != nullptr, "grad_accumulate: segment %d has a null source", i);
+    ODVAE_CHECK_ARG(numel[i] > 0, "grad_accumulate: segment %d has numel %lld", i, (long long)numel[i]);
+    ODVAE_CHECK_ARG(dst_off[i] >= 0 && dst_off[i] <= arena_numel && numel[i] <= arena_numel - dst_off[i],
+                    "grad_accumulate: segment %d [%lld, +%lld) leaves the arena of %lld floats", i, (long long)dst_off[i], (long long)numel[i],
+                    (long long)arena_numel);
+    ODVAE_CHECK_ARG(ceil_div64(numel[i], kGradAccChunk) <= 0x7fffffffll, "grad_accumulate: segment %d of %lld floats is too large", i, (long long)numel[i]);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  GradAccTable t;
+  int i = 0;
+  while (i < count) {
+    uint64_t chunks = 0;
+    int k = 0;
+    for (; k < kGradAccSegs && i < count; ++k, ++i) {
+      const uint64_t c = (uint64_t)ceil_div64(numel[i], kGradAccChunk);
+      if (k > 0 && chunks + c > 0x7fffffffull) break;      // (the prefix is 32-bit: a launch closes early; one segment alone always fits)
+      t.dst[k] = arena + dst_off[i];
+      t.src[k] = src[i];
+      t.numel[k] = numel[i];
+      t.chunk_prefix[k] = (unsigned)chunks;
+      chunks += c;
+    }
+    for (int j = k; j <= kGradAccSegs; ++j) t.chunk_prefix[j] = (unsigned)chunks;
+    for (int j = k; j < kGradAccSegs; ++j) { t.dst[j] = nullptr; t.src[j] = nullptr; t.numel[j] = 0; }
+    t.count = k;
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)std::min<uint64_t>(chunks, 8192)), dim3(256), 0, st, t);
+    ODVAE_LAUNCH_CHECK("grad_accumulate");
+  }
   return ODVAE_OK;
 }
 

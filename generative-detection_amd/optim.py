@@ -22,6 +22,9 @@ class FusedAdam(torch.optim.Optimizer):
         self._steps = 0
         self._clip = None       # device [norm, coef] written by clip_grad_norm_
         self._clip_armed = False
+        self._window = False    # True between begin_microbatch() and the next zero_grad() / step(): the arena holds running sums
+        self._acc_args = {}     # fresh-parameter tuple -> cached ctypes (dst_off, numel) arrays of the accumulate entry point
+        self.accumulate_calls = 0   # calls of odvae_grad_accumulate_f32 so far (one launch each; host counter, tests read it)
 
     # ---- arenas -------------------------------------------------------------------------------------------------
     def _params(self):
@@ -75,12 +78,17 @@ class FusedAdam(torch.optim.Optimizer):
         f = self.materialize()
         return [(p, o, p.numel()) for p, o in zip(f["params"], f["offsets"])]
 
-    def gather_grads(self, indices=None):
+    def gather_grads(self, indices=None, accumulate=False):
         """Bring the gradients of parameters `indices` (default: all) into the arena and re-point `.grad` at their arena views.
         After `zero_grad(set_to_none=True)` autograd hands each parameter the tensor the weight-gradient kernel produced (no
         accumulate kernel per parameter); those tensors are copied into the arena by ONE multi-tensor copy here, slices of
         parameters the backward did not reach are zeroed (the norm kernel reads the whole arena).  Gradients that already live
-        in the arena are left alone."""
+        in the arena are left alone.
+        accumulate=True (a later micro-batch of a gradient-accumulation window, after `begin_microbatch`): the fresh tensors are ADDED to
+        their arena slices by one multi-tensor launch per K of them (odvae_grad_accumulate_f32) instead of copied; a parameter this
+        backward did not reach (`.grad is None`) is left alone -- its slice keeps the running sum."""
+        if accumulate:
+            return self._accumulate_grads(indices)
         f = self._flat
         views, ptrs, params = f["gviews"], f["gptrs"], f["params"]      # cached: this loop runs once per step on the host
         dst, src, zero = [], [], []
@@ -100,7 +108,70 @@ class FusedAdam(torch.optim.Optimizer):
             if zero:
                 torch._foreach_zero_(zero)
 
+    def _accumulate_grads(self, indices):
+        import ctypes
+        f = self._flat
+        views, ptrs, params = f["gviews"], f["gptrs"], f["params"]
+        fresh, src = [], []
+        for i in (range(len(params)) if indices is None else indices):
+            g = params[i].grad
+            if g is not None and g.data_ptr() != ptrs[i]:
+                if g.dtype != torch.float32 or g.device != views[i].device or g.numel() != views[i].numel():
+                    raise ValueError("FusedAdam: gradient of parameter %d is %s %s on %s, expected %d float32 on %s"
+                                     % (i, tuple(g.shape), g.dtype, g.device, views[i].numel(), views[i].device))
+                fresh.append(i)
+                src.append(g if g.is_contiguous() else g.contiguous())
+        if not fresh:
+            return
+        L = _lib.load()
+        K = int(L.odvae_grad_accumulate_segments_per_launch())
+        key = tuple(fresh)
+        args = self._acc_args.get(key)
+        if args is None:       # offsets and sizes never change; only the source pointers do
+            if len(self._acc_args) >= 64:
+                self._acc_args.clear()
+            args = self._acc_args[key] = [((ctypes.c_int64 * len(c))(*[f["offsets"][i] for i in c]),
+                                           (ctypes.c_int64 * len(c))(*[params[i].numel() for i in c]),
+                                           4.0 * sum(params[i].numel() for i in c))
+                                          for c in (key[a:a + K] for a in range(0, len(key), K))]
+        from . import ops
+        arena, total, stream = f["g"].data_ptr(), f["total"], _lib.stream_ptr()
+        a = 0
+        for dst_off, numel, nbytes in args:
+            n = len(dst_off)
+            srcs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in src[a:a + n]])
+            tag = ops.KERNEL_EVENTS.begin(secondary=True)
+            _lib.check(L.odvae_grad_accumulate_f32(arena, total, dst_off, srcs, numel, n, stream), "grad_accumulate")
+            ops.KERNEL_EVENTS.end("grad_accumulate", 0.0, tag, 3.0 * nbytes, issued=0.0)
+            self.accumulate_calls += 1
+            a += n
+        for i in fresh:     # (the sources go back to the caching allocator here: stream-ordered, the launches above are already queued)
+            params[i].grad = views[i]
+
+    def begin_microbatch(self):
+        """Open a later micro-batch of a gradient-accumulation window: every `.grad` is dropped, the arena (the running sums) is left
+        untouched, so the next backward again hands over the weight-gradient kernels' outputs instead of accumulating in place
+        parameter by parameter; `gather_grads(accumulate=True)` then adds them to the arena.  `zero_grad` opens a new window."""
+        f = self.materialize()
+        for p in f["params"]:
+            p.grad = None
+        self._window = True
+
+    def discard_window(self):
+        """Forget an accumulation window that will not be stepped (the trainer's AnomalyError path)."""
+        self._touched.clear()
+        self._window = False
+        self._clip_armed = False
+
     def _ensure_grad_views(self):
+        if self._window:
+            # a window's arena holds sums: anything still fresh is added, never copied over them, and the slices of parameters that
+            # an earlier micro-batch reached (but the last one did not) are re-attached as they are, not zeroed
+            self._accumulate_grads(None)
+            f = self._flat
+            for i in self._touched:
+                if f["params"][i].grad is None:
+                    f["params"][i].grad = f["gviews"][i]
         self.gather_grads()
 
     def zero_grad(self, set_to_none=False):
@@ -108,6 +179,7 @@ class FusedAdam(torch.optim.Optimizer):
         uses): `.grad` is dropped, the next backward's gradients are gathered into the arena by `gather_grads`."""
         if self._flat is None:
             return super().zero_grad(set_to_none=set_to_none)
+        self._window = False
         if set_to_none:
             for p in self._flat["params"]:
                 p.grad = None
@@ -161,6 +233,7 @@ class FusedAdam(torch.optim.Optimizer):
                                              float(g0["eps"]), count, clip, _lib.stream_ptr()), "adam_step")
         self._touched.clear()
         self._clip_armed = False
+        self._window = False
         from . import ops
         ops.PACK_CACHE.bump()   # parameters changed under torch's version counters: conv weight packs are stale
         return loss

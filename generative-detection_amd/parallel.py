@@ -83,6 +83,8 @@ class GradReducer:
         self._works = []
         self._launched = set()
         self._touched_buckets = set()
+        self._window_touched = set()     # buckets any backward since the last window start reached (gradient accumulation)
+        self._sync, self._accumulate = True, False
         self.launch_order = []   # bucket ids in the order their collectives were issued (tests look at this)
         # record_timeline = True (a diagnostic, off by default): one event on the compute stream when the backward starts, one per bucket at the
         # moment its collective is issued (= its last gradient's kernel is queued), one when finish() returns -- `timeline()` turns them into
@@ -93,9 +95,18 @@ class GradReducer:
             p.register_post_accumulate_grad_hook(lambda _p, i=i: self._on_grad(i))
 
     # ---- per-backward state ---------------------------------------------------------------------------------------
-    def prepare_for_backward(self):
+    def prepare_for_backward(self, first=True, sync=True):
+        """Before every backward.  The defaults are the plain step: one backward, exchanged.  Inside a gradient-accumulation window
+        (Trainer(accumulate_grad_batches=N)): `first` = this is the window's first micro-batch (the running sums start over), `sync=False` = a
+        non-final micro-batch, DDP's `no_sync` -- the hooks still note which buckets the backward reached, no collective is issued and `finish()`
+        only closes the backward.  The final micro-batch (`sync=True`) exchanges the accumulated local sums of every bucket touched anywhere
+        in the window; with `first=False` FusedAdam's fresh gradients are added to its arena (`gather_grads(accumulate=True)`) instead of copied."""
+        self._sync, self._accumulate = bool(sync), not first
+        if first:
+            self._window_touched = set()
         if self.own_arena:
-            self.arena.zero_()
+            if first:       # later micro-batches: `.grad` still is the arena view, autograd accumulates in place
+                self.arena.zero_()
             for p, off, n in self.slices:
                 view = self.arena[off:off + n].view(p.shape)
                 if p.grad is None or p.grad.data_ptr() != view.data_ptr():
@@ -128,6 +139,9 @@ class GradReducer:
         if self._pending is None:
             return  # backward outside a prepare/finish window (e.g. torch.autograd.grad probes)
         b = self.param_bucket[i]
+        self._window_touched.add(b)
+        if not self._sync:
+            return
         self._touched_buckets.add(b)
         self._pending[b] -= 1
         if self._pending[b] == 0:
@@ -136,7 +150,7 @@ class GradReducer:
     def _launch(self, b):
         s, e = self.buckets[b]
         if not self.own_arena:
-            self.optimizer.gather_grads(self.bucket_members[b])
+            self.optimizer.gather_grads(self.bucket_members[b], accumulate=self._accumulate)
         self._launched.add(b)
         self.launch_order.append(b)
         if self._tl is not None and self.record_timeline:
@@ -197,8 +211,12 @@ class GradReducer:
     def finish(self):
         """Issue the collectives of buckets that only some of their parameters reached (same set on every rank,
         since control flow depends on global_step only) and wait for all.  The mean comes for free when the loss was
-        pre-scaled by 1/world (`prescaled`); otherwise the reduced buckets are averaged here."""
-        for b in sorted(self._touched_buckets - self._launched, reverse=True):
+        pre-scaled by 1/world (`prescaled`); otherwise the reduced buckets are averaged here.  At the end of an accumulation window that
+        covers the buckets an earlier micro-batch reached and the last one did not; after a `sync=False` backward nothing is exchanged."""
+        if not self._sync:
+            self._pending = None
+            return
+        for b in sorted((self._touched_buckets | self._window_touched) - self._launched, reverse=True):
             self._launch(b)
         if self.f32_accumulate:
             self._second_halves()

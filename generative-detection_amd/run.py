@@ -39,10 +39,14 @@ def parse(argv):
 
 
 def trainer_kwargs(trainer_cfg):
-    """The `lightning.trainer` keys of the yaml this Trainer honours: gradient_clip_val, precision and detect_anomaly (yaml:138; absent
-    = None, which leaves the choice to ODVAE_DETECT_ANOMALY)."""
-    return {"gradient_clip_val": trainer_cfg.get("gradient_clip_val", None), "precision": trainer_cfg.get("precision", None),
-            "detect_anomaly": trainer_cfg.get("detect_anomaly", None)}
+    """The `lightning.trainer` keys of the yaml this Trainer honours: gradient_clip_val, precision, detect_anomaly (yaml:138; absent
+    = None, which leaves the choice to ODVAE_DETECT_ANOMALY) and accumulate_grad_batches (yaml:134; passed on only when it is not 1)."""
+    kw = {"gradient_clip_val": trainer_cfg.get("gradient_clip_val", None), "precision": trainer_cfg.get("precision", None),
+          "detect_anomaly": trainer_cfg.get("detect_anomaly", None)}
+    accumulate = trainer_cfg.get("accumulate_grad_batches", 1)
+    if accumulate != 1:      # (yaml:134; configure_learning_rate already multiplies the learning rate by it)
+        kw["accumulate_grad_batches"] = accumulate
+    return kw
 
 
 def main(argv=None):
@@ -74,7 +78,7 @@ def main(argv=None):
     bs = config.data.params.batch_size
     for step in range(opt.steps):
         batch = synthetic.make_batch(bs, opt.height, seed=opt.seed + step)
-        losses = trainer.training_batch(batch, step)
+        losses = trainer.training_batch(batch, step, last_in_epoch=step == opt.steps - 1)   # (closes an accumulation window)
         print("batch %d  global_step %d  aeloss %.4f  discloss %.4f  lr %.2e" %
               (step, model.global_step, losses[0].item(), losses[1].item(), model.learning_rate), flush=True)
     return model

@@ -3,6 +3,7 @@
 Per batch, for optimizer_idx in (0, 1): toggle_optimizer -> training_step -> zero_grad -> backward (DDP buckets fire)
 -> clip_grad_norm_(gradient_clip_val) -> optimizer.step -> untoggle; global_step advances once per optimizer step,
 i.e. by 2 per batch (every `global_step` threshold in the model and the loss depends on that).
+`accumulate_grad_batches = N` stretches zero_grad ... step over a window of N batches (backward of loss / N each, no exchange before the last).
 `fit` takes any iterable of batch dicts; `validate` drives `validation_step` (src/models/autoencoder.py:332-363) over a loader with
 the epoch mean and the `sync_dist` rank mean of `val/rec_loss`; `save_checkpoint` / `load_checkpoint` write and read the
 Lightning-1.9 checkpoint layout the reference's `ModelCheckpoint` produces (train.py:228-249), so a run of this trainer resumes
@@ -31,7 +32,7 @@ class _TrainerHandle:
 class Trainer:
     def __init__(self, model, gradient_clip_val=None, optimizer_indices=(0, 1), process_group=None, bucket_mb=None, precision=None,
                  distributed=None, comm_dtype=None, callbacks=(), logger=None, comm_f32_accumulate=False,
-                 detect_anomaly=None):
+                 detect_anomaly=None, accumulate_grad_batches=1):
         """optimizer_indices: which of the model's optimizers run each batch; (0,) is the "rec+KL only" benchmark
         configuration (discriminator off, optimizer 1 skipped -- SURVEY.md 8(d)).
         comm_dtype: dtype of the gradient buckets on the wire; None = f32 in every precision -- what the reference's `strategy: ddp`
@@ -44,7 +45,15 @@ class Trainer:
         detect_anomaly: lightning.trainer.detect_anomaly of the yaml (:138).  False = off; True or "nan" = torch's anomaly mode semantics
         (the first backward node that returns a NaN output raises AnomalyError before clipping and the optimizer step); "nonfinite" also
         flags +-Inf; None reads ODVAE_DETECT_ANOMALY (unset / 0 = off, 1 = nan, nonfinite).  The checks run on the device
-        (anomaly.py): one host wait per optimizer step."""
+        (anomaly.py): one host wait per optimizer step.
+        accumulate_grad_batches: lightning.trainer.accumulate_grad_batches of the yaml (:134), PL-1.9 automatic optimisation: N consecutive
+        batches form a window; every batch back-propagates loss / N into gradients that are zeroed only before the window's first backward; clip,
+        optimizer.step() and the global_step increment happen on the window's last batch only.  1 = a step after
+        every batch."""
+        if isinstance(accumulate_grad_batches, bool) or not isinstance(accumulate_grad_batches, int) or accumulate_grad_batches < 1:
+            raise ValueError("accumulate_grad_batches must be an integer >= 1, got %r" % (accumulate_grad_batches,))
+        self.accumulate_grad_batches = accumulate_grad_batches
+        self._window_pos = 0              # micro-batches already in the open accumulation window (0 = closed)
         self.model = model
         # callbacks: objects with the pytorch_lightning.Callback hooks used by the reference's yaml (callbacks.ImageLogger, ...);
         # `on_train_batch_end` runs after the last optimizer step of a batch, as under PL's automatic optimisation.  logger: anything
@@ -104,45 +113,80 @@ class Trainer:
         for p, rg in saved.values():
             p.requires_grad = rg
 
-    def training_batch(self, batch, batch_idx=0):
-        """One batch = one step of each scheduled optimizer.  Returns the list of loss tensors (device, not synced)."""
+    @property
+    def accumulation_index(self):
+        """Micro-batches in the open gradient-accumulation window; 0 when no window is open."""
+        return self._window_pos
+
+    def _discard_window(self):
+        self._window_pos = 0
+        for o in self.optimizers:
+            if hasattr(o, "discard_window"):
+                o.discard_window()
+
+    def training_batch(self, batch, batch_idx=0, last_in_epoch=False):
+        """One batch = one step of each scheduled optimizer.  Returns the list of loss tensors (device, not synced).
+        With accumulate_grad_batches = N > 1 one batch is one micro-batch of a window: each scheduled optimizer still gets its toggle,
+        training_step and backward (of loss / N), but it is stepped -- clip, step, global_step + 1 -- only on the window's last batch, the N-th
+        or the one flagged `last_in_epoch` (the divisor stays N).  The returned losses are unscaled."""
         model = self.model
         losses = []
-        for idx in self.optimizer_indices:
-            opt = self.optimizers[idx]
-            saved = self._toggle(idx)
-            an = self.anomaly
-            try:
-                if an is not None:
-                    an.begin(_device_of(model))      # before training_step: PoseLoss's torch.autograd.grad passes are checked too
-                loss = model.training_step(batch, batch_idx, idx)
-                opt.zero_grad(set_to_none=True)   # FusedAdam: gradients are gathered into its arena after the backward (optim.gather_grads)
-                red = self.reducers[idx] if self.reducers else None
-                if red is not None:
-                    red.prepare_for_backward()
-                    root = loss * red.inv_world         # sum over ranks of grad(loss / world) = DDP's mean gradient
+        n_acc = self.accumulate_grad_batches
+        first = self._window_pos == 0
+        final = self._window_pos + 1 >= n_acc or bool(last_in_epoch)
+        try:
+            for idx in self.optimizer_indices:
+                opt = self.optimizers[idx]
+                saved = self._toggle(idx)
+                an = self.anomaly
+                try:
                     if an is not None:
-                        an.watch(root)
-                    root.backward()
-                    red.finish()
-                else:
-                    if an is not None:
-                        an.watch(loss)
-                    loss.backward()
-                if an is not None:
-                    self._check_anomaly(an, idx, red)
-                if self.clip:
-                    if hasattr(opt, "clip_grad_norm_"):
-                        opt.clip_grad_norm_(self.clip)
+                        an.begin(_device_of(model))      # before training_step: PoseLoss's torch.autograd.grad passes are checked too
+                    loss = model.training_step(batch, batch_idx, idx)
+                    if first:
+                        opt.zero_grad(set_to_none=True)   # FusedAdam: gradients are gathered into its arena after the backward (optim.gather_grads)
+                    elif hasattr(opt, "begin_microbatch"):
+                        opt.begin_microbatch()            # FusedAdam: the arena keeps the sums, the backward hands over fresh kernel outputs again
+                    root = loss if n_acc == 1 else loss / n_acc
+                    red = self.reducers[idx] if self.reducers else None
+                    if red is not None:
+                        if n_acc == 1:
+                            red.prepare_for_backward()
+                        else:                             # DDP no_sync until the window's last backward, which exchanges the accumulated sums
+                            red.prepare_for_backward(first=first, sync=final)
+                        root = root * red.inv_world       # sum over ranks of grad(loss / world) = DDP's mean gradient
+                        if an is not None:
+                            an.watch(root)
+                        root.backward()
+                        red.finish()
                     else:
-                        torch.nn.utils.clip_grad_norm_([p for g in opt.param_groups for p in g["params"]], self.clip)
-                opt.step()
-            finally:
-                self._untoggle(saved)
-                if an is not None:
-                    an.end()
-            model._global_step += 1
-            losses.append(loss.detach())
+                        if an is not None:
+                            an.watch(root)
+                        root.backward()
+                    if an is not None:
+                        self._check_anomaly(an, idx, red)
+                    if final:
+                        # (FusedAdam inside a window: clip_grad_norm_ / step add whatever this backward left fresh to the arena's sums first)
+                        if self.clip:
+                            if hasattr(opt, "clip_grad_norm_"):
+                                opt.clip_grad_norm_(self.clip)
+                            else:
+                                torch.nn.utils.clip_grad_norm_([p for g in opt.param_groups for p in g["params"]], self.clip)
+                        opt.step()
+                    elif hasattr(opt, "gather_grads"):
+                        opt.gather_grads(accumulate=not first)   # one multi-tensor copy (window start) or add (later) into the arena
+                finally:
+                    self._untoggle(saved)
+                    if an is not None:
+                        an.end()
+                if final:
+                    model._global_step += 1
+                losses.append(loss.detach())
+        except AnomalyError:
+            if n_acc > 1:
+                self._discard_window()    # the next batch starts a new window
+            raise
+        self._window_pos = 0 if final else self._window_pos + 1
         for cb in self.callbacks:
             cb.on_train_batch_end(self, model, losses, batch, batch_idx)
         return losses
@@ -210,10 +254,19 @@ class Trainer:
         out = []
         for _ in range(max_epochs):
             self.model.train()
-            for i, batch in enumerate(batches):
-                if max_batches is not None and i >= max_batches:
-                    break
-                out.append(self.training_batch(batch, i))
+            if self.accumulate_grad_batches == 1:
+                for i, batch in enumerate(batches):
+                    if max_batches is not None and i >= max_batches:
+                        break
+                    out.append(self.training_batch(batch, i))
+            else:       # one batch of look-ahead: the epoch's last batch (or the `max_batches` cut) closes the accumulation window
+                it, end = iter(batches), object()
+                nxt, i = next(it, end), 0
+                while nxt is not end and (max_batches is None or i < max_batches):
+                    batch, nxt = nxt, next(it, end)
+                    last = nxt is end or (max_batches is not None and i + 1 >= max_batches)
+                    out.append(self.training_batch(batch, i, last_in_epoch=last))
+                    i += 1
             if val_batches is not None:
                 self.validate(val_batches)
             self._set_epoch(self.current_epoch + 1)
@@ -280,7 +333,9 @@ class Trainer:
         torch.optim.Adam's layout (optim.FusedAdam writes exactly that), lr_schedulers is empty (configure_optimizers returns none,
         autoencoder.py:377).  `state_dict` keys / shapes / dtypes are the reference module tree's (OIHW f32); every
         tensor is copied to the host.  No "loops" entry: PL-1.9 then restores `global_step` and `epoch` from the top-level keys (its
-        path for pre-1.6 checkpoints) instead of from a progress-tracker tree this trainer does not keep."""
+        path for pre-1.6 checkpoints) instead of from a progress-tracker tree this trainer does not keep.
+        RuntimeError inside an open gradient-accumulation window: the layout carries no gradients, the window's sums would be lost silently."""
+        self._no_open_window("dump_checkpoint")
         model = self.model
         ckpt = {"epoch": self.current_epoch, "global_step": int(model.global_step), "pytorch-lightning_version": "1.9.0",
                 "state_dict": {k: v.detach().to("cpu", copy=True) for k, v in model.state_dict().items()}}
@@ -302,8 +357,14 @@ class Trainer:
                     ckpt["callbacks"][getattr(cb, "state_key", type(cb).__qualname__)] = sd()
         return ckpt
 
+    def _no_open_window(self, what):
+        if self._window_pos:
+            raise RuntimeError("%s inside an open gradient-accumulation window (%d of %d micro-batches): a Lightning checkpoint carries no "
+                               "gradients; finish the window first" % (what, self._window_pos, self.accumulate_grad_batches))
+
     def save_checkpoint(self, path, weights_only=False):
         """Rank 0 writes `path` (atomically: temporary file + rename); every rank returns the path."""
+        self._no_open_window("save_checkpoint")
         self.check_device_health("writing %s" % os.path.basename(path))      # never a checkpoint of weights stepped with wrong gradients
         if _rank() == 0:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -328,6 +389,8 @@ class Trainer:
                     "checkpoint with hyper_parameters / callback state -- call load_checkpoint(path, trusted=True)." % (path, str(e).splitlines()[0])) from e
             ckpt = torch.load(path, map_location="cpu", weights_only=False)
         res = self.model.load_state_dict(ckpt["state_dict"], strict=strict)
+        if self._window_pos:
+            self._discard_window()      # a resume starts at a window boundary
         from . import ops
         ops.PACK_CACHE.bump()           # load_state_dict copies into .data of the arena views: no version bump the pack cache could see
         self.model._global_step = int(ckpt.get("global_step", 0))

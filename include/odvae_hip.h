@@ -307,6 +307,13 @@ int odvae_grad_norm_f32(const float* g, int64_t n, float max_norm, float* out, v
 /* torch.optim.Adam step (src/models/autoencoder.py:365-377) over flat arenas; clip = odvae_grad_norm_f32 output or NULL */
 int odvae_adam_step_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                         float eps, int step, const float* clip, void* stream);
+/* Gradient accumulation (lightning.trainer.accumulate_grad_batches): arena[dst_off[i] + j] += src[i][j], j < numel[i], for `count` disjoint
+ * segments in ceil(count / K) launches, K = odvae_grad_accumulate_segments_per_launch().  dst_off / numel are host arrays, src a host array
+ * of device pointers; the table travels in the kernel arguments (no copy, no allocation, no host wait).  One f32 rounding per element, no
+ * atomics; NaN / Inf propagate.  Every segment is validated before the first launch; count == 0 is a no-op. */
+int odvae_grad_accumulate_segments_per_launch(void);
+int odvae_grad_accumulate_f32(float* arena, int64_t arena_numel, const int64_t* dst_off, const float* const* src, const int64_t* numel,
+                              int count, void* stream);
 int odvae_nhwc_to_nchw_f32(const float* x, float* y, int N, int C, int HW, void* stream);
 /* y = x * mask[n][hw] broadcast over channels (inputs*mask_2d_bbox, contperceptual.py:252-255); x,y [npix][C] */
 int odvae_mul_mask_f32(const float* x, const float* mask, float* y, int64_t npix, int C, void* stream);
