@@ -217,6 +217,137 @@ __global__ __launch_bounds__(256) void lrelu_bwd_kernel(const float* __restrict_
 
 int stat_blocks(int64_t rows) { return (int)std::min<int64_t>(std::max<int64_t>(rows / 128, 1), 1024); }
 
+// ---- ActNorm + LeakyReLU ([UPSTREAM] taming/modules/util.py ActNorm, NLayerDiscriminator(use_actnorm=True)) -----------------------
+// h = scale[c] * (x + loc[c]), y = lrelu(h).  loc and scale are parameters: nothing is reduced in the forward, and in the backward dx
+// does not depend on the parameter sums, so the activations are read once (BatchNorm in training mode: 3 tensor passes forward, 5
+// backward; here 2 and 3).  V = 4: 16-byte accesses (C % 4 == 0 and 16-byte aligned pointers, every real layer); V = 1: scalar.
+template <int V> struct an_vec;
+template <> struct an_vec<1> { typedef float type; };
+template <> struct an_vec<4> { typedef f32x4 type; };
+template <int V> __device__ __forceinline__ void an_load(const float* p, float (&v)[V]) {
+  const typename an_vec<V>::type t = *reinterpret_cast<const typename an_vec<V>::type*>(p);
+  if constexpr (V == 1) v[0] = t; else { v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+}
+template <int V> __device__ __forceinline__ void an_store(float* p, const float (&v)[V]) {
+  typename an_vec<V>::type t;
+  if constexpr (V == 1) t = v[0]; else { t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3]; }
+  *reinterpret_cast<typename an_vec<V>::type*>(p) = t;
+}
+
+// BWD = 0: y = lrelu(scale * (x + loc)).  BWD = 1 (neither parameter needs a gradient): dx = scale * dy * lrelu'(scale * (x + loc)).
+// Both evaluate h by the same two f32 operations, so the backward sees the sign the forward saw.
+template <int V, int BWD>
+__global__ __launch_bounds__(256) void an_lrelu_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                       const float* __restrict__ loc, const float* __restrict__ scale, float slope,
+                                                       int64_t total_v, int CV, float* __restrict__ out) {
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total_v; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(idx % CV) * V;
+    float xv[V], lo[V], sc[V], dv[V], o[V];
+    an_load<V>(x + idx * V, xv); an_load<V>(loc + c, lo); an_load<V>(scale + c, sc);
+    if (BWD) an_load<V>(dy + idx * V, dv);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const float h = sc[j] * (xv[j] + lo[j]);
+      o[j] = BWD ? sc[j] * (dv[j] * (h > 0.f ? 1.f : slope)) : (h > 0.f ? h : slope * h);
+    }
+    an_store<V>(out + idx * V, o);
+  }
+}
+
+// One pass over x and dy: dx = scale * g, g = dy * lrelu'(h), and part[blk][2][C] = the block's sums of g and of g * (x + loc).
+// A thread keeps one channel (V = 4: four adjacent ones) and walks every `lanes`-th row of the block's row range, as bn_colstats_kernel.
+template <int V>
+__global__ __launch_bounds__(256) void an_lrelu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                           const float* __restrict__ loc, const float* __restrict__ scale, float slope,
+                                                           int64_t rows, int C, int rows_per_block, float* __restrict__ dx,
+                                                           float* __restrict__ part) {
+  __shared__ float sh[2][V][256];
+  const int CV = C / V;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = std::min<int64_t>(rows, r0 + rows_per_block);
+  for (int cbase = 0; cbase < CV; cbase += 256) {
+    const int cw = min(256, CV - cbase);
+    const int lanes = 256 / cw;
+    const int c = (cbase + threadIdx.x % cw) * V, rl = threadIdx.x / cw;
+    float a[V], b[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) a[j] = b[j] = 0.f;
+    if (rl < lanes) {
+      float lo[V], sc[V];
+      an_load<V>(loc + c, lo); an_load<V>(scale + c, sc);
+      for (int64_t r = r0 + rl; r < r1; r += lanes) {
+        float xv[V], dv[V], o[V];
+        an_load<V>(x + r * C + c, xv); an_load<V>(dy + r * C + c, dv);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          const float t = xv[j] + lo[j];
+          const float h = sc[j] * t;
+          const float g = dv[j] * (h > 0.f ? 1.f : slope);
+          a[j] += g; b[j] += g * t;
+          o[j] = sc[j] * g;
+        }
+        an_store<V>(dx + r * C + c, o);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) { sh[0][j][threadIdx.x] = a[j]; sh[1][j][threadIdx.x] = b[j]; }
+    __syncthreads();
+    if (threadIdx.x < cw) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        float ta = 0.f, tb = 0.f;
+        for (int k = 0; k < lanes; ++k) { ta += sh[0][j][k * cw + threadIdx.x]; tb += sh[1][j][k * cw + threadIdx.x]; }
+        part[((int64_t)blockIdx.x * 2 + 0) * C + (cbase + threadIdx.x) * V + j] = ta;
+        part[((int64_t)blockIdx.x * 2 + 1) * C + (cbase + threadIdx.x) * V + j] = tb;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// dloc = scale * sum g, dscale = sum g (x + loc): one wavefront per (which, channel), f64, fixed butterfly (as bn_sum_partials_kernel)
+__global__ void an_sum_partials_kernel(const float* __restrict__ part, const float* __restrict__ scale, int nblk, int C,
+                                       float* __restrict__ dloc, float* __restrict__ dscale) {
+  const int lane = threadIdx.x & 63;
+  const int idx = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (idx >= 2 * C) return;
+  const int which = idx / C, c = idx % C;
+  double a = 0.0;
+  for (int k = lane; k < nblk; k += 64) a += (double)part[((int64_t)k * 2 + which) * C + c];
+  a = wave_sum_f64(a);
+  if (lane != 0) return;
+  if (which == 0) dloc[c] = (float)((double)scale[c] * a); else dscale[c] = (float)a;
+}
+
+// data-dependent initialisation from the partials of bn_colstats_kernel<0> (sums of d and d^2 about the pivot x[0][c]):
+// loc = -mean, scale = 1 / (std + eps) with the unbiased (rows - 1) std, written into the parameters' own storage.
+// One wavefront per channel, f64, as bn_finalize_kernel.
+__global__ void an_init_finalize_kernel(const float* __restrict__ part, const float* __restrict__ x, int nblk, int C, int64_t rows, float eps,
+                                        float* __restrict__ loc, float* __restrict__ scale) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (c >= C) return;
+  double a = 0.0, b = 0.0;
+  for (int k = lane; k < nblk; k += 64) { a += (double)part[((int64_t)k * 2 + 0) * C + c]; b += (double)part[((int64_t)k * 2 + 1) * C + c]; }
+  a = wave_sum_f64(a); b = wave_sum_f64(b);
+  if (lane != 0) return;
+  const double m = (double)rows;
+  const double dm = a / m;
+  double var = (b - a * dm) / (m - 1.0);
+  if (var < 0.0) var = 0.0;
+  loc[c] = (float)(-((double)x[c] + dm));
+  scale[c] = (float)(1.0 / (sqrt(var) + (double)eps));
+}
+
+// blocks of the one-pass backward: ~16 rows per thread, at most 1024 blocks (the partials stay a few per cent of the tensor)
+int an_bwd_blocks(int64_t rows, int C, int V) {
+  const int lanes = 256 / std::min(C / V, 256);
+  return (int)std::min<int64_t>(std::max<int64_t>(rows / (16 * (int64_t)lanes), 1), 1024);
+}
+bool an_vec4(int C, const void* a, const void* b, const void* c, const void* d, const void* e) {
+  return C % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -288,6 +419,68 @@ int odvae_batchnorm_lrelu_bwd_f32(const float* x, const float* dy, int64_t rows,
   hipMemcpyAsync(dgamma, sums + C, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, st);
   hipLaunchKernelGGL(bn_lrelu_bwd_apply_kernel, dim3(grid_1d(rows * C)), dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, sums, slope, rows, C, train, dx);
   ODVAE_LAUNCH_CHECK("batchnorm_lrelu_bwd");
+  return ODVAE_OK;
+}
+
+// ---- ActNorm + LeakyReLU ------------------------------------------------------------------------------------------------------------
+size_t odvae_actnorm_workspace_bytes(int64_t rows, int C) {
+  const size_t init = (size_t)stat_blocks(rows) * 2 * C;
+  const size_t bwd = (size_t)std::max(an_bwd_blocks(rows, C, 1), C % 4 == 0 ? an_bwd_blocks(rows, C, 4) : 1) * 2 * C;
+  return std::max(init, bwd) * sizeof(float);
+}
+
+// loc[c] = -mean_c, scale[c] = 1 / (std_c + eps), std_c the unbiased standard deviation over the rows; both written on the device
+int odvae_actnorm_init_f32(const float* x, int64_t rows, int C, float eps, float* loc, float* scale,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(x && loc && scale && C > 0, "actnorm_init: bad arguments");
+  ODVAE_CHECK_ARG(rows >= 2, "actnorm_init: the unbiased standard deviation needs at least 2 rows (N*H*W), got %lld", (long long)rows);
+  const size_t need = odvae_actnorm_workspace_bytes(rows, C);
+  if (!workspace || workspace_bytes < need) { odvae_set_error("actnorm_init: needs %zu workspace bytes", need); return ODVAE_ERR_WORKSPACE; }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  const int nblk = stat_blocks(rows);
+  const int rpb = (int)ceil_div64(rows, nblk);
+  const int nb = (int)ceil_div64(rows, rpb);
+  hipLaunchKernelGGL((bn_colstats_kernel<0>), dim3(nb), dim3(256), 0, st, x, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, rows, C, rpb, part);
+  hipLaunchKernelGGL(an_init_finalize_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, x, nb, C, rows, eps, loc, scale);
+  ODVAE_LAUNCH_CHECK("actnorm_init");
+  return ODVAE_OK;
+}
+
+int odvae_actnorm_lrelu_fwd_f32(const float* x, int64_t rows, int C, const float* loc, const float* scale, float slope, float* y, void* stream) {
+  ODVAE_CHECK_ARG(x && loc && scale && y && rows > 0 && C > 0, "actnorm_lrelu_fwd: bad arguments");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (an_vec4(C, x, y, loc, scale, nullptr))
+    hipLaunchKernelGGL((an_lrelu_kernel<4, 0>), dim3(grid_1d(rows * C / 4, 2048)), dim3(256), 0, st, x, nullptr, loc, scale, slope, rows * C / 4, C / 4, y);
+  else
+    hipLaunchKernelGGL((an_lrelu_kernel<1, 0>), dim3(grid_1d(rows * C, 2048)), dim3(256), 0, st, x, nullptr, loc, scale, slope, rows * C, C, y);
+  ODVAE_LAUNCH_CHECK("actnorm_lrelu_fwd");
+  return ODVAE_OK;
+}
+
+// dloc == dscale == NULL: the dx-only form (no partials, no workspace)
+int odvae_actnorm_lrelu_bwd_f32(const float* x, const float* dy, int64_t rows, int C, const float* loc, const float* scale, float slope,
+                                float* dx, float* dloc, float* dscale, void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(x && dy && loc && scale && dx && rows > 0 && C > 0, "actnorm_lrelu_bwd: bad arguments");
+  ODVAE_CHECK_ARG((dloc == nullptr) == (dscale == nullptr), "actnorm_lrelu_bwd: dloc and dscale are given together or not at all");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool v4 = an_vec4(C, x, dy, dx, loc, scale);
+  if (!dloc) {
+    if (v4) hipLaunchKernelGGL((an_lrelu_kernel<4, 1>), dim3(grid_1d(rows * C / 4, 2048)), dim3(256), 0, st, x, dy, loc, scale, slope, rows * C / 4, C / 4, dx);
+    else hipLaunchKernelGGL((an_lrelu_kernel<1, 1>), dim3(grid_1d(rows * C, 2048)), dim3(256), 0, st, x, dy, loc, scale, slope, rows * C, C, dx);
+    ODVAE_LAUNCH_CHECK("actnorm_lrelu_bwd");
+    return ODVAE_OK;
+  }
+  const size_t need = odvae_actnorm_workspace_bytes(rows, C);
+  if (!workspace || workspace_bytes < need) { odvae_set_error("actnorm_lrelu_bwd: needs %zu workspace bytes", need); return ODVAE_ERR_WORKSPACE; }
+  float* part = static_cast<float*>(workspace);
+  const int nblk = an_bwd_blocks(rows, C, v4 ? 4 : 1);
+  const int rpb = (int)ceil_div64(rows, nblk);
+  const int nb = (int)ceil_div64(rows, rpb);
+  if (v4) hipLaunchKernelGGL((an_lrelu_bwd_kernel<4>), dim3(nb), dim3(256), 0, st, x, dy, loc, scale, slope, rows, C, rpb, dx, part);
+  else hipLaunchKernelGGL((an_lrelu_bwd_kernel<1>), dim3(nb), dim3(256), 0, st, x, dy, loc, scale, slope, rows, C, rpb, dx, part);
+  hipLaunchKernelGGL(an_sum_partials_kernel, dim3(ceil_div(2 * C, 4)), dim3(256), 0, st, part, scale, nb, C, dloc, dscale);
+  ODVAE_LAUNCH_CHECK("actnorm_lrelu_bwd");
   return ODVAE_OK;
 }
 

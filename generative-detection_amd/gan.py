@@ -4,6 +4,13 @@
   Conv(4x4,s2,p1)+LeakyReLU(0.2), two Conv(4x4,s2,p1,no bias)+BatchNorm2d+LeakyReLU, one Conv(4x4,s1,p1,no bias)+BN+
   LeakyReLU, Conv(4x4,s1,p1) -> logits [B,1,30,30] at 256x256 (src/modules/losses/contperceptual.py:285).
   state_dict keys main.{0,2,3,5,6,8,9,11} as in the reference checkpoint layout.
+* ActNormLReLU / NLayerDiscriminator(use_actnorm=True): [UPSTREAM] taming/modules/util.py ActNorm and the `use_actnorm` branch of the
+  same NLayerDiscriminator.  The taming sources are not at hand: this is the published algorithm restated (parity "unpinned",
+  DESIGN.md 5).  ActNorm(num_features, logdet=False, affine=True, allow_reverse_init=False): parameters loc (zeros) and scale (ones)
+  [1,C,1,1], uint8 buffer `initialized`; h = scale * (x + loc); on the first TRAINING forward, without a graph, loc = -mean_c and
+  scale = 1 / (std_c + 1e-6) with the unbiased std over N*H*W, `initialized` = 1, and that same forward already uses the new values; in
+  eval mode an uninitialised layer stays uninitialised.  ActNorm stands at main.{3,6,9}, the convolutions at main.{2,5,8} get a bias,
+  weights_init leaves loc / scale alone (it matches "Conv" and "BatchNorm").
 * LPIPSStyle: [UPSTREAM] taming/modules/losses/lpips.py structure (ScalingLayer, VGG16 feature slices relu1_2 ... relu5_3,
   channel-unit-normalise, squared difference, 1x1 "lin" heads, spatial mean, sum over the five taps).  The real LPIPS
   weights are downloads (torchvision VGG16 + vgg.pth) that do not exist offline, so the weights here are seeded
@@ -43,6 +50,58 @@ class BatchNormLReLU(nn.BatchNorm2d):
         return ops.batchnorm_lrelu(x, self, 0.2)
 
 
+class ActNormLReLU(nn.Module):
+    """[UPSTREAM] taming ActNorm (logdet=False, the discriminator's form) fused with the LeakyReLU(0.2) that follows it in the PatchGAN.
+    State under the upstream names and shapes: loc, scale [1,C,1,1], initialized (uint8 scalar).
+
+    Upstream reads `self.initialized.item()` on every forward: a device synchronisation per layer per call.  Here a host-side mirror of
+    the flag decides, so the steady-state forward never reads the buffer; the mirror is refreshed where the buffer can change behind it
+    (`_load_from_state_dict`, the data-parallel broadcast), one read each.
+
+    DELIBERATE DEVIATION: upstream initialises per rank and the replicas then keep different loc / scale for the whole
+    run.  When the Trainer has handed the layer a process group (`dist_group`), rank 0's values are broadcast right after initialising."""
+
+    EPS = 1e-6
+
+    def __init__(self, num_features, logdet=False, affine=True, allow_reverse_init=False):
+        assert affine
+        super().__init__()
+        if logdet or allow_reverse_init:
+            raise NotImplementedError("ActNorm logdet / reverse are not on the discriminator's path")
+        self.logdet = logdet
+        self.loc = nn.Parameter(torch.zeros(1, num_features, 1, 1))
+        self.scale = nn.Parameter(torch.ones(1, num_features, 1, 1))
+        self.register_buffer("initialized", torch.tensor(0, dtype=torch.uint8))
+        self._initialized_host = False
+        self.dist_group = None          # set by the Trainer in a data-parallel run
+
+    def refresh_initialized(self):
+        """Re-read the flag from the buffer (one device read): after anything that wrote the buffer behind the mirror."""
+        self._initialized_host = bool(int(self.initialized.item()))
+        return self._initialized_host
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        self.refresh_initialized()
+
+    def initialize(self, x):
+        """loc, scale from the statistics of `x`, on the device, without a graph and without a value coming back to the host"""
+        ops.actnorm_init(x, self.loc, self.scale, self.EPS)
+        with torch.no_grad():
+            self.initialized.fill_(1)
+        self._initialized_host = True
+        if self.dist_group is not None:
+            from .parallel import broadcast_actnorm
+            broadcast_actnorm([self], self.dist_group)
+
+    def forward(self, x, reverse=False):
+        if reverse:
+            raise NotImplementedError("ActNorm reverse is not on the discriminator's path")
+        if self.training and not self._initialized_host:
+            self.initialize(x)
+        return ops.actnorm_lrelu(x, self, 0.2)
+
+
 class LeakyReLU(nn.LeakyReLU):
     def forward(self, x):
         return ops.leaky_relu(x, self.negative_slope)
@@ -55,20 +114,27 @@ class _Fused(nn.Identity):
 class NLayerDiscriminator(nn.Module):
     def __init__(self, input_nc=3, ndf=64, n_layers=3, use_actnorm=False):
         super().__init__()
-        if use_actnorm:
-            raise NotImplementedError("ActNorm discriminator is not used by the OD-VAE configs")
+        # [UPSTREAM]: BatchNorm2d and bias-free convolutions in front of it, or ActNorm and use_bias=True
+        norm, use_bias = (ActNormLReLU, True) if use_actnorm else (BatchNormLReLU, False)
         seq = [Conv4x4(input_nc, ndf, 2, bias=True), LeakyReLU(0.2, True)]
         mult = 1
         for n in range(1, n_layers):
             prev, mult = mult, min(2 ** n, 8)
-            seq += [Conv4x4(ndf * prev, ndf * mult, 2, bias=False), BatchNormLReLU(ndf * mult), _Fused()]
+            seq += [Conv4x4(ndf * prev, ndf * mult, 2, bias=use_bias), norm(ndf * mult), _Fused()]
         prev, mult = mult, min(2 ** n_layers, 8)
-        seq += [Conv4x4(ndf * prev, ndf * mult, 1, bias=False), BatchNormLReLU(ndf * mult), _Fused()]
+        seq += [Conv4x4(ndf * prev, ndf * mult, 1, bias=use_bias), norm(ndf * mult), _Fused()]
         seq += [Conv4x4(ndf * mult, 1, 1, bias=True)]
         self.main = nn.Sequential(*seq)
 
     def forward(self, input):
         return self.main(input)
+
+    def actnorm_layers(self):
+        return [m for m in self.main if isinstance(m, ActNormLReLU)]
+
+    def actnorm_uninitialized(self):
+        """True while an ActNorm layer still waits for its first training forward (host-side flags only)"""
+        return any(not m._initialized_host for m in self.actnorm_layers())
 
 
 class _VggConv(nn.Conv2d):

@@ -104,6 +104,10 @@ PROTOTYPES = {
     "odvae_batchnorm_workspace_bytes": (_Z, [_L, _I]),
     "odvae_batchnorm_lrelu_fwd_f32": (_I, [_P, _L, _I, _P, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "odvae_batchnorm_lrelu_bwd_f32": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _Z, _P]),
+    "odvae_actnorm_workspace_bytes": (_Z, [_L, _I]),
+    "odvae_actnorm_init_f32": (_I, [_P, _L, _I, _F, _P, _P, _P, _Z, _P]),
+    "odvae_actnorm_lrelu_fwd_f32": (_I, [_P, _L, _I, _P, _P, _F, _P, _P]),
+    "odvae_actnorm_lrelu_bwd_f32": (_I, [_P, _P, _L, _I, _P, _P, _F, _P, _P, _P, _P, _Z, _P]),
     "odvae_leaky_relu_f32": (_I, [_P, _P, _F, _L, _P]),
     "odvae_leaky_relu_bwd_f32": (_I, [_P, _P, _P, _F, _L, _P]),
     "odvae_scaling_layer_f32": (_I, [_P, _P, _P, _P, _L, _I, _I, _P]),

@@ -77,8 +77,6 @@ class LPIPSWithDiscriminator(nn.Module):
                  disc_conditional=False, disc_loss="hinge"):
         super().__init__()
         assert disc_loss in ["hinge", "vanilla"]
-        if use_actnorm:
-            raise NotImplementedError("use_actnorm=True is not used by the OD-VAE configs")
         self.kl_weight = kl_weight
         self.pixel_weight = pixelloss_weight
         self.perceptual_loss = LPIPSStyle().eval()
@@ -353,12 +351,16 @@ class PoseLoss(LPIPSWithDiscriminator):
             if self.disc_factor > 0.0:
                 logits_fake = self.discriminator(ops.mul_mask(reconstructions, mask_2d_bbox))
                 g_loss = -torch.mean(logits_fake * bg4)
-            elif self.log_exact_g_loss:
+            elif self.log_exact_g_loss or (self.discriminator.training and self.discriminator.actnorm_uninitialized()):
                 # discriminator off: the reference still evaluates D(x_rec) (its BatchNorm running statistics move too) and
                 # multiplies the term by an exact 0 (:285-292,305).  The forward runs here without a graph, so the logged
                 # `g_loss` and the discriminator's buffers are the reference's; the all-zero backward through D is skipped.
+                # use_actnorm: the reference's ActNorm layers initialise from THIS tensor on the first training batch, so the
+                # forward also runs while any of them is uninitialised; afterwards the shortcut below applies again.
                 with torch.no_grad():
                     g_loss = -torch.mean(self.discriminator(ops.mul_mask(reconstructions.detach(), mask_2d_bbox)) * bg4)
+                if not self.log_exact_g_loss:     # the forward ran for the initialisation alone: the logged value stays the shortcut's 0
+                    g_loss = torch.zeros((), device=rgb_gt.device)
             else:
                 g_loss = torch.zeros((), device=rgb_gt.device)
             one_pass = None      # (g_nll, g_g) when the main backward is to start from the combined gradient at the reconstruction

@@ -1529,6 +1529,61 @@ def batchnorm_lrelu(x, bn, slope):
     return _BatchNormLReLU.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, slope, train)
 
 
+class _ActNormLReLU(Function):
+    @staticmethod
+    def forward(ctx, x, loc, scale, slope):
+        L = _L()
+        x = _cl(x)
+        _lib.require_device(loc, scale)
+        n, c, h, w = x.shape
+        y = _new_cl(n, c, h, w, x)
+        _lib.check(L.odvae_actnorm_lrelu_fwd_f32(x.data_ptr(), n * h * w, c, loc.detach().contiguous().data_ptr(),
+                                                 scale.detach().contiguous().data_ptr(), float(slope), y.data_ptr(), _lib.stream_ptr()),
+                   "actnorm_lrelu_fwd")
+        ctx.slope = float(slope)
+        ctx.save_for_backward(x, loc, scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        x, loc, scale = ctx.saved_tensors
+        dy = _cl(dy)
+        n, c, h, w = x.shape
+        rows = n * h * w
+        dx = _new_cl(n, c, h, w, x)
+        dloc = dscale = None
+        wp, wn = None, 0
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:   # neither: the dx-only kernel, no partial sums
+            dloc = torch.empty(1, c, 1, 1, dtype=torch.float32, device=x.device)
+            dscale = torch.empty(1, c, 1, 1, dtype=torch.float32, device=x.device)
+            wp, wn = _ws(L.odvae_actnorm_workspace_bytes(rows, c), x)
+        _lib.check(L.odvae_actnorm_lrelu_bwd_f32(x.data_ptr(), dy.data_ptr(), rows, c, loc.detach().contiguous().data_ptr(),
+                                                 scale.detach().contiguous().data_ptr(), ctx.slope, dx.data_ptr(), _lib.ptr(dloc),
+                                                 _lib.ptr(dscale), wp, wn, _lib.stream_ptr()), "actnorm_lrelu_bwd")
+        return dx, dloc, dscale, None
+
+
+def actnorm_init(x, loc, scale, eps=1e-6):
+    """ActNorm's data-dependent initialisation: loc = -mean_c(x), scale = 1 / (std_c(x) + eps), unbiased std over N*H*W, written into
+    the two parameters' storage on the device (no graph, nothing comes back to the host).  Needs N*H*W >= 2."""
+    L = _L()
+    x = _cl(x.detach())
+    _lib.require_device(loc, scale)
+    n, c, h, w = x.shape
+    if loc.numel() != c or scale.numel() != c or not (loc.is_contiguous() and scale.is_contiguous()):
+        raise ValueError("actnorm_init: loc / scale must be contiguous with %d elements" % c)
+    rows = n * h * w
+    wp, wn = _ws(L.odvae_actnorm_workspace_bytes(rows, c), x)
+    _lib.check(L.odvae_actnorm_init_f32(x.data_ptr(), rows, c, float(eps), loc.data_ptr(), scale.data_ptr(), wp, wn, _lib.stream_ptr()),
+               "actnorm_init")
+
+
+def actnorm_lrelu(x, an, slope):
+    """ActNorm `an` (holder of loc, scale [1,C,1,1]) + LeakyReLU(slope): lrelu(scale * (x + loc)); gradients dx, dloc, dscale."""
+    return _ActNormLReLU.apply(x, an.loc, an.scale, slope)
+
+
 class _LeakyReLU(Function):
     @staticmethod
     def forward(ctx, x, slope):

@@ -10,6 +10,7 @@ towards the encoder.  xGMI is point-to-point, so buckets are sized large (defaul
 
 Works with any backend: "nccl" (= RCCL on ROCm) on GPUs, "gloo" on CPU tensors for the tests.
 Not synchronised across ranks, as in the reference: BatchNorm statistics, _rescale min/max, RNG streams.
+Synchronised although the reference does not: ActNorm's data-dependent initialisation (`broadcast_actnorm`).
 """
 import torch
 import torch.distributed as dist
@@ -246,6 +247,20 @@ class GradReducer:
         # raw .data writes bump no version counter: conv weight packs cached from an earlier forward are stale now
         from . import ops
         ops.PACK_CACHE.bump()
+
+
+def broadcast_actnorm(modules, group=None):
+    """loc, scale and `initialized` of the given ActNorm layers from the group's rank 0 to every rank, then each layer's host-side mirror
+    of the flag is re-read.  DELIBERATE DEVIATION: upstream lets every rank initialise ActNorm from its own first batch and
+    never reconciles them.  No-op on one rank or without a process group."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return
+    src = 0 if group is None or group is dist.group.WORLD else dist.get_global_rank(group, 0)
+    with torch.no_grad():
+        for m in modules:
+            for t in (m.loc, m.scale, m.initialized):
+                dist.broadcast(t.data, src=src, group=group)
+            m.refresh_initialized()
 
 
 def all_reduce_mean(value, group=None):

@@ -92,6 +92,11 @@ class Trainer:
             self.reducers = [GradReducer(o, process_group=process_group, bucket_mb=bucket_mb, prescaled=True, comm_dtype=comm_dtype, f32_accumulate=comm_f32_accumulate)
                              for o in opts]
             self.reducers[0].broadcast_parameters(model)
+            # ActNorm layers initialise from data on their first training forward: rank 0's values then go to every rank (parallel.broadcast_actnorm)
+            for m in model.modules():
+                if hasattr(m, "dist_group") and hasattr(m, "refresh_initialized"):
+                    m.dist_group = process_group if process_group is not None else torch.distributed.group.WORLD
+                    m.refresh_initialized()
 
     # PL-1.9 toggle_optimizer: parameters owned by the *other* optimizers stop requiring grad; parameters in no
     # optimizer (loss.logvar, the frozen LPIPS net) are left alone

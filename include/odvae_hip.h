@@ -335,6 +335,15 @@ int odvae_batchnorm_lrelu_fwd_f32(const float* x, int64_t rows, int C, const flo
 int odvae_batchnorm_lrelu_bwd_f32(const float* x, const float* dy, int64_t rows, int C, const float* gamma, const float* beta,
                                   const float* mean, const float* rstd, float slope, int train,
                                   float* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+/* ActNorm ([UPSTREAM] taming ActNorm: h = scale[c] * (x + loc[c])) + LeakyReLU(slope), x [rows][C].
+ * init: loc = -mean_c, scale = 1 / (std_c + eps), std_c the unbiased standard deviation over the rows (rows >= 2), written on the device.
+ * bwd: dx = scale * g, dloc = scale * sum g, dscale = sum g (x + loc), g = dy * lrelu'(h); dloc = dscale = NULL: dx only, no workspace. */
+size_t odvae_actnorm_workspace_bytes(int64_t rows, int C);
+int odvae_actnorm_init_f32(const float* x, int64_t rows, int C, float eps, float* loc, float* scale,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int odvae_actnorm_lrelu_fwd_f32(const float* x, int64_t rows, int C, const float* loc, const float* scale, float slope, float* y, void* stream);
+int odvae_actnorm_lrelu_bwd_f32(const float* x, const float* dy, int64_t rows, int C, const float* loc, const float* scale, float slope,
+                                float* dx, float* dloc, float* dscale, void* workspace, size_t workspace_bytes, void* stream);
 /* torch.nn.LeakyReLU(slope); the backward with slope 0 is the ReLU backward */
 int odvae_leaky_relu_f32(const float* x, float* y, float slope, int64_t n, void* stream);
 int odvae_leaky_relu_bwd_f32(const float* x, const float* dy, float* dx, float slope, int64_t n, void* stream);
