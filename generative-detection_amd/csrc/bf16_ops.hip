@@ -351,6 +351,19 @@ __global__ void sumpool2x2_bf16_kernel(const bf16_t* __restrict__ du, bf16_t* __
     *reinterpret_cast<u32x4*>(dx + 8 * i) = pack8(a);
   }
 }
+// ---- conv-less resamplers on bf16 activations: f32 arithmetic, one rounding on the way out; the statistics are those of the rounded values ----
+struct RsBF16 {
+  typedef bf16_t elem_t;
+  static constexpr int W = 8;
+  static __device__ __forceinline__ void load(const bf16_t* p, float (&f)[8]) { unpack8(ldnt(reinterpret_cast<const u32x4*>(p)), f); }
+  static __device__ __forceinline__ void store(bf16_t* p, float (&f)[8]) {
+    const u32x4 v = pack8(f);
+    stnt(reinterpret_cast<u32x4*>(p), v);
+    unpack8(v, f);
+  }
+};
+#include "resample.h"
+
 // partial[block][C] column sums of a [rows][C] bf16 matrix; second kernel adds the blocks in order
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restrict__ x, int64_t rows, int C, int rows_per_block, float* __restrict__ partial) {
   __shared__ float red[256 * 8];
@@ -520,6 +533,20 @@ int odvae_upsample2x_bwd_bf16(const void* du, void* dx, int N, int H, int W, int
                      static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(du), static_cast<bf16_t*>(dx), N, H, W, C);
   ODVAE_LAUNCH_CHECK("upsample2x_bwd_bf16");
   return ODVAE_OK;
+}
+
+// The bf16 forms of odvae_avgpool2x2_f32 / _bwd_f32 / odvae_upsample2x_f32 (C % 8 == 0): f32 arithmetic, one rounding on the way out;
+// gn_partial holds the statistics of the bf16-rounded values, as odvae_conv_bf16_stats leaves them
+int odvae_avgpool2x2_bf16(const void* x, void* y, int N, int H, int W, int C, float* gn_partial, int gn_groups, int chunks, void* stream) {
+  return rs_avgpool<RsBF16>(x, y, N, H, W, C, gn_partial, gn_groups, chunks, stream);
+}
+
+int odvae_avgpool2x2_bwd_bf16(const void* dy, void* dx, int N, int H, int W, int C, void* stream) {
+  return rs_avgpool_bwd<RsBF16>(dy, dx, N, H, W, C, stream);
+}
+
+int odvae_upsample2x_bf16(const void* x, void* u, int N, int H, int W, int C, float* gn_partial, int gn_groups, int chunks, void* stream) {
+  return rs_upsample<RsBF16>(x, u, N, H, W, C, gn_partial, gn_groups, chunks, stream);
 }
 
 size_t odvae_colsum_bf16_workspace_bytes(int64_t rows, int C) { return (size_t)colsum_blocks(rows) * C * sizeof(float); }

@@ -203,6 +203,45 @@ __global__ __launch_bounds__(256) void upsample2x_bwd_kernel(const float* __rest
   }
 }
 
+// ---- conv-less resamplers (ddconfig.resamp_with_conv = False) and Decoder(tanh_out=True) ----------------
+// streaming accesses, as the GroupNorm apply passes: every byte is touched once here and next by another kernel
+typedef float ew_f4 __attribute__((ext_vector_type(4)));
+struct RsF32 {
+  typedef float elem_t;
+  static constexpr int W = 4;
+  static __device__ __forceinline__ void load(const float* p, float (&f)[4]) {
+    const ew_f4 v = __builtin_nontemporal_load(reinterpret_cast<const ew_f4*>(p));
+    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+  }
+  static __device__ __forceinline__ void store(float* p, float (&f)[4]) {
+    __builtin_nontemporal_store(ew_f4{f[0], f[1], f[2], f[3]}, reinterpret_cast<ew_f4*>(p));
+  }
+};
+#include "resample.h"
+
+// y = tanh(x) on a flat array ([UPSTREAM] Decoder.forward: `if self.tanh_out: h = torch.tanh(h)`); float4 body where the pointers allow
+// Plain (cached) accesses, unlike the resamplers' streaming ones: the reconstruction is 3 channels (25 MB at B = 32, 256 x 256) and the loss kernels
+// read it next, y again in the backward -- it should stay in the cache, not pass it by.
+__global__ __launch_bounds__(256) void tanh_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n, int vec) {
+  const int64_t n4 = vec ? n / 4 : 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 v = reinterpret_cast<const float4*>(x)[i];
+    reinterpret_cast<float4*>(y)[i] = make_float4(tanhf(v.x), tanhf(v.y), tanhf(v.z), tanhf(v.w));
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = tanhf(x[i]);
+}
+// dx = dy * (1 - y^2): only y is kept
+__global__ __launch_bounds__(256) void tanh_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy, float* __restrict__ dx,
+                                                       int64_t n, int vec) {
+  const int64_t n4 = vec ? n / 4 : 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 v = reinterpret_cast<const float4*>(y)[i], g = reinterpret_cast<const float4*>(dy)[i];
+    reinterpret_cast<float4*>(dx)[i] = make_float4(g.x * (1.f - v.x * v.x), g.y * (1.f - v.y * v.y), g.z * (1.f - v.z * v.z), g.w * (1.f - v.w * v.w));
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    dx[i] = dy[i] * (1.f - y[i] * y[i]);
+}
+
 // ---- batch min/max rescale: 2(x-min)/(max-min)-1  (src/models/autoencoder.py:434-436) -----------------
 __global__ __launch_bounds__(256) void minmax_partial_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ part) {
   __shared__ float sh[8];
@@ -713,6 +752,39 @@ int odvae_upsample2x_bwd_f32(const float* du, float* dx, int N, int H, int W, in
   ODVAE_CHECK_ARG(du && dx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "upsample2x_bwd: need C %% 4 == 0");
   hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(grid_1d((int64_t)N * H * W * (C / 4))), dim3(256), 0, static_cast<hipStream_t>(stream), du, dx, N, H, W, C);
   ODVAE_LAUNCH_CHECK("upsample2x_bwd");
+  return ODVAE_OK;
+}
+
+// Downsample(with_conv=False): y [N][H/2][W/2][C] = F.avg_pool2d(x [N][H][W][C], 2, 2) (an odd last row / column is dropped).
+// gn_partial (nullable): [N][chunks][gn_groups][2] = (sum, sum of squares) of y, every slot written -- what odvae_groupnorm_fwd_partials_f32 takes
+int odvae_avgpool2x2_f32(const float* x, float* y, int N, int H, int W, int C, float* gn_partial, int gn_groups, int chunks, void* stream) {
+  return rs_avgpool<RsF32>(x, y, N, H, W, C, gn_partial, gn_groups, chunks, stream);
+}
+
+// dx [N][H][W][C] (overwritten, zeros in a dropped row / column) from dy [N][H/2][W/2][C]
+int odvae_avgpool2x2_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
+  return rs_avgpool_bwd<RsF32>(dy, dx, N, H, W, C, stream);
+}
+
+// Upsample(with_conv=False): u [N][2H][2W][C] = F.interpolate(x [N][H][W][C], scale_factor=2, mode="nearest"); gn_partial as above, the
+// statistics of u (4 x those of x).  Backward: odvae_upsample2x_bwd_f32
+int odvae_upsample2x_f32(const float* x, float* u, int N, int H, int W, int C, float* gn_partial, int gn_groups, int chunks, void* stream) {
+  return rs_upsample<RsF32>(x, u, N, H, W, C, gn_partial, gn_groups, chunks, stream);
+}
+
+int odvae_tanh_f32(const float* x, float* y, int64_t n, void* stream) {
+  ODVAE_CHECK_ARG(x && y && n > 0, "tanh: bad arguments");
+  const int vec = (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+  hipLaunchKernelGGL(tanh_kernel, dim3(grid_1d(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, n, vec);
+  ODVAE_LAUNCH_CHECK("tanh");
+  return ODVAE_OK;
+}
+
+int odvae_tanh_bwd_f32(const float* y, const float* dy, float* dx, int64_t n, void* stream) {
+  ODVAE_CHECK_ARG(y && dy && dx && n > 0, "tanh_bwd: bad arguments");
+  const int vec = (((uintptr_t)y | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0;
+  hipLaunchKernelGGL(tanh_bwd_kernel, dim3(grid_1d(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), y, dy, dx, n, vec);
+  ODVAE_LAUNCH_CHECK("tanh_bwd");
   return ODVAE_OK;
 }
 

@@ -83,6 +83,11 @@ PROTOTYPES = {
     "odvae_softmax_rows_f32": (_I, [_P, _P, _L, _I, _F, _P]),
     "odvae_softmax_rows_bwd_f32": (_I, [_P, _P, _P, _L, _I, _F, _P]),
     "odvae_upsample2x_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "odvae_avgpool2x2_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "odvae_avgpool2x2_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "odvae_upsample2x_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "odvae_tanh_f32": (_I, [_P, _P, _L, _P]),
+    "odvae_tanh_bwd_f32": (_I, [_P, _P, _P, _L, _P]),
     "odvae_rescale_minmax_f32": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
     "odvae_gaussian_sample_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "odvae_gaussian_kl_f32": (_I, [_P, _P, _I, _I, _I, _P]),
@@ -154,6 +159,9 @@ PROTOTYPES = {
     "odvae_cast_pad_bf16": (_I, [_P, _L, _I, _I, _P, _P]),
     "odvae_cast_f32_from_bf16": (_I, [_P, _L, _P, _P]),
     "odvae_upsample2x_bwd_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "odvae_avgpool2x2_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "odvae_avgpool2x2_bwd_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "odvae_upsample2x_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "odvae_colsum_bf16_workspace_bytes": (_Z, [_L, _I]),
     "odvae_colsum_bf16": (_I, [_P, _L, _I, _P, _P, _Z, _P]),
     "odvae_patch_table_ints": (_I, [_I]),

@@ -58,12 +58,13 @@ class Conv1x1(nn.Conv2d):
 class Upsample(nn.Module):
     def __init__(self, channels, with_conv=True):
         super().__init__()
-        if not with_conv:
-            raise NotImplementedError("Upsample without conv is not on the OD-VAE path (resamp_with_conv=True)")
         self.with_conv = with_conv
-        self.conv = Conv3x3(channels, channels, mode=2)
+        if with_conv:
+            self.conv = Conv3x3(channels, channels, mode=2)
 
     def forward(self, x):
+        if not self.with_conv:      # (no parameters, as upstream) nearest 2x; the statistics of the result from the same pass
+            return ops.upsample2x(x, gn_stats=True)
         # nearest 2x is folded into the conv's input gather; a ResnetBlock's norm1 reads the result: statistics from the conv's epilogue
         return self.conv(x, gn_stats=True)
 
@@ -71,12 +72,13 @@ class Upsample(nn.Module):
 class Downsample(nn.Module):
     def __init__(self, channels, with_conv=True):
         super().__init__()
-        if not with_conv:
-            raise NotImplementedError("Downsample without conv is not on the OD-VAE path (resamp_with_conv=True)")
         self.with_conv = with_conv
-        self.conv = Conv3x3(channels, channels, mode=1)
+        if with_conv:
+            self.conv = Conv3x3(channels, channels, mode=1)
 
     def forward(self, x):
+        if not self.with_conv:      # F.avg_pool2d(x, 2, 2); a ResnetBlock's norm1 reads the result: statistics from the same pass
+            return ops.avg_pool2x2(x, gn_stats=True)
         return self.conv(x)  # pad (0,1,0,1) + stride 2 inside the kernel
 
 
@@ -259,8 +261,6 @@ class Decoder(nn.Module):
         self.compute_dtype = torch.float32   # see Encoder
         if use_linear_attn:
             attn_type = "linear"
-        if tanh_out:
-            raise NotImplementedError("tanh_out is not used by the OD-VAE configs")
         self.ch, self.temb_ch = ch, 0
         self.num_resolutions = len(ch_mult)
         self.num_res_blocks = num_res_blocks
@@ -332,4 +332,5 @@ class Decoder(nn.Module):
         h = self.norm_out(h, swish=True)
         self.recompute_norm = norm_policy
         with _remake(self, h):
-            return self.conv_out(h, out_f32=True)   # the reconstruction (and the losses on it) stay f32
+            h = self.conv_out(h, out_f32=True)   # the reconstruction (and the losses on it) stay f32
+        return ops.tanh(h) if self.tanh_out else h

@@ -285,6 +285,19 @@ int odvae_gemm_softmax_bwd_scaled_f32(int M, int N, int K, float alpha, const fl
                                       int64_t strideRow, float* dS, int ldc, int64_t strideC, int batch, void* stream);
 /* backward of F.interpolate(scale_factor=2, mode="nearest"): dx[N][H][W][C] from du[N][2H][2W][C] */
 int odvae_upsample2x_bwd_f32(const float* du, float* dx, int N, int H, int W, int C, void* stream);
+/* The conv-less resamplers (ddconfig.resamp_with_conv = False), NHWC, C % 4 == 0, C <= 1024, 16-byte aligned operands, no atomics.
+ * avgpool2x2: y [N][H/2][W/2][C] = F.avg_pool2d(x [N][H][W][C], 2, 2); an odd last row / column is dropped (H, W >= 2).  Its backward
+ * overwrites dx [N][H][W][C] = 0.25 dy broadcast, zeros in a dropped row / column.  upsample2x: u [N][2H][2W][C] =
+ * F.interpolate(x [N][H][W][C], scale_factor=2, mode="nearest"); its backward is odvae_upsample2x_bwd_f32.
+ * gn_partial (nullable): the same pass leaves the GroupNorm statistics of the RESULT, gn_partial [N][chunks][gn_groups][2] = (sum, sum of
+ * squares), every slot written -- the layout odvae_groupnorm_fwd_partials_f32 takes (gn_groups <= 256 divides C).  The kernel cuts the result's
+ * pixels into `chunks` runs itself; pass the count the consumer expects (odvae_conv3x3_wino4_stats_chunks of the result's H, W). */
+int odvae_avgpool2x2_f32(const float* x, float* y, int N, int H, int W, int C, float* gn_partial, int gn_groups, int chunks, void* stream);
+int odvae_avgpool2x2_bwd_f32(const float* dy, float* dx, int N, int H, int W, int C, void* stream);
+int odvae_upsample2x_f32(const float* x, float* u, int N, int H, int W, int C, float* gn_partial, int gn_groups, int chunks, void* stream);
+/* Decoder(tanh_out=True): y = tanh(x) on a flat f32 array of n elements; dx = dy * (1 - y * y) from the saved y */
+int odvae_tanh_f32(const float* x, float* y, int64_t n, void* stream);
+int odvae_tanh_bwd_f32(const float* y, const float* dy, float* dx, int64_t n, void* stream);
 /* PoseAutoencoder._rescale (src/models/autoencoder.py:434-436): NCHW in, NHWC out; workspace >= 8 KiB */
 int odvae_rescale_minmax_f32(const float* x_nchw, float* y_nhwc, int N, int C, int HW, float* minmax_out,
                              void* workspace, size_t workspace_bytes, void* stream);
@@ -482,6 +495,11 @@ int odvae_cast_pad_bf16(const float* x, int64_t rows, int C, int CP, void* y, vo
 int odvae_cast_f32_from_bf16(const void* x, int64_t n, float* y, void* stream);
 /* dx [N][H][W][C] = 2x2 sum-pool of du [N][2H][2W][C]: data gradient of F.interpolate(scale 2, nearest) */
 int odvae_upsample2x_bwd_bf16(const void* du, void* dx, int N, int H, int W, int C, void* stream);
+/* The bf16 forms of odvae_avgpool2x2_f32 / _bwd_f32 / odvae_upsample2x_f32 (C % 8 == 0, C <= 2048): f32 arithmetic, one rounding on the
+ * way out; gn_partial holds the statistics of the bf16-rounded result (chunks: odvae_conv_bf16_stats_chunks of the result's H, W) */
+int odvae_avgpool2x2_bf16(const void* x, void* y, int N, int H, int W, int C, float* gn_partial, int gn_groups, int chunks, void* stream);
+int odvae_avgpool2x2_bwd_bf16(const void* dy, void* dx, int N, int H, int W, int C, void* stream);
+int odvae_upsample2x_bf16(const void* x, void* u, int N, int H, int W, int C, float* gn_partial, int gn_groups, int chunks, void* stream);
 size_t odvae_colsum_bf16_workspace_bytes(int64_t rows, int C);
 /* out f32 [C] = column sums of x bf16 [rows][C] (bias gradients) */
 int odvae_colsum_bf16(const void* x, int64_t rows, int C, float* out, void* workspace, size_t workspace_bytes, void* stream);
