@@ -5,6 +5,8 @@ f32 and both sides accumulate in f32, so what remains is summation order plus ON
 (relative to max|ref|): f32 outputs (weight / bias gradients, statistics) 1e-3; bf16 outputs 1e-2 (bf16 has 8 significant bits:
 one rounding moves a value by up to half an ulp, between 2^-9 and 2^-8 = 4e-3 of the value itself, plus the rounding of bf16
 intermediates inside multi-kernel ops).  tests/test_bf16_exact_gpu.py pins the same kernels bit for bit on exactly summable inputs.
+Attention: with Gaussian q and k one key is 1/T of an output, so these tolerances cannot see a dropped key or a row constant of the
+neighbouring tile; tests/test_flash_attn_bf16_exact_gpu.py pins the flash-attention kernels on inputs with closed-form answers.
 """
 import math
 
