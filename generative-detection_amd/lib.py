@@ -166,6 +166,7 @@ PROTOTYPES = {
     "odvae_colsum_bf16": (_I, [_P, _L, _I, _P, _P, _Z, _P]),
     "odvae_patch_table_ints": (_I, [_I]),
     "odvae_patch_crop_resize_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "odvae_patch_reduce_resize_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     # device-side anomaly detection (anomaly.py); the tensor list is a host array of OdvaeAnomalyTensor
     "odvae_anomaly_scan": (_I, [_P, _I, _L, _I, _P, _P]),
     "odvae_anomaly_reset": (_I, [_P, _P]),

@@ -11,6 +11,9 @@ Host side, per instance (plain integer arithmetic, no device sync):
                       centre, snapping to PATCH_SIZES under `perturb_scale`, the four border clamps, padding pixels)
   * `mask_slice`   -- numpy's slice rule for `mask_bool[y1:y2, x1:x2] = True` (:178-187; negative starts wrap, as there)
   * `resample_table` -- Pillow's coefficient windows for (crop size -> S), cached per crop size
+  * `reduced_resample_table` -- the same behind Pillow's box pre-reduction (`reducing_gap=1.0`, crop size >= 2 S), with
+                      `reduce_multipliers` for the reduce itself (GpuPatcher(box_reduce=True))
+  * `crop_is_background` -- the acceptance rule for a background square (nuscenes.py:585-595); `backgrounds=` cuts them
 """
 import math
 
@@ -119,11 +122,83 @@ def resample_table(in_size, out_size):
     return tab
 
 
+def reduced_resample_table(in_size, out_size):
+    """(f, table) for `Image.resize((out_size, out_size), BILINEAR, reducing_gap=1.0)` on a square of side in_size: Pillow
+    first box-reduces by f = int(in_size / out_size) or 1 (Image.py resize) to side r = ceil(in_size / f), then resamples
+    from the reduced image with the source box [0, in_size / f) -- handed to C as float32 -- clipped to [0, r).  The table
+    has the layout of `resample_table`, windows over the REDUCED image; column 7 (the NEAREST index of the box mask, which
+    is never pre-reduced) stays the in_size -> out_size walk.  f == 1: `resample_table` itself."""
+    f = int(in_size / out_size) or 1
+    if f == 1:
+        return 1, resample_table(in_size, out_size)
+    r = -(-in_size // f)
+    in1 = float(np.float32(in_size / f))
+    scale = in1 / out_size                                         # < 2: at most 5 taps, as resample_table
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    inv = 1.0 / filterscale
+    idx = np.arange(out_size, dtype=np.float64)
+    center = 0.0 + (idx + 0.5) * scale
+    first = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    last = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), r)
+    taps = last - first
+    assert 1 <= taps.min() and taps.max() <= 5
+    w = np.zeros((out_size, 5), np.float64)
+    total = np.zeros(out_size, np.float64)
+    for t in range(5):
+        a = np.abs(((t + first).astype(np.float64) - center + 0.5) * inv)
+        wt = np.where((a < 1.0) & (t < taps), 1.0 - a, 0.0)
+        w[:, t] = wt
+        total = total + wt
+    w = np.where(total[:, None] != 0.0, w / np.where(total == 0.0, 1.0, total)[:, None], w)
+    tab = np.zeros((out_size, 8), np.int32)
+    tab[:, :5] = np.trunc(0.5 + w * float(1 << PRECISION_BITS)).astype(np.int64)
+    tab[:, 5] = first
+    tab[:, 6] = taps
+    step = float(in_size) / out_size
+    xo = 0.0 + step * 0.5
+    for i in range(out_size):
+        tab[i, 7] = int(xo)
+        xo += step
+    return f, tab
+
+
+def reduce_multiplier(n):
+    """Pillow Reduce.c division_UINT32(n, 8): (ss + n/2) * this >> 24 is the rounded mean of n bytes in u32 arithmetic."""
+    return int(np.float32(4294967296.0) / np.float32(256 * n))
+
+
+def reduce_multipliers(in_size, f):
+    """uint32 [4] = {mult(f*f), mult(f*rem), mult(rem*rem), 0}: full boxes, the narrower last column / row (rem = its width,
+    == f where f divides in_size) and their corner.  A partial box averages over the pixels it has (ImagingReduceCorners)."""
+    rem = in_size - (-(-in_size // f) - 1) * f
+    return np.asarray([reduce_multiplier(f * f), reduce_multiplier(f * rem), reduce_multiplier(rem * rem), 0], np.uint32)
+
+
+def crop_is_background(square, bboxes):
+    """Whether `get_random_crop_without_overlap` (nuscenes.py:585-595) accepts the square (x, y, size) as a background crop:
+    its IoU with every [x1, y1, x2, y2] box is < 0.5, or there are no boxes.  float32 like torchvision's box_iou on the
+    reference's float tensors.  The random draw of the square stays with the caller."""
+    x, y, size = square
+    if len(bboxes) == 0:
+        return True
+    c = np.asarray([x, y, x + size, y + size], np.float32)
+    bb = np.asarray(bboxes, np.float32).reshape(-1, 4)
+    wh = np.maximum(np.minimum(c[2:], bb[:, 2:]) - np.maximum(c[:2], bb[:, :2]), np.float32(0))
+    inter = wh[:, 0] * wh[:, 1]
+    area_c = (c[2] - c[0]) * (c[3] - c[1])
+    area_b = (bb[:, 2] - bb[:, 0]) * (bb[:, 3] - bb[:, 1])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou = inter / (area_c + area_b - inter)
+    return bool(np.all(iou < np.float32(0.5)))
+
+
 class PatchBatch:
     """What `_generate_patch` returns, batched: patch [n,3,S,S], mask [n,1,S,S] (device), patch_size [n,2] f32 (w, h) of
     the crop, resampling_factor [(fx, fy)], padding_pixels_resampled [n] and `kept` = indices of the instances that
-    were not dropped."""
-    __slots__ = ("patch", "mask", "patch_size", "resampling_factor", "padding_pixels_resampled", "kept", "plans")
+    were not dropped.  Background rows follow the object rows: `background` [n] bools says which rows they are; theirs are
+    patch_size (S, S) (the reference stores the network size there, nuscenes.py:549), an all-zero mask and no padding."""
+    __slots__ = ("patch", "mask", "patch_size", "resampling_factor", "padding_pixels_resampled", "kept", "plans", "background")
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -131,50 +206,80 @@ class PatchBatch:
 
 
 class GpuPatcher:
-    def __init__(self, patch_height=256, patch_aspect_ratio=1.0, perturb_scale=False, device="cuda:0"):
+    """`box_reduce=False` (default) refuses a crop of side >= 2 S with ValueError; `box_reduce=True` takes it the way Pillow's
+    `reducing_gap=1.0` does (box-reduce by int(side / S), then bilinear from the reduced image), on the device in the same
+    launch.  The reference always behaves like `box_reduce=True`."""
+
+    def __init__(self, patch_height=256, patch_aspect_ratio=1.0, perturb_scale=False, device="cuda:0", box_reduce=False):
         self.size = (patch_height, int(patch_height * patch_aspect_ratio))   # nuscenes.py:67
         if self.size[0] != self.size[1]:
             raise ValueError("the reference asserts equal resampling factors (nuscenes.py:172): square patches only")
         self.S = int(patch_height)
         self.perturb_scale = bool(perturb_scale)
+        self.box_reduce = bool(box_reduce)
         self.device = torch.device(device)
         self._slot = {}
         self._host_tables = []
+        self._host_mults = []
+        self._factors = []
         self._tables = None
 
-    def _table_slot(self, crop):
-        slot = self._slot.get(crop)
+    def _table_slot(self, crop, reduce):
+        """Slot of the tables for one crop size; `reduce` = resize with reducing_gap (objects) or without (backgrounds).  The two
+        differ only for crop >= 2 S, where the plain resize is refused."""
+        reduce = reduce and crop >= 2 * self.S
+        slot = self._slot.get((crop, reduce))
         if slot is None:
-            slot = self._slot[crop] = len(self._host_tables)
-            self._host_tables.append(resample_table(crop, self.S))
+            f, tab = reduced_resample_table(crop, self.S) if reduce else (1, resample_table(crop, self.S))
+            slot = self._slot[(crop, reduce)] = len(self._host_tables)
+            self._host_tables.append(tab)
+            self._host_mults.append(reduce_multipliers(crop, f))
+            self._factors.append(f)
             self._tables = None
         return slot
 
     def _device_tables(self):
         if self._tables is None:
-            self._tables = torch.from_numpy(np.stack(self._host_tables)).to(self.device)
+            self._tables = (torch.from_numpy(np.stack(self._host_tables)).to(self.device),
+                            torch.from_numpy(np.stack(self._host_mults).view(np.int32)).to(self.device))
         return self._tables
 
-    def __call__(self, images, instances):
+    def __call__(self, images, instances, backgrounds=()):
         """images: list of u8 [H,W,3] tensors on the device (decoded camera images); instances: iterable of
-        (image_index, bbox[4], center_2d[2]).  One launch for all kept instances."""
-        staged = self.stage(images, instances)
+        (image_index, bbox[4], center_2d[2]); backgrounds: iterable of (image_index, x, y, size), explicit squares
+        [x, x+size) x [y, y+size) cut like the reference's background samples (nuscenes.py:539-560): plain BILINEAR resize
+        without `reducing_gap`, all-zero mask.  A background of side >= 2 S would need windows wider than the kernel's 5
+        taps and raises ValueError (it cannot happen at S >= 201 with PATCH_SIZES <= 400).  One launch for all kept
+        instances and all backgrounds."""
+        staged = self.stage(images, instances, backgrounds)
         return self.launch(staged) if staged["n"] else PatchBatch(
-            patch=None, mask=None, patch_size=None, resampling_factor=[], padding_pixels_resampled=[], kept=[], plans=[])
+            patch=None, mask=None, patch_size=None, resampling_factor=[], padding_pixels_resampled=[], kept=[], plans=[], background=[])
 
-    def stage(self, images, instances):
+    def _check_image(self, img):
+        if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous() or not 6 <= img.numel() < 2 ** 31:
+            raise ValueError("camera images must be contiguous u8 [H,W,3] tensors")
+        if not img.is_cuda:
+            raise _lib.HipLibraryError("camera images must live on the HIP device (no CPU fallback), got %s" % img.device)
+
+    def stage(self, images, instances, backgrounds=()):
         """Host half: plan every instance and ship pointers, geometry and mask rectangles in one H2D copy."""
         plans, kept = [], []
         for i, (img_idx, bbox, center) in enumerate(instances):
             img = images[img_idx]
-            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous() or not 6 <= img.numel() < 2 ** 31:
-                raise ValueError("camera images must be contiguous u8 [H,W,3] tensors")
-            if not img.is_cuda:
-                raise _lib.HipLibraryError("camera images must live on the HIP device (no CPU fallback), got %s" % img.device)
+            self._check_image(img)
             plan = plan_patch(bbox, center, img.shape[1], img.shape[0], self.perturb_scale)
             if plan is not None:
-                plans.append((img_idx, plan))
+                plans.append((img_idx, plan, self.box_reduce))
                 kept.append(i)
+        n_obj = len(plans)
+        for img_idx, x, y, size in backgrounds:
+            self._check_image(images[img_idx])
+            if int(size) <= 0:
+                raise ValueError("background square of side %r" % (size,))
+            if int(size) >= 2 * self.S:
+                raise ValueError("background %d -> %d: a plain BILINEAR resize (no reducing_gap) needs windows wider than 5 taps; "
+                                 "not supported" % (size, self.S))
+            plans.append((img_idx, PatchPlan(int(x), int(y), int(size), 0, (0, 0), (0, 0)), False))   # empty mask rectangle
         n = len(plans)
         if n == 0:
             return {"n": 0}
@@ -184,28 +289,38 @@ class GpuPatcher:
         ptrs = host[:8 * n].view(np.int64)
         geom = host[ptr_bytes:ptr_bytes + 32 * n].view(np.int32).reshape(n, 8)
         rect = host[ptr_bytes + 32 * n:].view(np.int32).reshape(n, 4)
-        for j, (img_idx, plan) in enumerate(plans):
+        for j, (img_idx, plan, reduce) in enumerate(plans):
             img = images[img_idx]
+            slot = self._table_slot(plan.size, reduce)
             ptrs[j] = img.data_ptr()
-            geom[j, :6] = (img.shape[0], img.shape[1], plan.x1, plan.y1, plan.size, self._table_slot(plan.size))
+            geom[j, :7] = (img.shape[0], img.shape[1], plan.x1, plan.y1, plan.size, slot, self._factors[slot])
             rect[j] = (plan.mask_x[0], plan.mask_x[1], plan.mask_y[0], plan.mask_y[1])
-        return {"n": n, "ptr_bytes": ptr_bytes, "dev": torch.from_numpy(host).to(self.device, non_blocking=True),
-                "tables": self._device_tables(), "plans": [p for _, p in plans], "kept": kept,
-                "images": [images[k] for k, _ in plans]}   # keeps the camera images alive until the launch is issued
+        return {"n": n, "n_obj": n_obj, "ptr_bytes": ptr_bytes, "dev": torch.from_numpy(host).to(self.device, non_blocking=True),
+                "tables": self._device_tables(), "plans": [p for _, p, _ in plans], "kept": kept,
+                "reduced": bool((geom[:, 6] > 1).any()),
+                "images": [images[k] for k, _, _ in plans]}   # keeps the camera images alive until the launch is issued
 
-    def launch(self, staged):
-        """Device half: one kernel launch on the current stream."""
+    def launch(self, staged, entry=None):
+        """Device half: one kernel launch on the current stream.  entry: "crop" = odvae_patch_crop_resize_u8 (no instance may
+        have a reduce factor > 1), "reduce" = odvae_patch_reduce_resize_u8 (any batch); None picks by the batch."""
         L = _lib.load()
-        n, S, plans = staged["n"], self.S, staged["plans"]
+        n, n_obj, S, plans = staged["n"], staged["n_obj"], self.S, staged["plans"]
+        entry = entry or ("reduce" if staged["reduced"] else "crop")
+        if entry not in ("crop", "reduce") or (entry == "crop" and staged["reduced"]):
+            raise ValueError("entry %r cannot run this batch" % (entry,))
         patch = torch.empty((n, S, S, 3), dtype=torch.float32, device=self.device)
         mask = torch.empty((n, 1, S, S), dtype=torch.float32, device=self.device)
-        base, tables = staged["dev"].data_ptr(), staged["tables"]
-        _lib.check(L.odvae_patch_crop_resize_u8(base, base + staged["ptr_bytes"], base + staged["ptr_bytes"] + 32 * n,
-                                                tables.data_ptr(), tables.shape[0], n, S, patch.data_ptr(), mask.data_ptr(),
-                                                _lib.stream_ptr()), "patch_crop_resize")
+        base, (tables, mults) = staged["dev"].data_ptr(), staged["tables"]
+        args = (base, base + staged["ptr_bytes"], base + staged["ptr_bytes"] + 32 * n, tables.data_ptr())
+        tail = (tables.shape[0], n, S, patch.data_ptr(), mask.data_ptr(), _lib.stream_ptr())
+        if entry == "reduce":
+            _lib.check(L.odvae_patch_reduce_resize_u8(*args, mults.data_ptr(), *tail), "patch_reduce_resize")
+        else:
+            _lib.check(L.odvae_patch_crop_resize_u8(*args, *tail), "patch_crop_resize")
+        background = [j >= n_obj for j in range(n)]
         factor = [(S / p.size, S / p.size) for p in plans]
         return PatchBatch(patch=patch.permute(0, 3, 1, 2), mask=mask,
-                          patch_size=torch.tensor([[p.size, p.size] for p in plans], dtype=torch.float32),
+                          patch_size=torch.tensor([[S, S] if bg else [p.size, p.size] for p, bg in zip(plans, background)], dtype=torch.float32),
                           resampling_factor=factor,
                           padding_pixels_resampled=[p.padding_pixels * f[0] for p, f in zip(plans, factor)],
-                          kept=staged["kept"], plans=plans)
+                          kept=staged["kept"], plans=plans, background=background)

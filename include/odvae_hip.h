@@ -383,6 +383,15 @@ int odvae_lpips_distance_bwd_f32(const float* f0, const float* f1, const float* 
 int odvae_patch_table_ints(int S);
 int odvae_patch_crop_resize_u8(const void* d_images, const void* d_geom, const void* d_mask_rect, const void* d_tables,
                                int n_slots, int B, int S, void* patch, void* mask, void* stream);
+/* The same with Pillow's box pre-reduction (`reducing_gap=1.0` on a crop of side >= 2 S) per instance: d_geom[b][6] = reduce
+   factor f >= 1 (0 reads as 1).  An instance with f > 1 is box-reduced by f to side r = ceil(crop_size / f) (each byte
+   ((sum + n/2) * mult(n)) >> 24 in unsigned 32-bit arithmetic, n = crop pixels in the box) and its table slot then holds the
+   BILINEAR windows over the reduced image (source box [0, (float)(crop_size / f)), clipped to [0, r)); the nearest source
+   index stays the one of the unreduced walk.  d_mults [n_slots][4] uint32 per slot {mult(f*f), mult(f*rem), mult(rem*rem), 0},
+   rem = crop_size - (r - 1) * f the width of the last box, mult(n) = (uint32)(4294967296.0f / (float)(256 * n)), 0 where
+   unused.  f = 1 gives the bits of odvae_patch_crop_resize_u8; mixed batches go out in one launch. */
+int odvae_patch_reduce_resize_u8(const void* d_images, const void* d_geom, const void* d_mask_rect, const void* d_tables,
+                                 const void* d_mults, int n_slots, int B, int S, void* patch, void* mask, void* stream);
 
 /* ---- pose_f32.hip: every pose-head loss term in one launch (src/modules/losses/contperceptual.py:111-132,176-212) ------------- */
 /* dec_pose [B][8+NC] (pose 4 | lhw 3 | fill 1 | class logits), moments [B][16] (box posterior mean | raw logvar), prior [L][3][8]
