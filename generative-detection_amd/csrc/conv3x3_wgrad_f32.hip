@@ -688,6 +688,14 @@ size_t thin_workspace_floats(int Cin, int Cout) {
   const int cb = Cin <= 3 ? Cout : Cin;
   return (size_t)THIN_BLOCKS * 4 * cb * 32 + (size_t)THIN_BIAS_BLOCKS * 3;
 }
+// grid of the thin kernel: channel groups of 128 on y, four waves (= four image rows in flight) per block on x
+struct ThinPlan { int groups, blocks; };
+ThinPlan make_thin_plan(int N, int Hi, int Cin, int Cout) {
+  ThinPlan tp;
+  tp.groups = ceil_div(Cin <= 3 ? Cout : Cin, 128);
+  tp.blocks = std::max(1, std::min(THIN_BLOCKS / tp.groups, ceil_div(N * Hi, 4)));
+  return tp;
+}
 
 template <int MODE, int TH>
 size_t wgrad_smem_bytes() { return (size_t)(Halo<MODE, TH>::H * Halo<MODE, TH>::W + TH * TW) * BC * sizeof(float); }
@@ -709,6 +717,28 @@ size_t odvae_conv3x3_wgrad_workspace_bytes(int mode, int N, int Ho, int Wo, int 
   const Plan pl = make_plan(mode, N, Ho, Wo, Cin, Cout);
   if (pl.up) return ((size_t)pl.nsplit * 16 * pl.CinP * pl.CoutP + (size_t)pl.nsplit * 4 * pl.CoutP) * sizeof(float);
   return ((size_t)pl.nsplit * 9 * pl.CinP * pl.CoutP + (size_t)pl.nsplit * pl.CoutP) * sizeof(float);
+}
+
+// Which kernel a call gets and how its pixels are split over blocks; host only, launches nothing.
+// out = {kind, ntiles, nsplit, tiles_per_split, ci_tiles, co_tiles, tile_rows, effective_mode}; kind 0 thin, 1 v1, 2 v2 (LDS-DMA), 3 up.
+// thin: {0, blocks per channel group, waves (= slabs), channel groups, 0, 0, 1, 0}.
+int odvae_conv3x3_wgrad_plan(int mode, int N, int Hi, int Wi, int Cin, int Cout, int out[8]) {
+  ODVAE_CHECK_ARG(out, "conv3x3_wgrad_plan: null out");
+  ODVAE_CHECK_ARG((mode >= 0 && mode <= 2) || mode == 5, "conv3x3_wgrad_plan: mode %d", mode);
+  ODVAE_CHECK_ARG(N > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "conv3x3_wgrad_plan: empty shape");
+  if (mode == 1) ODVAE_CHECK_ARG(Hi % 2 == 0 && Wi % 2 == 0, "conv3x3_wgrad_plan mode 1: need even Hi,Wi");
+  if (thin_applies(mode, Hi, Wi, Cin, Cout)) {
+    const ThinPlan tp = make_thin_plan(N, Hi, Cin, Cout);
+    const int v[8] = {0, tp.blocks, tp.blocks * 4, tp.groups, 0, 0, 1, 0};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return ODVAE_OK;
+  }
+  const int Ho = mode == 0 ? Hi : mode == 1 ? Hi / 2 : 2 * Hi, Wo = mode == 0 ? Wi : mode == 1 ? Wi / 2 : 2 * Wi;
+  const Plan pl = make_plan(mode, N, Ho, Wo, Cin, Cout);
+  const int v[8] = {pl.up ? 3 : pl.v2 ? 2 : 1, pl.ntiles, pl.nsplit, pl.tiles_per_split, pl.ci_tiles, pl.co_tiles, pl.th,
+                    (mode == 5 && !pl.up) ? 2 : mode};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return ODVAE_OK;
 }
 
 // dw: OIHW [Cout][Cin][3][3] (overwritten).  dbias: [Cout] or null.
@@ -737,8 +767,8 @@ int odvae_conv3x3_wgrad_f32(int mode, const float* x, const float* dy, int N, in
     t.slab = static_cast<float*>(workspace);
     t.N = N; t.H = Hi; t.W = Wi; t.Cb = in_thin ? Cout : Cin; t.Cs = in_thin ? Cin : Cout; t.CbP = t.Cb;
     t.sign = in_thin ? 1 : -1; t.ones_col = (in_thin && dbias) ? 9 * t.Cs : -1;
-    const int groups = ceil_div(t.Cb, 128);
-    const int blocks = std::max(1, std::min(THIN_BLOCKS / groups, ceil_div(N * Hi, 4)));
+    const ThinPlan tp = make_thin_plan(N, Hi, Cin, Cout);
+    const int groups = tp.groups, blocks = tp.blocks;
     hipLaunchKernelGGL(conv3x3_wgrad_thin_kernel, dim3(blocks, groups), dim3(256), 0, st, t);
     ODVAE_LAUNCH_CHECK("conv3x3_wgrad thin");
     float* bpart = t.slab + (size_t)THIN_BLOCKS * 4 * t.Cb * 32;

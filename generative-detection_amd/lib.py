@@ -60,6 +60,7 @@ PROTOTYPES = {
     "odvae_conv3x3_f32": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "odvae_conv3x3_wgrad_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "odvae_conv3x3_wgrad_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "odvae_conv3x3_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "odvae_conv3x3_wgrad_wino_supported": (_I, [_I, _I, _I, _I, _I]),
     "odvae_conv3x3_wgrad_wino_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "odvae_conv3x3_wgrad_wino_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
@@ -225,6 +226,19 @@ def check(rc, what):
     if rc != 0:
         msg = load().odvae_last_error().decode("utf-8", "replace")
         raise HipLibraryError("%s failed (code %d): %s" % (what, rc, msg))
+
+
+WGRAD_PLAN_FIELDS = ("kind", "ntiles", "nsplit", "tiles_per_split", "ci_tiles", "co_tiles", "tile_rows", "effective_mode")
+WGRAD_KINDS = ("thin", "v1", "v2", "up")
+
+
+def conv3x3_wgrad_plan(mode, n, hi, wi, cin, cout):
+    """odvae_conv3x3_wgrad_plan as a dict (kind by name); host only, needs no device.  hi, wi are the input's."""
+    out = (_I * 8)()
+    check(load().odvae_conv3x3_wgrad_plan(mode, n, hi, wi, cin, cout, out), "odvae_conv3x3_wgrad_plan")
+    plan = dict(zip(WGRAD_PLAN_FIELDS, out))
+    plan["kind"] = WGRAD_KINDS[plan["kind"]]
+    return plan
 
 
 def stream_ptr():

@@ -146,6 +146,13 @@ size_t odvae_conv3x3_wgrad_workspace_bytes(int mode, int N, int Ho, int Wo, int 
 int odvae_conv3x3_wgrad_f32(int mode, const float* x, const float* dy, int N, int Hi, int Wi, int Cin,
                             int Ho, int Wo, int Cout, float* dw, float* dbias,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* Which kernel that call gets and how its pixels are split over blocks: host only, needs no device, launches nothing.  Hi, Wi are the
+ * INPUT's.  out = {kind, ntiles, nsplit, tiles_per_split, ci_tiles, co_tiles, tile_rows, effective_mode}: kind 0 thin (conv_in /
+ * conv_out), 1 v1, 2 v2 (LDS-DMA), 3 up (parity classes); tiles are tile_rows x 16 output pixels (kind 3: low-resolution pixels), split
+ * s owns tiles [s * tiles_per_split, min(ntiles, (s + 1) * tiles_per_split)); effective_mode is 2 where mode 5 falls back to the dense
+ * form.  kind 0: {0, blocks per channel group, waves (= partial slabs), channel groups of 128, 0, 0, 1, 0}; wave w owns image rows w,
+ * w + waves, ... of the N * Hi rows. */
+int odvae_conv3x3_wgrad_plan(int mode, int N, int Hi, int Wi, int Cin, int Cout, int out[8]);
 
 /* ---- conv3x3_wgrad_wino_f32.hip: the same weight/bias gradient for mode 0 (stride 1, pad 1) in the Winograd
  * F(2x2,3x3) domain: dU[xi] = sum over 2x2 tiles of (B^T d B)[xi]^T (A dY A^T)[xi], dw = G^T dU G -- 16 instead of 36

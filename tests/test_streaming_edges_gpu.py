@@ -14,48 +14,12 @@ import numpy as np
 import pytest
 import torch
 
+from canary_buffers import DEV, assert_canary, assert_workspace_canary, call, out_buf, padded, workspace
 import gn_offset_inputs as G
 import streaming_inputs as S
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-CANARY = 12345.0
-PAD = 8
 ERR_WORKSPACE = 2       # ODVAE_ERR_WORKSPACE
-
-
-def call(fn, *args):
-    from odvae_amd import lib
-    lib.check(fn(*args, lib.stream_ptr()), fn.__name__)
-
-
-def out_buf(n, fill=float("nan")):
-    """n output elements pre-filled with NaN and PAD canary elements behind them: (whole buffer, view of the n)"""
-    buf = torch.full((int(n) + PAD,), fill, device=DEV)
-    buf[int(n):] = CANARY
-    return buf, buf[:int(n)]
-
-
-def padded(t):
-    """a device copy of t with PAD canary elements behind it: (whole buffer, view shaped like t)"""
-    buf, view = out_buf(t.numel())
-    view.copy_(t.reshape(-1))
-    return buf, view.view(t.shape)
-
-
-def assert_canary(*bufs):
-    for b in bufs:
-        assert (b[-PAD:] == CANARY).all().item(), "the kernel wrote past the end of an output"
-
-
-def workspace(nbytes):
-    """exactly nbytes of workspace with 64 canary bytes behind it"""
-    buf = torch.full((int(nbytes) + 64,), 0xA5, dtype=torch.uint8, device=DEV)
-    return buf
-
-
-def assert_workspace_canary(buf):
-    assert (buf[-64:] == 0xA5).all().item(), "the kernel wrote past the workspace it asked for"
 
 
 # ---- row softmax, forward ------------------------------------------------------------------------------------------------------------
