@@ -354,14 +354,16 @@ extern "C" {
 
 int odvae_im2col4x4_f32(const float* x, float* cols, int N, int Hi, int Wi, int C, int Ho, int Wo, int stride, void* stream) {
   ODVAE_CHECK_ARG(x && cols && N > 0 && C > 0 && (stride == 1 || stride == 2), "im2col4x4: bad arguments");
-  ODVAE_CHECK_ARG(Ho == (Hi + 2 - 4) / stride + 1 && Wo == (Wi + 2 - 4) / stride + 1, "im2col4x4: Ho/Wo do not match k=4, pad=1, stride=%d", stride);
+  // Hi, Wi >= 2: the padded image holds the 4x4 window (and (Hi - 2) / stride is no truncation of a negative number)
+  ODVAE_CHECK_ARG(Hi >= 2 && Wi >= 2 && Ho == (Hi - 2) / stride + 1 && Wo == (Wi - 2) / stride + 1, "im2col4x4: Ho/Wo do not match k=4, pad=1, stride=%d", stride);
   hipLaunchKernelGGL(im2col4x4_kernel, dim3(grid_1d((int64_t)N * Ho * Wo * 16 * C, 16384)), dim3(256), 0, static_cast<hipStream_t>(stream), x, cols, N, Hi, Wi, C, Ho, Wo, stride);
   ODVAE_LAUNCH_CHECK("im2col4x4");
   return ODVAE_OK;
 }
 
 int odvae_col2im4x4_f32(const float* dcols, float* dx, int N, int Hi, int Wi, int C, int Ho, int Wo, int stride, void* stream) {
-  ODVAE_CHECK_ARG(dcols && dx && N > 0 && C > 0 && (stride == 1 || stride == 2), "col2im4x4: bad arguments");
+  ODVAE_CHECK_ARG(dcols && dx && N > 0 && C > 0 && Hi > 0 && Wi > 0 && (stride == 1 || stride == 2), "col2im4x4: bad arguments");
+  ODVAE_CHECK_ARG(Hi >= 2 && Wi >= 2 && Ho == (Hi - 2) / stride + 1 && Wo == (Wi - 2) / stride + 1, "col2im4x4: Ho/Wo do not match k=4, pad=1, stride=%d", stride);
   hipLaunchKernelGGL(col2im4x4_kernel, dim3(grid_1d((int64_t)N * Hi * Wi * C, 16384)), dim3(256), 0, static_cast<hipStream_t>(stream), dcols, dx, N, Hi, Wi, C, Ho, Wo, stride);
   ODVAE_LAUNCH_CHECK("col2im4x4");
   return ODVAE_OK;

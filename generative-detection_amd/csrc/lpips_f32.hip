@@ -22,9 +22,16 @@ __global__ __launch_bounds__(256) void scaling_layer_kernel(const float* __restr
   }
 }
 
-// y[n][oy][ox][c] = max over the 2x2 window of x (H, W even)
-__global__ __launch_bounds__(256) void maxpool2x2_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int Ho, int Wo, int C) {
-  const int q = C / 4;
+// y[n][oy][ox][c] = max over the 2x2 window of x [N][H][W][C], Ho = H / 2, Wo = W / 2: an odd last row / column is dropped (torch floors).
+// A window that holds a NaN yields NaN (torch's scan keeps the last one); fmaxf alone would return the window's largest number.
+__device__ __forceinline__ float max4_nan(float a, float b, float c, float d) {
+  float m = fmaxf(fmaxf(a, b), fmaxf(c, d));
+  m = a != a ? a : m; m = b != b ? b : m; m = c != c ? c : m; m = d != d ? d : m;
+  return m;
+}
+__global__ __launch_bounds__(256) void maxpool2x2_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W, int C) {
+  const int q = C / 4, Ho = H / 2, Wo = W / 2;
+  const int64_t row = (int64_t)W * C;
   const int64_t total = (int64_t)N * Ho * Wo * q;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (int64_t)gridDim.x * blockDim.x) {
@@ -32,36 +39,48 @@ __global__ __launch_bounds__(256) void maxpool2x2_kernel(const float* __restrict
     int64_t r = idx / q;
     const int ox = (int)(r % Wo); r /= Wo;
     const int oy = (int)(r % Ho); const int n = (int)(r / Ho);
-    const float* s = x + (((int64_t)n * 2 * Ho + 2 * oy) * 2 * Wo + 2 * ox) * C + 4 * cq;
+    const float* s = x + (((int64_t)n * H + 2 * oy) * W + 2 * ox) * C + 4 * cq;
     const float4 a = *reinterpret_cast<const float4*>(s), b = *reinterpret_cast<const float4*>(s + C);
-    const float4 c = *reinterpret_cast<const float4*>(s + (int64_t)2 * Wo * C), d = *reinterpret_cast<const float4*>(s + (int64_t)2 * Wo * C + C);
+    const float4 c = *reinterpret_cast<const float4*>(s + row), d = *reinterpret_cast<const float4*>(s + row + C);
     float4 o;
-    o.x = fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x)); o.y = fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y));
-    o.z = fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z)); o.w = fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w));
+    o.x = max4_nan(a.x, b.x, c.x, d.x); o.y = max4_nan(a.y, b.y, c.y, d.y);
+    o.z = max4_nan(a.z, b.z, c.z, d.z); o.w = max4_nan(a.w, b.w, c.w, d.w);
     *reinterpret_cast<float4*>(y + idx * 4) = o;
   }
 }
 
-// dx: dy goes to the first element of the window (row-major scan) that equals the max, zero elsewhere (torch rule)
+// dx: dy goes to the first element of the window (row-major scan) that equals the max, zero elsewhere (torch rule); where the max is
+// NaN, to the window's first NaN.  One thread per 2x2 cell of the input and channel, the cells of an odd last row / column included:
+// those hold one or two pixels that no window covers, and get 0, so every element of dx is written.
 __global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                              const float* __restrict__ dy, float* __restrict__ dx,
-                                                             int N, int Ho, int Wo, int C) {
-  const int64_t total = (int64_t)N * Ho * Wo * C;
+                                                             int N, int H, int W, int C) {
+  const int Ho = H / 2, Wo = W / 2, Hc = (H + 1) / 2, Wc = (W + 1) / 2;
+  const int64_t row = (int64_t)W * C;
+  const int64_t total = (int64_t)N * Hc * Wc * C;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(idx % C);
     int64_t r = idx / C;
-    const int ox = (int)(r % Wo); r /= Wo;
-    const int oy = (int)(r % Ho); const int n = (int)(r / Ho);
-    const int64_t base = (((int64_t)n * 2 * Ho + 2 * oy) * 2 * Wo + 2 * ox) * C + c;
-    const int64_t off[4] = {0, C, (int64_t)2 * Wo * C, (int64_t)2 * Wo * C + C};
-    const float m = y[idx], g = dy[idx];
-    bool done = false;
+    const int cx = (int)(r % Wc); r /= Wc;
+    const int cy = (int)(r % Hc); const int n = (int)(r / Hc);
+    const int64_t base = (((int64_t)n * H + 2 * cy) * W + 2 * cx) * C + c;
+    if (cy < Ho && cx < Wo) {
+      const int64_t off[4] = {0, C, row, row + C};
+      const int64_t o = (((int64_t)n * Ho + cy) * Wo + cx) * C + c;
+      const float m = y[o], g = dy[o];
+      bool done = false;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const bool hit = !done && x[base + off[k]] == m;
-      dx[base + off[k]] = hit ? g : 0.f;
-      done = done || hit;
+      for (int k = 0; k < 4; ++k) {
+        const float v = x[base + off[k]];
+        const bool hit = !done && (v == m || (m != m && v != v));
+        dx[base + off[k]] = hit ? g : 0.f;
+        done = done || hit;
+      }
+    } else {      // cy == Ho (H odd) and / or cx == Wo (W odd): the cell's pixels that exist
+      dx[base] = 0.f;
+      if (2 * cx + 1 < W) dx[base + C] = 0.f;
+      if (2 * cy + 1 < H) dx[base + row] = 0.f;
     }
   }
 }
@@ -165,17 +184,21 @@ int odvae_scaling_layer_f32(const float* x, const float* shift, const float* sca
   return ODVAE_OK;
 }
 
-// x [N][2Ho][2Wo][C] -> y [N][Ho][Wo][C]
-int odvae_maxpool2x2_f32(const float* x, float* y, int N, int Ho, int Wo, int C, void* stream) {
-  ODVAE_CHECK_ARG(x && y && N > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 4 == 0, "maxpool2x2: need C %% 4 == 0");
-  hipLaunchKernelGGL(maxpool2x2_kernel, dim3(grid_1d((int64_t)N * Ho * Wo * (C / 4))), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, N, Ho, Wo, C);
+// x [N][Hi][Wi][C] -> y [N][Ho][Wo][C], Ho = Hi / 2, Wo = Wi / 2 (floor, as torch.nn.MaxPool2d(2, 2))
+int odvae_maxpool2x2_f32(const float* x, float* y, int N, int Hi, int Wi, int C, int Ho, int Wo, void* stream) {
+  ODVAE_CHECK_ARG(x && y && N > 0 && Hi >= 2 && Wi >= 2 && C > 0 && C % 4 == 0, "maxpool2x2: need Hi, Wi >= 2 and C %% 4 == 0");
+  ODVAE_CHECK_ARG(Ho == Hi / 2 && Wo == Wi / 2, "maxpool2x2: Ho/Wo must be Hi / 2, Wi / 2 (floor): got %d x %d for %d x %d", Ho, Wo, Hi, Wi);
+  hipLaunchKernelGGL(maxpool2x2_kernel, dim3(grid_1d((int64_t)N * Ho * Wo * (C / 4))), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, N, Hi, Wi, C);
   ODVAE_LAUNCH_CHECK("maxpool2x2");
   return ODVAE_OK;
 }
 
-int odvae_maxpool2x2_bwd_f32(const float* x, const float* y, const float* dy, float* dx, int N, int Ho, int Wo, int C, void* stream) {
-  ODVAE_CHECK_ARG(x && y && dy && dx && N > 0 && Ho > 0 && Wo > 0 && C > 0, "maxpool2x2_bwd: bad arguments");
-  hipLaunchKernelGGL(maxpool2x2_bwd_kernel, dim3(grid_1d((int64_t)N * Ho * Wo * C)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, dy, dx, N, Ho, Wo, C);
+// writes all of dx [N][Hi][Wi][C]: an odd last row / column gets 0
+int odvae_maxpool2x2_bwd_f32(const float* x, const float* y, const float* dy, float* dx, int N, int Hi, int Wi, int C, int Ho, int Wo, void* stream) {
+  ODVAE_CHECK_ARG(x && y && dy && dx && N > 0 && Hi >= 2 && Wi >= 2 && C > 0, "maxpool2x2_bwd: bad arguments");
+  ODVAE_CHECK_ARG(Ho == Hi / 2 && Wo == Wi / 2, "maxpool2x2_bwd: Ho/Wo must be Hi / 2, Wi / 2 (floor): got %d x %d for %d x %d", Ho, Wo, Hi, Wi);
+  const int64_t cells = (int64_t)N * ((Hi + 1) / 2) * ((Wi + 1) / 2) * C;
+  hipLaunchKernelGGL(maxpool2x2_bwd_kernel, dim3(grid_1d(cells)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, dy, dx, N, Hi, Wi, C);
   ODVAE_LAUNCH_CHECK("maxpool2x2_bwd");
   return ODVAE_OK;
 }

@@ -117,8 +117,8 @@ PROTOTYPES = {
     "odvae_leaky_relu_f32": (_I, [_P, _P, _F, _L, _P]),
     "odvae_leaky_relu_bwd_f32": (_I, [_P, _P, _P, _F, _L, _P]),
     "odvae_scaling_layer_f32": (_I, [_P, _P, _P, _P, _L, _I, _I, _P]),
-    "odvae_maxpool2x2_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "odvae_maxpool2x2_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "odvae_maxpool2x2_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "odvae_maxpool2x2_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "odvae_lpips_distance_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "odvae_lpips_distance_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "odvae_pose_losses_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),

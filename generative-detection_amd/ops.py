@@ -1624,7 +1624,14 @@ class _Conv4x4(Function):
 
 def conv4x4(x, weight, bias, stride):
     """PatchGAN convolution.  Cout = 1 (the logit head) is zero-padded to 4 output channels for the GEMM's
-    float4 staging and sliced back (torch cat/slice on [4,C,4,4] / [B,4,30,30]-sized tensors)."""
+    float4 staging and sliced back (torch cat/slice on [4,C,4,4] / [B,4,30,30]-sized tensors).
+    An input under 2 pixels high or wide is refused here, as torch refuses it (the padded image is smaller than the kernel)."""
+    if stride not in (1, 2):
+        raise ValueError("conv4x4: stride must be 1 or 2, got %r" % (stride,))
+    if x.dim() != 4 or x.shape[2] < 2 or x.shape[3] < 2:
+        raise ValueError("conv4x4: needs an [N, C, H, W] input with H, W >= 2 (kernel 4, padding 1), got %s" % (tuple(x.shape),))
+    if tuple(weight.shape[1:]) != (x.shape[1], 4, 4):
+        raise ValueError("conv4x4: weight %s does not fit an input with %d channels" % (tuple(weight.shape), x.shape[1]))
     cout = weight.shape[0]
     if cout % 4 == 0:
         return _Conv4x4.apply(x, weight, bias, stride)
@@ -1806,7 +1813,7 @@ class _MaxPool2x2(Function):
         x = _cl(x)
         n, c, h, w = x.shape
         y = _new_cl(n, c, h // 2, w // 2, x)
-        _lib.check(L.odvae_maxpool2x2_f32(x.data_ptr(), y.data_ptr(), n, h // 2, w // 2, c, _lib.stream_ptr()), "maxpool2x2")
+        _lib.check(L.odvae_maxpool2x2_f32(x.data_ptr(), y.data_ptr(), n, h, w, c, h // 2, w // 2, _lib.stream_ptr()), "maxpool2x2")
         ctx.save_for_backward(x, y)
         return y
 
@@ -1817,12 +1824,15 @@ class _MaxPool2x2(Function):
         dy = _cl(dy)
         n, c, h, w = x.shape
         dx = _new_cl(n, c, h, w, x)
-        _lib.check(L.odvae_maxpool2x2_bwd_f32(x.data_ptr(), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, h // 2, w // 2, c,
+        _lib.check(L.odvae_maxpool2x2_bwd_f32(x.data_ptr(), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, h, w, c, h // 2, w // 2,
                                               _lib.stream_ptr()), "maxpool2x2_bwd")
         return dx
 
 
 def maxpool2x2(x):
+    """torch.nn.MaxPool2d(2, 2): floors, so an odd last row / column is dropped and gets a zero gradient; NaN propagates."""
+    if x.dim() != 4 or x.shape[2] < 2 or x.shape[3] < 2:
+        raise ValueError("maxpool2x2: needs an [N, C, H, W] input with H, W >= 2, got %s" % (tuple(x.shape),))
     return _MaxPool2x2.apply(x)
 
 

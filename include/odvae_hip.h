@@ -371,9 +371,11 @@ int odvae_leaky_relu_bwd_f32(const float* x, const float* dy, float* dx, float s
 /* ---- lpips_f32.hip: LPIPS-style perceptual distance ([UPSTREAM] taming lpips.py; contperceptual.py:143) ------------- */
 /* ScalingLayer (x - shift[c]) / scale[c]; backward=1 computes x / scale[c] */
 int odvae_scaling_layer_f32(const float* x, const float* shift, const float* scale, float* y, int64_t npix, int C, int backward, void* stream);
-/* torch.nn.MaxPool2d(2, 2): x [N][2Ho][2Wo][C] -> y [N][Ho][Wo][C] */
-int odvae_maxpool2x2_f32(const float* x, float* y, int N, int Ho, int Wo, int C, void* stream);
-int odvae_maxpool2x2_bwd_f32(const float* x, const float* y, const float* dy, float* dx, int N, int Ho, int Wo, int C, void* stream);
+/* torch.nn.MaxPool2d(2, 2): x [N][Hi][Wi][C] -> y [N][Ho][Wo][C] with Ho == Hi / 2, Wo == Wi / 2 (floor; checked): an odd last row /
+ * column is dropped.  Hi, Wi >= 2; the forward needs C % 4 == 0.  A window that holds a NaN yields NaN.  The backward writes every element
+ * of dx (0 on a dropped row / column); dy goes to the window's first maximum in row-major order, in a NaN window to its first NaN. */
+int odvae_maxpool2x2_f32(const float* x, float* y, int N, int Hi, int Wi, int C, int Ho, int Wo, void* stream);
+int odvae_maxpool2x2_bwd_f32(const float* x, const float* y, const float* dy, float* dx, int N, int Hi, int Wi, int C, int Ho, int Wo, void* stream);
 /* out[n] = spatial mean of lin_w . (normalize_tensor(f0) - normalize_tensor(f1))^2 ; gradient w.r.t. f1 only */
 int odvae_lpips_distance_f32(const float* f0, const float* f1, const float* w, float* out, int N, int HW, int C,
                              void* workspace, size_t workspace_bytes, void* stream);
