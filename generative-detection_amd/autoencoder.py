@@ -54,10 +54,12 @@ class AutoencoderKL(LightningModule):
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
 
-    def set_precision(self, precision):
+    def set_precision(self, precision, perceptual_precision=None):
         """The trainer's `precision` (configs/autoencoder/pose/autoencoder_kl_16x16x16.yaml:139; PL-1.9 accepts 32, "32", 16, "bf16"):
         32 = f32 everywhere; "bf16" = mixed precision -- bf16 activations inside Encoder / Decoder on the bf16 MFMA kernels, f32
-        master weights, gradients, statistics, latent, reconstruction and losses.  fp16 is not offered (no loss scaler here)."""
+        master weights, gradients, statistics, latent, reconstruction and losses.  fp16 is not offered (no loss scaler here).
+        perceptual_precision: 32 or "bf16" for the LPIPS-style net of the loss (LPIPSStyle.set_precision); None leaves it as it is -- f32
+        unless ODVAE_LPIPS_BF16=1, with which `precision` takes the perceptual net along."""
         p = str(precision).lower()
         if p in ("32", "32-true", "fp32"):
             dt = torch.float32
@@ -67,6 +69,13 @@ class AutoencoderKL(LightningModule):
             raise ValueError("precision %r: this build computes in 32 (f32) or bf16 (mixed precision)" % (precision,))
         self.encoder.compute_dtype = dt
         self.decoder.compute_dtype = dt
+        lpips = getattr(getattr(self, "loss", None), "perceptual_loss", None)
+        if perceptual_precision is not None:
+            if not hasattr(lpips, "set_precision"):
+                raise ValueError("perceptual_precision=%r: the loss has no perceptual net" % (perceptual_precision,))
+            lpips.set_precision(perceptual_precision)
+        elif ops.LPIPS_BF16 and hasattr(lpips, "set_precision"):
+            lpips.set_precision(precision)
         return self
 
     def init_from_ckpt(self, path, ignore_keys=list()):

@@ -32,6 +32,7 @@ struct ConvB {
   int xcd;                 // 1: XCD-contiguous tile order
   float* gn_partial;       // STATS launches: [N][tiles per image][gn_groups][2] = (sum, sum of squares) of y per tile and channel group
   int gn_groups, gn_cpg;   // channel groups of the GroupNorm that reads y; channels per group (a multiple of 4, <= 128)
+  const bf16_t* mask;      // MASK launches: [N][Ho][Wo][Cout] bf16, the stored ReLU output of the layer below
 };
 
 template <int MODE, int TH> struct HaloB;
@@ -66,7 +67,11 @@ __device__ __forceinline__ void halo_origin_b(int oy0, int ox0, int& iy0, int& i
 // butterfly, the two pixel halves of the block meet in LDS, and one thread per group writes its slot (no atomics; the consumer's
 // finalize adds the tiles in f64 in a fixed order).  A template parameter: data-gradient launches and convs without a GroupNorm
 // behind them run the plain build.
-template <int MODE, int KC, int WCT, int WPT, int WAVES_CO, int WAVES_PX, int TH, int MINW = 1, bool STATS = false>
+// RELU / MASK (stride-1 3x3, bf16 output; the frozen VGG stack of the perceptual loss): RELU stores max(acc, 0), taken on the f32 accumulator
+// in front of the one rounding, with a NaN accumulator kept; MASK -- a data-gradient launch -- stores `mask > 0 ? acc : 0`, mask being the
+// stored ReLU output of the layer below, so what reaches HBM is the gradient at that layer's pre-activation and no dy * (y > 0) pass runs.
+template <int MODE, int KC, int WCT, int WPT, int WAVES_CO, int WAVES_PX, int TH, int MINW = 1, bool STATS = false, bool RELU = false,
+          bool MASK = false>
 __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
   static_assert(WAVES_CO * WAVES_PX == 4 && WAVES_PX * WPT * 32 == TH * TW, "tile layout");
   constexpr int BCO = WAVES_CO * WCT * 32;
@@ -92,8 +97,9 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
   int iy0, ix0;
   halo_origin_b<MODE>(oy0, ox0, iy0, ix0);
   static_assert(MODE == 0 || MODE == 4 || TH == 8, "the wide tile is only built for modes 0 and 4");
+  static_assert(!(RELU || MASK) || (MODE == 0 && !STATS && !(RELU && MASK)), "ReLU / mask epilogues: stride-1 3x3 only, one at a time");
 
-  const int esz = p.out_f32 ? 4 : 2;
+  const int esz = (!(RELU || MASK) && p.out_f32) ? 4 : 2;
   const unsigned OOB = 0x7FFFFFF0u;
   // this lane's pixel in each of its pixel tiles (column of the MFMA result)
   unsigned pixoff[WPT];      // element offset of the output pixel, or OOB
@@ -242,6 +248,9 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
     for (int g = 0; g < 4; ++g) { gs[ct][g] = 0.f; gq[ct][g] = 0.f; }
   const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(
       static_cast<char*>(p.y) + (int64_t)n * p.Ho * p.Wo * p.Cout * esz, 0, p.Ho * p.Wo * p.Cout * esz, 0x00020000);
+  // MASK: the mask has the output's shape and is read at the output's offsets (a lane outside the image reads 0 and stores nothing)
+  const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<bf16_t*>(MASK ? p.mask + (int64_t)n * p.Ho * p.Wo * p.Cout : p.x), 0, MASK ? p.Ho * p.Wo * p.Cout * 2 : 0, 0x00020000);
 #pragma unroll
   for (int ct = 0; ct < WCT; ++ct)
 #pragma unroll
@@ -249,7 +258,7 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
       const int co = co0 + (wco * WCT + ct) * 32 + 8 * g + 4 * h;
 #pragma unroll
       for (int pt = 0; pt < WPT; ++pt) {
-        if (p.out_f32) {
+        if (!(RELU || MASK) && p.out_f32) {   // (the ReLU / mask builds write bf16 only: without this branch they keep the plain build's registers)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const unsigned off = (pixoff[pt] != OOB && co + j < p.Cout) ? (pixoff[pt] + (unsigned)(co + j)) * 4u : OOB;
@@ -257,9 +266,20 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
           }
         } else {   // Cout % 4 == 0 (host check): a 4-channel run is inside or outside as a whole
           const unsigned off = (pixoff[pt] != OOB && co < p.Cout) ? (pixoff[pt] + (unsigned)co) * 2u : OOB;
+          float a4[4] = {acc[ct][pt][4 * g + 0], acc[ct][pt][4 * g + 1], acc[ct][pt][4 * g + 2], acc[ct][pt][4 * g + 3]};
+          if (RELU) {       // (a <= 0 is false for a NaN: it stays, as in torch.relu; -0 becomes +0)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a4[j] = a4[j] <= 0.f ? 0.f : a4[j];
+          }
+          if (MASK) {
+            const u32x2 m = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(mrsrc, off, 0, 0));
+            const float mv[4] = {bf16_lo(m.x), bf16_hi(m.x), bf16_lo(m.y), bf16_hi(m.y)};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a4[j] = mv[j] > 0.f ? a4[j] : 0.f;
+          }
           u32x2 v;
-          v.x = pack_bf16x2(acc[ct][pt][4 * g + 0], acc[ct][pt][4 * g + 1]);
-          v.y = pack_bf16x2(acc[ct][pt][4 * g + 2], acc[ct][pt][4 * g + 3]);
+          v.x = pack_bf16x2(a4[0], a4[1]);
+          v.y = pack_bf16x2(a4[2], a4[3]);
           __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned int, v), yrsrc, off, 0, 0);
           if (STATS && off != OOB) {
             const float r0 = bf16_lo(v.x), r1 = bf16_hi(v.x), r2 = bf16_lo(v.y), r3 = bf16_hi(v.y);
@@ -336,16 +356,17 @@ __global__ void conv_pack_bf16_kernel(const float* __restrict__ w, int Cout, int
 
 int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 
-template <int MODE, int KC, int WCT, int WPT, int WAVES_CO, int WAVES_PX, int TH, int MINW = 1, bool STATS = false>
+template <int MODE, int KC, int WCT, int WPT, int WAVES_CO, int WAVES_PX, int TH, int MINW = 1, bool STATS = false, bool RELU = false,
+          bool MASK = false>
 void launch_cfg(const ConvB& p, dim3 grid, hipStream_t st) {
   constexpr int bytes = 2 * HaloB<MODE, TH>::H * HaloB<MODE, TH>::W * (KC + 8) * 2;
   static bool once = false;
   if (!once) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MODE, KC, WCT, WPT, WAVES_CO, WAVES_PX, TH, MINW, STATS>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MODE, KC, WCT, WPT, WAVES_CO, WAVES_PX, TH, MINW, STATS, RELU, MASK>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     once = true;
   }
-  hipLaunchKernelGGL((conv_bf16_kernel<MODE, KC, WCT, WPT, WAVES_CO, WAVES_PX, TH, MINW, STATS>), grid, dim3(256), bytes, st, p);
+  hipLaunchKernelGGL((conv_bf16_kernel<MODE, KC, WCT, WPT, WAVES_CO, WAVES_PX, TH, MINW, STATS, RELU, MASK>), grid, dim3(256), bytes, st, p);
 }
 
 template <int MODE, int KC>
@@ -361,6 +382,14 @@ void launch_by_cout(ConvB& p, hipStream_t st) {
   if (p.Cout > 64)      launch_cfg<MODE, KC, 2, 2, 2, 2, 8, MW>(p, dim3(tiles, ceil_div(p.Cout, 128)), st);
   else if (p.Cout > 32) launch_cfg<MODE, KC, 2, 1, 1, 4, 8>(p, dim3(tiles, 1), st);
   else                  launch_cfg<MODE, KC, 1, 1, 1, 4, 8>(p, dim3(tiles, 1), st);
+}
+
+// The stride-1 3x3 conv with a ReLU (EPI 1) or a mask (EPI 2) epilogue: the shapes of the VGG stack, more than 32 output channels
+template <int KC, int EPI>
+void launch_epi(ConvB& p, hipStream_t st) {
+  const int tiles = p.N * p.tiles_x * p.tiles_y;
+  if (p.Cout > 64) launch_cfg<0, KC, 2, 2, 2, 2, 8, 1, false, EPI == 1, EPI == 2>(p, dim3(tiles, ceil_div(p.Cout, 128)), st);
+  else             launch_cfg<0, KC, 2, 1, 1, 4, 8, 1, false, EPI == 1, EPI == 2>(p, dim3(tiles, 1), st);
 }
 
 }  // namespace
@@ -394,7 +423,8 @@ int odvae_conv_pack_bf16(const float* w, int Cout, int Cin, int taps, void* fwd_
 // (reduce = Cin, out = Cout), bias f32 [Cout] or NULL, residual bf16 [N][Ho][Wo][Cout] or NULL, y bf16 (out_f32 = 0; needs
 // Cout % 4 == 0) or f32 (out_f32 = 1, any Cout).  mode 0..3 as in odvae_conv3x3_f32; mode 4 = 1x1 on [N][Hi][Wi] = [1][M/16][16].
 static int conv_bf16_impl(int mode, const void* x, int N, int Hi, int Wi, int Cin, const void* pack, int Cout, const float* bias,
-                          const void* residual, void* y, int Ho, int Wo, int out_f32, float* gn_partial, int gn_groups, void* stream);
+                          const void* residual, void* y, int Ho, int Wo, int out_f32, float* gn_partial, int gn_groups, void* stream,
+                          int epi = 0, const void* mask = nullptr);
 
 int odvae_conv_bf16(int mode, const void* x, int N, int Hi, int Wi, int Cin, const void* pack, int Cout, const float* bias,
                     const void* residual, void* y, int Ho, int Wo, int out_f32, void* stream) {
@@ -420,8 +450,23 @@ int odvae_conv_bf16_stats(const void* x, int N, int H, int W, int Cin, const voi
   return conv_bf16_impl(0, x, N, H, W, Cin, pack, Cout, bias, residual, y, H, W, 0, gn_partial, gn_groups, stream);
 }
 
+// The stride-1 3x3 conv + ReLU in one launch: y = relu(conv(x) + bias), the max taken on the f32 accumulator in front of the one rounding
+// to bf16; a NaN stays a NaN.  More than 32 output channels (a multiple of 4).
+int odvae_conv_bf16_relu(const void* x, int N, int H, int W, int Cin, const void* pack, int Cout, const float* bias, void* y, void* stream) {
+  return conv_bf16_impl(0, x, N, H, W, Cin, pack, Cout, bias, nullptr, y, H, W, 0, nullptr, 0, stream, 1, nullptr);
+}
+
+// The stride-1 3x3 conv whose epilogue writes `mask > 0 ? acc : 0`: with the flipped pack and mask = the stored ReLU output of the layer
+// below, the data gradient at that layer's pre-activation.  mask bf16 [N][H][W][Cout]; more than 32 output channels (a multiple of 4).
+int odvae_conv_bf16_masked(const void* x, int N, int H, int W, int Cin, const void* pack, int Cout, const void* mask, void* y, void* stream) {
+  ODVAE_CHECK_ARG(mask && ((uintptr_t)mask & 7) == 0, "conv_bf16_masked: null or misaligned mask");
+  return conv_bf16_impl(0, x, N, H, W, Cin, pack, Cout, nullptr, nullptr, y, H, W, 0, nullptr, 0, stream, 2, mask);
+}
+
 static int conv_bf16_impl(int mode, const void* x, int N, int Hi, int Wi, int Cin, const void* pack, int Cout, const float* bias,
-                          const void* residual, void* y, int Ho, int Wo, int out_f32, float* gn_partial, int gn_groups, void* stream) {
+                          const void* residual, void* y, int Ho, int Wo, int out_f32, float* gn_partial, int gn_groups, void* stream,
+                          int epi, const void* mask) {
+  ODVAE_CHECK_ARG(epi == 0 || (mode == 0 && !out_f32 && Cout > 32), "conv_bf16: the ReLU / mask epilogues need Cout > 32, got %d", Cout);
   ODVAE_CHECK_ARG(mode >= 0 && mode <= 4, "conv_bf16: mode %d", mode);
   ODVAE_CHECK_ARG(x && pack && y && N > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "conv_bf16: null or empty operand");
   ODVAE_CHECK_ARG(Cin % 8 == 0, "conv_bf16: Cin = %d must be a multiple of 8 (16-byte channel vectors)", Cin);
@@ -444,10 +489,13 @@ static int conv_bf16_impl(int mode, const void* x, int N, int Hi, int Wi, int Ci
   p.tiles_x = ceil_div(Wo, TW); p.tiles_y = ceil_div(Ho, 8); p.out_f32 = out_f32;
   p.gn_partial = gn_partial; p.gn_groups = gn_groups; p.gn_cpg = gn_groups > 0 ? Cout / gn_groups : 0;
   p.xcd = 1;
+  p.mask = static_cast<const bf16_t*>(mask);
   ODVAE_CHECK_ARG((int64_t)N * p.tiles_x * p.tiles_y < 0x7FFFFFFFll, "conv_bf16: too many tiles");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool k64 = p.CinP % 64 == 0;
-  switch (mode) {
+  if (epi == 1) { if (k64) launch_epi<64, 1>(p, st); else launch_epi<32, 1>(p, st); }
+  else if (epi == 2) { if (k64) launch_epi<64, 2>(p, st); else launch_epi<32, 2>(p, st); }
+  else switch (mode) {
     // (32-channel chunks at three blocks per CU -- __launch_bounds__(256, 3): 168 registers, 29 KB of LDS -- measured the same as
     // 64-channel chunks at two blocks per CU: 747 vs 740 TFLOP/s at 128 channels, B=32)
     case 0: if (k64) launch_by_cout<0, 64>(p, st); else launch_by_cout<0, 32>(p, st); break;

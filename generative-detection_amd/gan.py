@@ -141,7 +141,10 @@ class _VggConv(nn.Conv2d):
     def __init__(self, cin, cout):
         super().__init__(cin, cout, kernel_size=3, padding=1)
 
-    def forward(self, x):
+    def forward(self, x, mask_input=False, grad_premasked=False):
+        """f32 or bf16 by the input's dtype; the two flags are the bf16 net's ReLU-mask wiring (ops.conv3x3_relu_bf16)"""
+        if x.dtype == torch.bfloat16:
+            return ops.conv3x3_relu_bf16(x, self.weight, self.bias, mask_input, grad_premasked)
         return ops.conv3x3(x, self.weight, self.bias, None, 0, relu=True)
 
 
@@ -166,9 +169,10 @@ class ScalingLayer(nn.Module):
         super().__init__()
         self.register_buffer("shift", torch.tensor([-.030, -.088, -.188])[None, :, None, None])
         self.register_buffer("scale", torch.tensor([.458, .448, .450])[None, :, None, None])
+        self.compute_dtype = torch.float32   # torch.bfloat16: hand the bf16 net its 8-channel bf16 image in the same pass
 
     def forward(self, x):
-        return ops.scale_shift(x, self.shift, self.scale)
+        return ops.scale_shift(x, self.shift, self.scale, out_dtype=self.compute_dtype)
 
 
 class _Vgg16Features(nn.Module):
@@ -219,6 +223,7 @@ class LPIPSStyle(nn.Module):
         super().__init__()
         self.scaling_layer = ScalingLayer()
         self.chns = list(LPIPS_CHNS)
+        self.compute_dtype = torch.float32     # see set_precision
         self.net = _Vgg16Features()
         gen = torch.Generator().manual_seed(seed)
         with torch.no_grad():   # He-normal stand-in for the pretrained VGG16 weights (no network here)
@@ -276,10 +281,63 @@ class LPIPSStyle(nn.Module):
         ops.PACK_CACHE.bump()
         return self
 
+    def set_precision(self, precision):
+        """32 (default) or "bf16": the 13 VGG layers on the bf16 MFMA conv kernels with the ReLU in their epilogue, bf16 features, the
+        pools and the distance taps on the bf16 kernels of lpips_bf16.hip -- what torch.autocast makes of LPIPS under the reference's
+        `precision: bf16`.  Parameters, buffers and the state_dict stay f32."""
+        p = str(precision).lower()
+        if p in ("32", "32-true", "fp32"):
+            dt = torch.float32
+        elif p in ("bf16", "bf16-mixed"):
+            dt = torch.bfloat16
+        else:
+            raise ValueError("precision %r: the perceptual net computes in 32 (f32) or bf16" % (precision,))
+        self.compute_dtype = dt
+        self.scaling_layer.compute_dtype = dt
+        return self
+
     def features(self, x):
         return self.net(self.scaling_layer(x))
 
+    def _forward_bf16(self, input, target):
+        """The bf16 net.  The input branch needs no gradient: nothing of it is saved and no data-gradient pack is built.  The target
+        (reconstruction) branch is wired so that every ReLU's backward rides in the epilogue of the kernel that produces its incoming
+        gradient (ops: "Where the ReLU masks go"): each layer runs with grad_premasked, each conv behind a conv masks its data gradient
+        with its own input, each tap masks the sum of its own gradient and the one arriving from the next slice's pool."""
+        if input.requires_grad:
+            raise NotImplementedError("LPIPSStyle: gradient w.r.t. the first (input) branch is not on the OD-VAE path")
+        with torch.no_grad():
+            f0 = self.features(input)
+        sl = self.scaling_layer
+        if not target.requires_grad:
+            f1 = self.features(target)
+            ds = [ops.lpips_layer_distance(f0[k], f1[k], getattr(self, "lin%d" % k).weight) for k in range(len(self.chns))]
+        else:
+            ds, h, last = [], target, len(VGG16_SLICES) - 1
+            for k, (name, convs) in enumerate(VGG16_SLICES):
+                if k > 0:
+                    h = ops.maxpool2x2(h)          # reads the tap's pass-through: the tap masks
+                s = getattr(self.net, name)
+                for j, (idx, _, _) in enumerate(convs):
+                    conv = getattr(s, str(idx))
+                    if k == 0 and j == 0:
+                        h = ops.vgg_stem_bf16(h, sl.shift, sl.scale, conv.weight, conv.bias, grad_premasked=True)
+                    else:
+                        h = conv(h, mask_input=j > 0, grad_premasked=True)
+                lin_w = getattr(self, "lin%d" % k).weight
+                if k < last:
+                    d, h = ops.lpips_tap_bf16(f0[k], h, lin_w, passthrough=True, relu_mask=True)
+                else:
+                    d = ops.lpips_tap_bf16(f0[k], h, lin_w, relu_mask=True)
+                ds.append(d)
+        total = ds[0]
+        for d in ds[1:]:
+            total = total + d
+        return total.reshape(-1, 1, 1, 1)
+
     def forward(self, input, target):
+        if self.compute_dtype == torch.bfloat16:
+            return self._forward_bf16(input, target)
         f0, f1 = self.features(input), self.features(target)
         total = None
         for k in range(len(self.chns)):

@@ -135,6 +135,8 @@ PROTOTYPES = {
     "odvae_conv_bf16_stats_chunks": (_I, [_I, _I]),
     "odvae_conv_bf16_stats_supported": (_I, [_I, _I]),
     "odvae_conv_bf16_stats": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
+    "odvae_conv_bf16_relu": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "odvae_conv_bf16_masked": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     "odvae_conv_wgrad_bf16_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
     "odvae_conv_wgrad_bf16": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "odvae_flash_attn_supported": (_I, [_I, _I, _I]),
@@ -165,6 +167,13 @@ PROTOTYPES = {
     "odvae_upsample2x_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "odvae_colsum_bf16_workspace_bytes": (_Z, [_L, _I]),
     "odvae_colsum_bf16": (_I, [_P, _L, _I, _P, _P, _Z, _P]),
+    # the LPIPS-style perceptual net on bf16 features (opt-in)
+    "odvae_scaling_layer_bf16": (_I, [_P, _P, _P, _P, _L, _I, _P]),
+    "odvae_relu_bwd_bf16": (_I, [_P, _P, _P, _L, _P]),
+    "odvae_maxpool2x2_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "odvae_maxpool2x2_bwd_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "odvae_lpips_distance_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
+    "odvae_lpips_distance_bwd_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "odvae_patch_table_ints": (_I, [_I]),
     "odvae_patch_crop_resize_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "odvae_patch_reduce_resize_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),

@@ -32,7 +32,7 @@ class _TrainerHandle:
 class Trainer:
     def __init__(self, model, gradient_clip_val=None, optimizer_indices=(0, 1), process_group=None, bucket_mb=None, precision=None,
                  distributed=None, comm_dtype=None, callbacks=(), logger=None, comm_f32_accumulate=False,
-                 detect_anomaly=None, accumulate_grad_batches=1):
+                 detect_anomaly=None, accumulate_grad_batches=1, perceptual_precision=None):
         """optimizer_indices: which of the model's optimizers run each batch; (0,) is the "rec+KL only" benchmark
         configuration (discriminator off, optimizer 1 skipped -- SURVEY.md 8(d)).
         comm_dtype: dtype of the gradient buckets on the wire; None = f32 in every precision -- what the reference's `strategy: ddp`
@@ -49,7 +49,8 @@ class Trainer:
         accumulate_grad_batches: lightning.trainer.accumulate_grad_batches of the yaml (:134), PL-1.9 automatic optimisation: N consecutive
         batches form a window; every batch back-propagates loss / N into gradients that are zeroed only before the window's first backward; clip,
         optimizer.step() and the global_step increment happen on the window's last batch only.  1 = a step after
-        every batch."""
+        every batch.
+        perceptual_precision: 32 or "bf16" for the loss's LPIPS-style net (AutoencoderKL.set_precision); None leaves it alone."""
         if isinstance(accumulate_grad_batches, bool) or not isinstance(accumulate_grad_batches, int) or accumulate_grad_batches < 1:
             raise ValueError("accumulate_grad_batches must be an integer >= 1, got %r" % (accumulate_grad_batches,))
         self.accumulate_grad_batches = accumulate_grad_batches
@@ -65,7 +66,12 @@ class Trainer:
             except AttributeError:      # a real pytorch_lightning.LightningModule: `logger` is a read-only property of its Trainer
                 model._odvae_logger = logger
         if precision is not None:   # lightning.trainer.precision of the yaml (:139): 32 or "bf16"
-            model.set_precision(precision)
+            if perceptual_precision is not None:
+                model.set_precision(precision, perceptual_precision=perceptual_precision)
+            else:
+                model.set_precision(precision)
+        elif perceptual_precision is not None:
+            model.loss.perceptual_loss.set_precision(perceptual_precision)
         self.clip = gradient_clip_val
         self.detect_anomaly = anomaly.parse_mode(detect_anomaly)
         self.anomaly = anomaly.Detector(self.detect_anomaly, model) if self.detect_anomaly else None

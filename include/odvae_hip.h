@@ -446,6 +446,14 @@ int odvae_conv_bf16_stats_chunks(int H, int W);
 int odvae_conv_bf16_stats_supported(int Cout, int gn_groups);
 int odvae_conv_bf16_stats(const void* x, int N, int H, int W, int Cin, const void* pack, int Cout, const float* bias, const void* residual,
                           void* y, float* gn_partial, int gn_groups, void* stream);
+/* The stride-1 3x3 conv + ReLU of a VGG layer in one launch (replaces torch.relu(F.conv2d(x, w, b, padding=1)) under autocast):
+ * y = max(conv(x) + bias, 0) taken on the f32 accumulator in front of the one rounding to bf16; a NaN stays a NaN.  Cout > 32, Cout % 4 == 0.
+ * The 3-channel image comes in zero-padded to Cin = 8 (odvae_scaling_layer_bf16). */
+int odvae_conv_bf16_relu(const void* x, int N, int H, int W, int Cin, const void* pack, int Cout, const float* bias, void* y, void* stream);
+/* The stride-1 3x3 conv whose epilogue writes `mask > 0 ? acc : 0` (mask bf16 [N][H][W][Cout]).  With the data-gradient pack and mask =
+ * the stored ReLU output of the layer below it replaces torch's conv2d data gradient followed by threshold_backward (dy * (y > 0)):
+ * what reaches HBM is the gradient at that layer's pre-activation.  Cout > 32, Cout % 4 == 0. */
+int odvae_conv_bf16_masked(const void* x, int N, int H, int W, int Cin, const void* pack, int Cout, const void* mask, void* y, void* stream);
 /* ---- conv_wgrad_bf16.hip: weight gradient, dw f32 OIHW, modes 0 / 1 / 2 / 4 as above; deterministic ---------------------------- */
 size_t odvae_conv_wgrad_bf16_workspace_bytes(int mode, int N, int Ho, int Wo, int Cin, int Cout);
 /* db f32 [Cout] (bias gradient = per-channel sum of dy) or NULL, produced in the same pass */
@@ -521,6 +529,33 @@ int odvae_upsample2x_bf16(const void* x, void* u, int N, int H, int W, int C, fl
 size_t odvae_colsum_bf16_workspace_bytes(int64_t rows, int C);
 /* out f32 [C] = column sums of x bf16 [rows][C] (bias gradients) */
 int odvae_colsum_bf16(const void* x, int64_t rows, int C, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- lpips_bf16.hip: the LPIPS-style perceptual distance on bf16 features (opt-in: LPIPSStyle.set_precision("bf16")) -------------
+ * Features and feature gradients are bf16 NHWC, rounded to nearest even once per store; all arithmetic in between is f32.  A ReLU's
+ * backward is folded into the kernel that produces its incoming gradient: `mask` below is the ReLU output that the layer consumed
+ * (or NULL), and the kernel writes `mask > 0 ? value : 0`. */
+/* lpips.ScalingLayer and the cast into the bf16 net in one pass (replaces ((x - shift) / scale).to(bfloat16) plus the channel pad):
+ * x f32 [npix][C], C <= 8 -> y bf16 [npix][8], channels C..7 zero.  Its backward is odvae_scaling_layer_f32(backward = 1) on the f32
+ * C-channel data gradient that odvae_conv_bf16(out_f32 = 1) writes. */
+int odvae_scaling_layer_bf16(const float* x, const float* shift, const float* scale, void* y, int64_t npix, int C, void* stream);
+/* torch.relu's backward on bf16 (threshold_backward): dx = y > 0 ? dy : 0, for a ReLU output whose consumer does not fold the mask in.
+ * n % 4 == 0 */
+int odvae_relu_bwd_bf16(const void* y, const void* dy, void* dx, int64_t n, void* stream);
+/* torch.nn.MaxPool2d(2, 2) on bf16, the semantics of odvae_maxpool2x2_f32 / _bwd_f32: Ho == Hi / 2, Wo == Wi / 2 (floor; checked), an
+ * odd last row / column is dropped and gets zero gradient, a NaN window yields NaN, dy goes to the window's first maximum in row-major
+ * order (in a NaN window to its first NaN).  C % 4 == 0.  The backward recomputes the maximum from x and writes every element of dx;
+ * mask [N][Hi][Wi][C] or NULL: the ReLU output the pool read (then usually x itself). */
+int odvae_maxpool2x2_bf16(const void* x, void* y, int N, int Hi, int Wi, int C, int Ho, int Wo, void* stream);
+int odvae_maxpool2x2_bwd_bf16(const void* x, const void* dy, const void* mask, void* dx, int N, int Hi, int Wi, int C, int Ho, int Wo, void* stream);
+/* odvae_lpips_distance_f32 / _bwd_f32 reading bf16 features (replaces normalize_tensor, the squared difference, the lin layer's 1x1 conv
+ * and spatial_average of lpips.py): out f32 [N], f32 arithmetic.  C in {64, 128, 256, 512}; workspace N * 256 floats.
+ * Backward: df1 bf16 = round(mask > 0 ? g[n] * d out[n] / d f1 + dnext : 0) -- dnext bf16 [N][HW][C] or NULL is the gradient arriving
+ * at the same tensor from the next slice's pool, mask or NULL the tap's own ReLU output (usually f1): one f32 sum, one rounding.  The
+ * normalisation term is 0 at an all-zero feature vector, as in the f32 kernel. */
+int odvae_lpips_distance_bf16(const void* f0, const void* f1, const float* w, float* out, int N, int HW, int C,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int odvae_lpips_distance_bwd_bf16(const void* f0, const void* f1, const float* w, const float* g, const void* dnext, const void* mask,
+                                  void* df1, int N, int HW, int C, void* stream);
 
 /* ---- anomaly.hip: the NaN check torch.autograd.set_detect_anomaly(True) makes on every backward output, on the device ----------
  * One launch scans up to 8 outputs of one backward node (any dense layout: ptr = lowest element, numel elements).  dtype 0 f32, 1 bf16;

@@ -1,6 +1,8 @@
 """Which allocations reach hipMalloc in steady state?  Runs the bf16 (or f32) training step, then records the caching allocator's
 history over a few more steps and prints every `segment_alloc` (= a device allocation: a synchronising call) with the python frames of
-the request that caused it, plus per-step device-allocation counts.  usage: python tools/alloc_probe.py [--f32] [--gc-off] [--steps N]"""
+the request that caused it, plus per-step device-allocation counts.  --gan: PatchGAN + LPIPS-style loss, both optimizers (BASELINE configs[3]);
+--lpips-bf16: the perceptual net on its bf16 kernels too (Trainer(perceptual_precision="bf16")).
+usage: python tools/alloc_probe.py [--f32] [--gan] [--lpips-bf16] [--gc-off] [--steps N] [--history]"""
 import gc
 import os
 import sys
@@ -21,9 +23,12 @@ def main():
     warm = int(sys.argv[sys.argv.index("--warmup") + 1]) if "--warmup" in sys.argv else 6
     dev = torch.device("cuda:0")
     torch.manual_seed(23)
-    model = synthetic.build_model(YAML, batch_size_for_lr=12, latent_hw=16).to(dev).train()
+    gan = "--gan" in sys.argv
+    kw = dict(perceptual_weight=1.0, disc_factor=1.0, disc_start=0) if gan else {}
+    model = synthetic.build_model(YAML, batch_size_for_lr=12, latent_hw=16, **kw).to(dev).train()
     model._global_step = 1
-    trainer = Trainer(model, gradient_clip_val=1.0, optimizer_indices=(0,), precision=None if f32 else "bf16")
+    trainer = Trainer(model, gradient_clip_val=1.0, optimizer_indices=(0, 1) if gan else (0,), precision=None if f32 else "bf16",
+                      perceptual_precision="bf16" if "--lpips-bf16" in sys.argv else None)
     data = synthetic.make_batch(32, 256, seed=23)
     data = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in data.items()}
 
