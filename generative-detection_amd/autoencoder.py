@@ -54,12 +54,13 @@ class AutoencoderKL(LightningModule):
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
 
-    def set_precision(self, precision, perceptual_precision=None):
+    def set_precision(self, precision, perceptual_precision=None, discriminator_precision=None):
         """The trainer's `precision` (configs/autoencoder/pose/autoencoder_kl_16x16x16.yaml:139; PL-1.9 accepts 32, "32", 16, "bf16"):
         32 = f32 everywhere; "bf16" = mixed precision -- bf16 activations inside Encoder / Decoder on the bf16 MFMA kernels, f32
         master weights, gradients, statistics, latent, reconstruction and losses.  fp16 is not offered (no loss scaler here).
         perceptual_precision: 32 or "bf16" for the LPIPS-style net of the loss (LPIPSStyle.set_precision); None leaves it as it is -- f32
-        unless ODVAE_LPIPS_BF16=1, with which `precision` takes the perceptual net along."""
+        unless ODVAE_LPIPS_BF16=1, with which `precision` takes the perceptual net along.
+        discriminator_precision: the same for the loss's PatchGAN discriminator (NLayerDiscriminator.set_precision) and ODVAE_DISC_BF16=1."""
         p = str(precision).lower()
         if p in ("32", "32-true", "fp32"):
             dt = torch.float32
@@ -76,6 +77,13 @@ class AutoencoderKL(LightningModule):
             lpips.set_precision(perceptual_precision)
         elif ops.LPIPS_BF16 and hasattr(lpips, "set_precision"):
             lpips.set_precision(precision)
+        disc = getattr(getattr(self, "loss", None), "discriminator", None)
+        if discriminator_precision is not None:
+            if not hasattr(disc, "set_precision"):
+                raise ValueError("discriminator_precision=%r: the loss has no discriminator" % (discriminator_precision,))
+            disc.set_precision(discriminator_precision)
+        elif ops.DISC_BF16 and hasattr(disc, "set_precision"):
+            disc.set_precision(precision)
         return self
 
     def init_from_ckpt(self, path, ignore_keys=list()):

@@ -6,6 +6,12 @@
 //   MODE 2  Upsample: nearest 2x + 3x3 stride 1 (the 4x intermediate is never formed: the gather reads x[y>>1][x>>1])
 //   MODE 3  data gradient of MODE 1 (stride-2 transposed conv; taps that would hit an inserted zero are masked)
 //   MODE 4  1x1 (nin_shortcut, AttnBlock q/k/v/proj_out, and their data gradients): pixels flattened to [M/16][16]
+// and the PatchGAN discriminator's Conv2d(k=4, pad=1) ([UPSTREAM] taming/modules/discriminator/model.py), 16 taps, no cols matrix:
+//   MODE 5  4x4 stride 1, pad p.pad: 1 = forward (Ho = Hi - 1), 2 with the flipped pack = its data gradient (Ho = Hi + 1)
+//   MODE 6  4x4 stride 2 pad 1 (Ho = (Hi - 2) / 2 + 1; an odd Hi leaves the last padded row unused)
+//   MODE 7  data gradient of MODE 6 (transposed conv).  An input pixel receives the 2x2 taps of its row / column parity; the 8x16 tile
+//           is ordered so that each of its four 32-pixel MFMA tiles holds ONE parity class (one wave each), and a wave walks only its
+//           class's four taps of the flipped pack: no masked tap, every issued MFMA is useful work
 // [UPSTREAM] ldm/modules/diffusionmodules/model.py via src/modules/autoencodermodules/feat_encoder.py:4, feat_decoder.py:4.
 //
 // Implicit GEMM with the OUTPUT CHANNEL on the MFMA row and the PIXEL on the lane:  D[co][px] += W[co][ci] * X[ci][px].
@@ -33,6 +39,8 @@ struct ConvB {
   float* gn_partial;       // STATS launches: [N][tiles per image][gn_groups][2] = (sum, sum of squares) of y per tile and channel group
   int gn_groups, gn_cpg;   // channel groups of the GroupNorm that reads y; channels per group (a multiple of 4, <= 128)
   const bf16_t* mask;      // MASK launches: [N][Ho][Wo][Cout] bf16, the stored ReLU output of the layer below
+  int pad;                 // MODE 5: 1 or 2
+  float slope;             // LRELU launches: the LeakyReLU slope
 };
 
 template <int MODE, int TH> struct HaloB;
@@ -41,6 +49,9 @@ template <int TH> struct HaloB<1, TH> { static constexpr int H = 2 * TH + 1, W =
 template <int TH> struct HaloB<2, TH> { static constexpr int H = TH / 2 + 2, W = TW / 2 + 2, TAPS = 9; };
 template <int TH> struct HaloB<3, TH> { static constexpr int H = TH / 2 + 1, W = TW / 2 + 1, TAPS = 9; };
 template <int TH> struct HaloB<4, TH> { static constexpr int H = TH, W = TW, TAPS = 1; };
+template <int TH> struct HaloB<5, TH> { static constexpr int H = TH + 3, W = TW + 3, TAPS = 16; };
+template <int TH> struct HaloB<6, TH> { static constexpr int H = 2 * TH + 2, W = 2 * TW + 2, TAPS = 16; };
+template <int TH> struct HaloB<7, TH> { static constexpr int H = TH / 2 + 2, W = TW / 2 + 2, TAPS = 4; };   // taps per parity class
 
 template <int MODE, int TH>
 __device__ __forceinline__ int halo_index_b(int r, int c, int kh, int kw, bool& ok) {
@@ -49,12 +60,17 @@ __device__ __forceinline__ int halo_index_b(int r, int c, int kh, int kw, bool& 
   if (MODE == 1) return (2 * r + kh) * HaloB<1, TH>::W + (2 * c + kw);
   if (MODE == 2) return ((r + kh + 1) >> 1) * HaloB<2, TH>::W + ((c + kw + 1) >> 1);
   if (MODE == 4) return r * TW + c;
+  if (MODE == 5) return (r + kh) * HaloB<5, TH>::W + (c + kw);
+  if (MODE == 6) return (2 * r + kh) * HaloB<6, TH>::W + (2 * c + kw);
+  if (MODE == 7) return (((r + 1) >> 1) + kh) * HaloB<7, TH>::W + (((c + 1) >> 1) + kw);   // kh, kw in {0, 1}: the class's 2x2 taps
   ok = (((r + kh) | (c + kw)) & 1) == 0;
   return ((r + kh) >> 1) * HaloB<3, TH>::W + ((c + kw) >> 1);
 }
 template <int MODE>
-__device__ __forceinline__ void halo_origin_b(int oy0, int ox0, int& iy0, int& ix0) {
-  if (MODE == 0) { iy0 = oy0 - 1; ix0 = ox0 - 1; }
+__device__ __forceinline__ void halo_origin_b(int oy0, int ox0, int pad, int& iy0, int& ix0) {
+  if (MODE == 5) { iy0 = oy0 - pad; ix0 = ox0 - pad; }
+  else if (MODE == 6) { iy0 = 2 * oy0 - 1; ix0 = 2 * ox0 - 1; }
+  else if (MODE == 0) { iy0 = oy0 - 1; ix0 = ox0 - 1; }
   else if (MODE == 1) { iy0 = 2 * oy0; ix0 = 2 * ox0; }
   else if (MODE == 4) { iy0 = oy0; ix0 = ox0; }
   else { iy0 = oy0 / 2 - 1; ix0 = ox0 / 2 - 1; }
@@ -70,8 +86,10 @@ __device__ __forceinline__ void halo_origin_b(int oy0, int ox0, int& iy0, int& i
 // RELU / MASK (stride-1 3x3, bf16 output; the frozen VGG stack of the perceptual loss): RELU stores max(acc, 0), taken on the f32 accumulator
 // in front of the one rounding, with a NaN accumulator kept; MASK -- a data-gradient launch -- stores `mask > 0 ? acc : 0`, mask being the
 // stored ReLU output of the layer below, so what reaches HBM is the gradient at that layer's pre-activation and no dy * (y > 0) pass runs.
+// LRELU (MODE 6, bf16 output; the discriminator's first layer): stores acc > 0 ? acc : slope * acc, taken on the f32 accumulator in
+// front of the one rounding; a NaN accumulator stays a NaN.
 template <int MODE, int KC, int WCT, int WPT, int WAVES_CO, int WAVES_PX, int TH, int MINW = 1, bool STATS = false, bool RELU = false,
-          bool MASK = false>
+          bool MASK = false, bool LRELU = false>
 __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
   static_assert(WAVES_CO * WAVES_PX == 4 && WAVES_PX * WPT * 32 == TH * TW, "tile layout");
   constexpr int BCO = WAVES_CO * WCT * 32;
@@ -81,6 +99,8 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
   constexpr int HALO_V = HPIX * VC;
   constexpr int HALO_IT = (HALO_V + 255) / 256;
   constexpr int TAPS = HaloB<MODE, TH>::TAPS;
+  constexpr int PTAPS = MODE == 7 ? 16 : TAPS;         // taps of the pack
+  constexpr int KW = MODE == 7 ? 2 : (TAPS == 16 ? 4 : 3);
   constexpr int KS = KC / 16;                          // MFMA k-steps per tap and chunk
   constexpr int NIT = TAPS * KS;
   extern __shared__ __attribute__((aligned(16))) bf16_t smem[];   // 2 * HPIX * HS bf16 (two halo stages; 93 KB in the wide form)
@@ -95,11 +115,13 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
   const int oy0 = ty * TH, ox0 = tx * TW;
   const int co0 = blockIdx.y * BCO;
   int iy0, ix0;
-  halo_origin_b<MODE>(oy0, ox0, iy0, ix0);
+  halo_origin_b<MODE>(oy0, ox0, p.pad, iy0, ix0);
   static_assert(MODE == 0 || MODE == 4 || TH == 8, "the wide tile is only built for modes 0 and 4");
   static_assert(!(RELU || MASK) || (MODE == 0 && !STATS && !(RELU && MASK)), "ReLU / mask epilogues: stride-1 3x3 only, one at a time");
+  static_assert(!LRELU || (MODE == 6 && !STATS && !RELU && !MASK), "LeakyReLU epilogue: the stride-2 4x4 conv only");
+  static_assert(MODE != 7 || (WPT == 1 && WAVES_PX == 4), "MODE 7: one parity class per wave");
 
-  const int esz = (!(RELU || MASK) && p.out_f32) ? 4 : 2;
+  const int esz = (!(RELU || MASK || LRELU) && p.out_f32) ? 4 : 2;
   const unsigned OOB = 0x7FFFFFF0u;
   // this lane's pixel in each of its pixel tiles (column of the MFMA result)
   unsigned pixoff[WPT];      // element offset of the output pixel, or OOB
@@ -107,7 +129,8 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
 #pragma unroll
   for (int pt = 0; pt < WPT; ++pt) {
     const int pm = (wpx * WPT + pt) * 32 + li;
-    prr[pt] = pm / TW; pcc[pt] = pm % TW;
+    if (MODE == 7) { prr[pt] = 2 * ((pm & 31) >> 3) + (pm >> 6); pcc[pt] = 2 * (pm & 7) + ((pm >> 5) & 1); }   // class = pm >> 5 = (row parity, column parity)
+    else { prr[pt] = pm / TW; pcc[pt] = pm % TW; }
     const int oy = oy0 + prr[pt], ox = ox0 + pcc[pt];
     pixoff[pt] = (oy < p.Ho && ox < p.Wo) ? (unsigned)((oy * p.Wo + ox) * p.Cout) : OOB;
   }
@@ -183,19 +206,21 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
   // those and waits vmcnt(0) at every join).
   const int KT = p.CinP / 16, CT = p.CoutP / 32;
   const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(p.wpk), 0, TAPS * KT * CT * 1024, 0x00020000);
+      const_cast<bf16_t*>(p.wpk), 0, PTAPS * KT * CT * 1024, 0x00020000);
   const int ct0 = co0 / 32 + wco * WCT;
   const unsigned lane16 = lane * 16;
   auto load_a = [&](int ch, int it, bf16x8 (&a)[WCT]) {   // step `it` of chunk `ch`; it >= NIT runs into chunk ch + 1
     const int c2 = ch + it / NIT, i2 = it % NIT;
-    const int tap = i2 / KS, ks = i2 % KS;
+    const int ks = i2 % KS;
+    int tap = i2 / KS;
+    if (MODE == 7) tap = ((wpx >> 1) + 2 * (tap >> 1)) * 4 + (wpx & 1) + 2 * (tap & 1);   // flipped-pack tap (py + 2a, px + 2b) of this wave's class
     const unsigned base = (unsigned)(((tap * KT + c2 * KS + ks) * CT + ct0) * 1024) + lane16;
 #pragma unroll
     for (int ct = 0; ct < WCT; ++ct) a[ct] = frag_from_u32x4(__builtin_amdgcn_raw_buffer_load_b128(wrsrc, base + ct * 1024, 0, 0));
   };
   auto load_b = [&](const bf16_t* Hs, int it, bf16x8 (&b)[WPT]) {
     const int tap = it / KS, ks = it % KS;
-    const int kh = TAPS == 1 ? 0 : tap / 3, kw = TAPS == 1 ? 0 : tap % 3;
+    const int kh = TAPS == 1 ? 0 : tap / KW, kw = TAPS == 1 ? 0 : tap % KW;
 #pragma unroll
     for (int pt = 0; pt < WPT; ++pt) {
       bool ok;
@@ -210,7 +235,7 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
   // step ahead (LDS); no rotation copies.  NIT % RA == 0 keeps the weight slots the same in every chunk.
   constexpr int RA = (NIT % 3 == 0) ? 3 : 2, PA = RA - 1;
   static_assert(NIT % RA == 0, "weight ring");
-  const int nchunks = p.CinP / KC;
+  const int nchunks = MODE >= 5 ? (p.Cin + KC - 1) / KC : p.CinP / KC;   // (4x4: the 8-channel image is one chunk, not CinP = 32)
   bf16x8 abuf[RA][WCT], bbuf[2][WPT];
   load_halo(0);
 #pragma unroll
@@ -258,7 +283,7 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
       const int co = co0 + (wco * WCT + ct) * 32 + 8 * g + 4 * h;
 #pragma unroll
       for (int pt = 0; pt < WPT; ++pt) {
-        if (!(RELU || MASK) && p.out_f32) {   // (the ReLU / mask builds write bf16 only: without this branch they keep the plain build's registers)
+        if (!(RELU || MASK || LRELU) && p.out_f32) {   // (the ReLU / mask builds write bf16 only: without this branch they keep the plain build's registers)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const unsigned off = (pixoff[pt] != OOB && co + j < p.Cout) ? (pixoff[pt] + (unsigned)(co + j)) * 4u : OOB;
@@ -270,6 +295,10 @@ __global__ __launch_bounds__(256, MINW) void conv_bf16_kernel(ConvB p) {
           if (RELU) {       // (a <= 0 is false for a NaN: it stays, as in torch.relu; -0 becomes +0)
 #pragma unroll
             for (int j = 0; j < 4; ++j) a4[j] = a4[j] <= 0.f ? 0.f : a4[j];
+          }
+          if (LRELU) {      // (a > 0 is false for a NaN: slope * NaN stays a NaN)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a4[j] = a4[j] > 0.f ? a4[j] : p.slope * a4[j];
           }
           if (MASK) {
             const u32x2 m = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(mrsrc, off, 0, 0));
@@ -357,16 +386,17 @@ __global__ void conv_pack_bf16_kernel(const float* __restrict__ w, int Cout, int
 int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 
 template <int MODE, int KC, int WCT, int WPT, int WAVES_CO, int WAVES_PX, int TH, int MINW = 1, bool STATS = false, bool RELU = false,
-          bool MASK = false>
+          bool MASK = false, bool LRELU = false>
 void launch_cfg(const ConvB& p, dim3 grid, hipStream_t st) {
+  static_assert(2 * HaloB<MODE, TH>::H * HaloB<MODE, TH>::W * (KC + 8) * 2 <= 160 * 1024, "two halo stages exceed the LDS");
   constexpr int bytes = 2 * HaloB<MODE, TH>::H * HaloB<MODE, TH>::W * (KC + 8) * 2;
   static bool once = false;
   if (!once) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MODE, KC, WCT, WPT, WAVES_CO, WAVES_PX, TH, MINW, STATS, RELU, MASK>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MODE, KC, WCT, WPT, WAVES_CO, WAVES_PX, TH, MINW, STATS, RELU, MASK, LRELU>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     once = true;
   }
-  hipLaunchKernelGGL((conv_bf16_kernel<MODE, KC, WCT, WPT, WAVES_CO, WAVES_PX, TH, MINW, STATS, RELU, MASK>), grid, dim3(256), bytes, st, p);
+  hipLaunchKernelGGL((conv_bf16_kernel<MODE, KC, WCT, WPT, WAVES_CO, WAVES_PX, TH, MINW, STATS, RELU, MASK, LRELU>), grid, dim3(256), bytes, st, p);
 }
 
 template <int MODE, int KC>
@@ -382,6 +412,23 @@ void launch_by_cout(ConvB& p, hipStream_t st) {
   if (p.Cout > 64)      launch_cfg<MODE, KC, 2, 2, 2, 2, 8, MW>(p, dim3(tiles, ceil_div(p.Cout, 128)), st);
   else if (p.Cout > 32) launch_cfg<MODE, KC, 2, 1, 1, 4, 8>(p, dim3(tiles, 1), st);
   else                  launch_cfg<MODE, KC, 1, 1, 1, 4, 8>(p, dim3(tiles, 1), st);
+}
+
+// MODE 7: one pixel tile (parity class) per wave, 32 * WCT output channels per block
+template <int KC>
+void launch_mode7(ConvB& p, hipStream_t st) {
+  const int tiles = p.N * p.tiles_x * p.tiles_y;
+  if (p.Cout > 64)      launch_cfg<7, KC, 4, 1, 1, 4, 8>(p, dim3(tiles, ceil_div(p.Cout, 128)), st);
+  else if (p.Cout > 32) launch_cfg<7, KC, 2, 1, 1, 4, 8>(p, dim3(tiles, 1), st);
+  else                  launch_cfg<7, KC, 1, 1, 1, 4, 8>(p, dim3(tiles, 1), st);
+}
+
+// MODE 6 with the LeakyReLU epilogue (bf16 output)
+void launch_lrelu6(ConvB& p, hipStream_t st) {
+  const int tiles = p.N * p.tiles_x * p.tiles_y;
+  if (p.Cout > 64)      launch_cfg<6, 16, 2, 2, 2, 2, 8, 1, false, false, false, true>(p, dim3(tiles, ceil_div(p.Cout, 128)), st);
+  else if (p.Cout > 32) launch_cfg<6, 16, 2, 1, 1, 4, 8, 1, false, false, false, true>(p, dim3(tiles, 1), st);
+  else                  launch_cfg<6, 16, 1, 1, 1, 4, 8, 1, false, false, false, true>(p, dim3(tiles, 1), st);
 }
 
 // The stride-1 3x3 conv with a ReLU (EPI 1) or a mask (EPI 2) epilogue: the shapes of the VGG stack, more than 32 output channels
@@ -403,10 +450,10 @@ size_t odvae_conv_bf16_pack_elems(int reduce_c, int out_c, int taps) {
   return (size_t)taps * odvae_conv_bf16_reduce_pad(reduce_c) * odvae_conv_bf16_out_pad(out_c);
 }
 
-// w: OIHW f32 [Cout][Cin][k][k], taps = k*k in {1, 9}.  fwd_pack / dgrad_pack: bf16, odvae_conv_bf16_pack_elems(Cin, Cout, taps) /
+// w: OIHW f32 [Cout][Cin][k][k], taps = k*k in {1, 9, 16}.  fwd_pack / dgrad_pack: bf16, odvae_conv_bf16_pack_elems(Cin, Cout, taps) /
 // (Cout, Cin, taps) elements; either may be NULL.
 int odvae_conv_pack_bf16(const float* w, int Cout, int Cin, int taps, void* fwd_pack, void* dgrad_pack, void* stream) {
-  ODVAE_CHECK_ARG(w && Cout > 0 && Cin > 0 && (taps == 1 || taps == 9), "conv_pack_bf16: bad arguments");
+  ODVAE_CHECK_ARG(w && Cout > 0 && Cin > 0 && (taps == 1 || taps == 9 || taps == 16), "conv_pack_bf16: bad arguments");
   const int64_t total = (fwd_pack ? (int64_t)odvae_conv_bf16_pack_elems(Cin, Cout, taps) : 0) +
                         (dgrad_pack ? (int64_t)odvae_conv_bf16_pack_elems(Cout, Cin, taps) : 0);
   if (total == 0) return ODVAE_OK;
@@ -424,10 +471,11 @@ int odvae_conv_pack_bf16(const float* w, int Cout, int Cin, int taps, void* fwd_
 // Cout % 4 == 0) or f32 (out_f32 = 1, any Cout).  mode 0..3 as in odvae_conv3x3_f32; mode 4 = 1x1 on [N][Hi][Wi] = [1][M/16][16].
 static int conv_bf16_impl(int mode, const void* x, int N, int Hi, int Wi, int Cin, const void* pack, int Cout, const float* bias,
                           const void* residual, void* y, int Ho, int Wo, int out_f32, float* gn_partial, int gn_groups, void* stream,
-                          int epi = 0, const void* mask = nullptr);
+                          int epi = 0, const void* mask = nullptr, int pad = 0, float slope = 0.f);
 
 int odvae_conv_bf16(int mode, const void* x, int N, int Hi, int Wi, int Cin, const void* pack, int Cout, const float* bias,
                     const void* residual, void* y, int Ho, int Wo, int out_f32, void* stream) {
+  ODVAE_CHECK_ARG(mode <= 4, "conv_bf16: mode %d (the 4x4 modes are odvae_conv4x4_bf16)", mode);
   return conv_bf16_impl(mode, x, N, Hi, Wi, Cin, pack, Cout, bias, residual, y, Ho, Wo, out_f32, nullptr, 0, stream);
 }
 
@@ -463,11 +511,27 @@ int odvae_conv_bf16_masked(const void* x, int N, int H, int W, int Cin, const vo
   return conv_bf16_impl(0, x, N, H, W, Cin, pack, Cout, nullptr, nullptr, y, H, W, 0, nullptr, 0, stream, 2, mask);
 }
 
+// The PatchGAN Conv2d(k=4, pad=1) and its data gradient as implicit GEMMs (no cols matrix).  dgrad = 0: y = conv(x) + bias, x bf16
+// [N][Hi][Wi][Cin], Ho = (Hi - 2) / stride + 1, pack = the forward pack of odvae_conv_pack_bf16(taps = 16); lrelu_slope != 0 (stride 2,
+// bf16 output): y = leaky_relu(conv(x) + bias) with one rounding.  dgrad = 1: x is dy [N][Hi][Wi][Cin = the conv's Cout], pack the
+// data-gradient pack, y = dx [N][Ho][Wo][Cout = the conv's Cin] with (Ho - 2) / stride + 1 == Hi (stride 1: Ho = Hi + 1); rows and
+// columns of dx that no window reads come out 0.  y bf16 (Cout % 4 == 0) or f32 (out_f32 = 1, any Cout >= 1).
+int odvae_conv4x4_bf16(int stride, int dgrad, const void* x, int N, int Hi, int Wi, int Cin, const void* pack, int Cout, const float* bias,
+                       void* y, int Ho, int Wo, int out_f32, float lrelu_slope, void* stream) {
+  ODVAE_CHECK_ARG(stride == 1 || stride == 2, "conv4x4_bf16: stride %d", stride);
+  ODVAE_CHECK_ARG(lrelu_slope == 0.f || (stride == 2 && !dgrad && !out_f32), "conv4x4_bf16: the LeakyReLU epilogue is built for the stride-2 forward with a bf16 output");
+  ODVAE_CHECK_ARG(!dgrad || !bias, "conv4x4_bf16: a data gradient takes no bias");
+  const int mode = stride == 1 ? 5 : (dgrad ? 7 : 6);
+  return conv_bf16_impl(mode, x, N, Hi, Wi, Cin, pack, Cout, bias, nullptr, y, Ho, Wo, out_f32, nullptr, 0, stream,
+                        lrelu_slope != 0.f ? 3 : 0, nullptr, dgrad ? 2 : 1, lrelu_slope);
+}
+
 static int conv_bf16_impl(int mode, const void* x, int N, int Hi, int Wi, int Cin, const void* pack, int Cout, const float* bias,
                           const void* residual, void* y, int Ho, int Wo, int out_f32, float* gn_partial, int gn_groups, void* stream,
-                          int epi, const void* mask) {
-  ODVAE_CHECK_ARG(epi == 0 || (mode == 0 && !out_f32 && Cout > 32), "conv_bf16: the ReLU / mask epilogues need Cout > 32, got %d", Cout);
-  ODVAE_CHECK_ARG(mode >= 0 && mode <= 4, "conv_bf16: mode %d", mode);
+                          int epi, const void* mask, int pad, float slope) {
+  ODVAE_CHECK_ARG(epi == 0 || (mode == 0 && !out_f32 && Cout > 32) || (epi == 3 && mode == 6 && !out_f32),
+                  "conv_bf16: the ReLU / mask epilogues need Cout > 32, got %d", Cout);
+  ODVAE_CHECK_ARG(mode >= 0 && mode <= 7, "conv_bf16: mode %d", mode);
   ODVAE_CHECK_ARG(x && pack && y && N > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "conv_bf16: null or empty operand");
   ODVAE_CHECK_ARG(Cin % 8 == 0, "conv_bf16: Cin = %d must be a multiple of 8 (16-byte channel vectors)", Cin);
   ODVAE_CHECK_ARG(out_f32 || Cout % 4 == 0, "conv_bf16: bf16 output needs Cout %% 4 == 0, got %d", Cout);
@@ -477,8 +541,11 @@ static int conv_bf16_impl(int mode, const void* x, int N, int Hi, int Wi, int Ci
   int eh, ew;
   if (mode == 0 || mode == 4) { eh = Hi; ew = Wi; }
   else if (mode == 1) { eh = (Hi - 2) / 2 + 1; ew = (Wi - 2) / 2 + 1; }   // (H + 1 - 3)/2 + 1 with the (0,1,0,1) pad
+  else if (mode == 5) { eh = Hi + 2 * pad - 3; ew = Wi + 2 * pad - 3; }
+  else if (mode == 6) { eh = Hi >= 2 ? (Hi - 2) / 2 + 1 : -1; ew = Wi >= 2 ? (Wi - 2) / 2 + 1 : -1; }
+  else if (mode == 7) { eh = (Ho >= 2 && (Ho - 2) / 2 + 1 == Hi) ? Ho : -1; ew = (Wo >= 2 && (Wo - 2) / 2 + 1 == Wi) ? Wo : -1; }
   else { eh = 2 * Hi; ew = 2 * Wi; }
-  ODVAE_CHECK_ARG(Ho == eh && Wo == ew, "conv_bf16(mode %d): output %dx%d does not match input %dx%d (expected %dx%d)", mode, Ho, Wo, Hi, Wi, eh, ew);
+  ODVAE_CHECK_ARG(eh > 0 && ew > 0 && Ho == eh && Wo == ew, "conv_bf16(mode %d): output %dx%d does not match input %dx%d (expected %dx%d)", mode, Ho, Wo, Hi, Wi, eh, ew);
   ODVAE_CHECK_ARG((int64_t)Hi * Wi * Cin * 2 <= 0x7FFFFFF0ll && (int64_t)Ho * Wo * Cout * (out_f32 ? 4 : 2) <= 0x7FFFFFF0ll,
                   "conv_bf16: one image exceeds the 2 GiB buffer-descriptor range");
   ConvB p;
@@ -490,11 +557,13 @@ static int conv_bf16_impl(int mode, const void* x, int N, int Hi, int Wi, int Ci
   p.gn_partial = gn_partial; p.gn_groups = gn_groups; p.gn_cpg = gn_groups > 0 ? Cout / gn_groups : 0;
   p.xcd = 1;
   p.mask = static_cast<const bf16_t*>(mask);
+  p.pad = pad; p.slope = slope;
   ODVAE_CHECK_ARG((int64_t)N * p.tiles_x * p.tiles_y < 0x7FFFFFFFll, "conv_bf16: too many tiles");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool k64 = p.CinP % 64 == 0;
   if (epi == 1) { if (k64) launch_epi<64, 1>(p, st); else launch_epi<32, 1>(p, st); }
   else if (epi == 2) { if (k64) launch_epi<64, 2>(p, st); else launch_epi<32, 2>(p, st); }
+  else if (epi == 3) launch_lrelu6(p, st);
   else switch (mode) {
     // (32-channel chunks at three blocks per CU -- __launch_bounds__(256, 3): 168 registers, 29 KB of LDS -- measured the same as
     // 64-channel chunks at two blocks per CU: 747 vs 740 TFLOP/s at 128 channels, B=32)
@@ -502,6 +571,9 @@ static int conv_bf16_impl(int mode, const void* x, int N, int Hi, int Wi, int Ci
     case 1: launch_by_cout<1, 16>(p, st); break;   // 17x33 halo pixels: KC = 16 keeps the two stages under 64 KB
     case 2: launch_by_cout<2, 32>(p, st); break;
     case 3: launch_by_cout<3, 32>(p, st); break;
+    case 5: if (k64) launch_by_cout<5, 64>(p, st); else launch_by_cout<5, 32>(p, st); break;
+    case 6: launch_by_cout<6, 16>(p, st); break;   // 18x34 halo pixels: two stages of 16 channels are 59 KB
+    case 7: if (k64) launch_mode7<64>(p, st); else launch_mode7<32>(p, st); break;
     default: if (k64) launch_by_cout<4, 64>(p, st); else launch_by_cout<4, 32>(p, st); break;
   }
   ODVAE_LAUNCH_CHECK("conv_bf16");

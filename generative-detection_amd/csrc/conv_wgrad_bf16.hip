@@ -10,6 +10,9 @@
 //   A = dy^T (rows = co), B = x (cols = ci), D[co][ci] per tap: 9 accumulator tiles per wave (144 registers).
 // Block = COT x CIT waves (one 32-co x 32-ci tile each, all taps), looping over its share of the 8x16 (4x16 for Downsample)
 // output-pixel tiles: next tile's dy rows and x halo are fetched into registers while the current one is multiplied.
+// Modes 5 / 6: the PatchGAN Conv2d(k=4, pad=1) at stride 1 / 2 (16 taps).  Sixteen accumulator tiles do not fit a wave's registers
+// next to the fragments, so a block takes one HALF of the taps (kernel rows 0-1 or 2-3: 8 tiles, 128 registers) and the halves are two
+// blocks of the grid's z dimension; each stages the same tiles.
 // Partial sums go to f32 slabs [split][tap][co][ci]; a second kernel adds the slabs in fixed order (deterministic) into OIHW.
 #include "bf16_common.h"
 
@@ -31,12 +34,16 @@ template <int TH> struct HaloW<0, TH> { static constexpr int H = TH + 2, W = TW 
 template <int TH> struct HaloW<1, TH> { static constexpr int H = 2 * TH + 1, W = 2 * TW + 1, TAPS = 9; };
 template <int TH> struct HaloW<2, TH> { static constexpr int H = TH / 2 + 2, W = TW / 2 + 2, TAPS = 9; };
 template <int TH> struct HaloW<4, TH> { static constexpr int H = TH, W = TW, TAPS = 1; };
+template <int TH> struct HaloW<5, TH> { static constexpr int H = TH + 3, W = TW + 3, TAPS = 16; };
+template <int TH> struct HaloW<6, TH> { static constexpr int H = 2 * TH + 2, W = 2 * TW + 2, TAPS = 16; };
 
 template <int MODE, int TH>
 __device__ __forceinline__ int halo_index_w(int r, int c, int kh, int kw) {
   if (MODE == 0) return (r + kh) * HaloW<0, TH>::W + (c + kw);
   if (MODE == 1) return (2 * r + kh) * HaloW<1, TH>::W + (2 * c + kw);
   if (MODE == 2) return ((r + kh + 1) >> 1) * HaloW<2, TH>::W + ((c + kw + 1) >> 1);
+  if (MODE == 5) return (r + kh) * HaloW<5, TH>::W + (c + kw);
+  if (MODE == 6) return (2 * r + kh) * HaloW<6, TH>::W + (2 * c + kw);
   return r * TW + c;
 }
 
@@ -46,7 +53,8 @@ __global__ __launch_bounds__(COT * CIT * 64) void conv_wgrad_bf16_kernel(WgradB 
   constexpr int BCO = COT * 32, BCI = CIT * 32;
   constexpr int DS = BCO + 32, XS = BCI + 32;          // LDS row strides (bf16): + 64 bytes keeps the transposed reads conflict-free
   constexpr int HPIX = HaloW<MODE, TH>::H * HaloW<MODE, TH>::W;
-  constexpr int TAPS = HaloW<MODE, TH>::TAPS;
+  constexpr int ALLTAPS = HaloW<MODE, TH>::TAPS;
+  constexpr int TAPS = ALLTAPS == 16 ? 8 : ALLTAPS;    // taps of this block: 16-tap kernels are walked in two halves (blockIdx.z & 1)
   constexpr int TPX = TH * TW;
   constexpr int DV = TPX * (BCO / 8), XV = HPIX * (BCI / 8);    // 16-byte vectors per stage
   constexpr int D_IT = (DV + NT - 1) / NT, X_IT = (XV + NT - 1) / NT;
@@ -56,7 +64,8 @@ __global__ __launch_bounds__(COT * CIT * 64) void conv_wgrad_bf16_kernel(WgradB 
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int cot = wave % COT, cit = wave / COT;
-  const int co0 = blockIdx.y * BCO, ci0 = blockIdx.z * BCI;
+  const int half = ALLTAPS == 16 ? (int)(blockIdx.z & 1) : 0;
+  const int co0 = blockIdx.y * BCO, ci0 = (ALLTAPS == 16 ? blockIdx.z >> 1 : blockIdx.z) * BCI;
   const unsigned OOB = 0x7FFFFFF0u;
 
   f32x16 acc[TAPS];
@@ -99,6 +108,8 @@ __global__ __launch_bounds__(COT * CIT * 64) void conv_wgrad_bf16_kernel(WgradB 
     if (MODE == 0) { iy0 = oy0 - 1; ix0 = ox0 - 1; }
     else if (MODE == 1) { iy0 = 2 * oy0; ix0 = 2 * ox0; }
     else if (MODE == 4) { iy0 = oy0; ix0 = ox0; }
+    else if (MODE == 5) { iy0 = oy0 - 1; ix0 = ox0 - 1; }
+    else if (MODE == 6) { iy0 = 2 * oy0 - 1; ix0 = 2 * ox0 - 1; }
     else { iy0 = oy0 / 2 - 1; ix0 = ox0 / 2 - 1; }
     const __amdgpu_buffer_rsrc_t drsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<bf16_t*>(p.dy + (int64_t)n * p.Ho * p.Wo * p.Cout), 0, p.Ho * p.Wo * p.Cout * 2, 0x00020000);
@@ -137,6 +148,8 @@ __global__ __launch_bounds__(COT * CIT * 64) void conv_wgrad_bf16_kernel(WgradB 
   const int dcol = cot * 32 + 16 * (g & 1) + 4 * pp;    // dy channel column this lane addresses
   const int xcol = cit * 32 + 16 * (g & 1) + 4 * pp;
 
+  // the second tap half (kernel rows 2, 3) reads the same halo two rows (stride 2: two halo rows) further down
+  const bf16_t* Xh = Xs + (ALLTAPS == 16 ? half * 2 * HaloW<MODE, TH>::W * XS : 0);
   int tile = blockIdx.x;
   if (tile < p.ntiles) fetch(tile);
   for (; tile < p.ntiles; tile += p.splits) {
@@ -150,9 +163,9 @@ __global__ __launch_bounds__(COT * CIT * 64) void conv_wgrad_bf16_kernel(WgradB 
       if (do_bias) bacc = mfma_bf16(a, ones, bacc);   // wave-uniform; every column of bacc = sum over the 16 pixels of dy^T rows
 #pragma unroll
       for (int t = 0; t < TAPS; ++t) {
-        const int kh = TAPS == 1 ? 0 : t / 3, kw = TAPS == 1 ? 0 : t % 3;
-        const bf16x8 b = frag_from_tr(lds_read_tr16(Xs + halo_index_w<MODE, TH>(r, c_lo, kh, kw) * XS + xcol),
-                                      lds_read_tr16(Xs + halo_index_w<MODE, TH>(r, c_hi, kh, kw) * XS + xcol));
+        const int kh = ALLTAPS == 16 ? t / 4 : (TAPS == 1 ? 0 : t / 3), kw = ALLTAPS == 16 ? t % 4 : (TAPS == 1 ? 0 : t % 3);
+        const bf16x8 b = frag_from_tr(lds_read_tr16(Xh + halo_index_w<MODE, TH>(r, c_lo, kh, kw) * XS + xcol),
+                                      lds_read_tr16(Xh + halo_index_w<MODE, TH>(r, c_hi, kh, kw) * XS + xcol));
         acc[t] = mfma_bf16(a, b, acc[t]);
       }
     }
@@ -160,7 +173,7 @@ __global__ __launch_bounds__(COT * CIT * 64) void conv_wgrad_bf16_kernel(WgradB 
   }
 
   // slab [split][tap][CoutP][CinP]: register i of lane (r, h) is dW[co = 32 cot + (i&3) + 8(i>>2) + 4h][ci = 32 cit + r]
-  float* slab = p.slab + (int64_t)blockIdx.x * TAPS * p.CoutP * p.CinP;
+  float* slab = p.slab + ((int64_t)blockIdx.x * ALLTAPS + half * TAPS) * p.CoutP * p.CinP;
   const int li = lane & 31, h = lane >> 5;
   if (do_bias && li == 0) {   // column 0 of the (all columns equal) sum tile: rows = channels
 #pragma unroll
@@ -209,6 +222,7 @@ __global__ void wgrad_bf16_reduce_kernel(const float* __restrict__ slab, int spl
 }
 
 int pad_to(int v, int m) { return (v + m - 1) / m * m; }
+int taps_of(int mode) { return mode == 4 ? 1 : (mode >= 5 ? 16 : 9); }
 
 template <int MODE, int TH, int COT, int CIT>
 void launch_wgrad(const WgradB& p, dim3 grid, hipStream_t st) {
@@ -225,8 +239,8 @@ void launch_wgrad(const WgradB& p, dim3 grid, hipStream_t st) {
 struct Plan { int CoutP, CinP, splits, ntiles, tiles_x, tiles_y, th, cot, cit; };
 
 bool make_plan(int mode, int N, int Ho, int Wo, int Cin, int Cout, Plan& pl) {
-  if (!(mode == 0 || mode == 1 || mode == 2 || mode == 4)) return false;
-  pl.th = mode == 1 ? 4 : 8;
+  if (!(mode == 0 || mode == 1 || mode == 2 || (mode >= 4 && mode <= 6))) return false;
+  pl.th = (mode == 1 || mode == 6) ? 4 : 8;
   pl.cot = Cout > 32 ? 4 : 1;
   pl.cit = Cout > 32 ? 2 : 4;
   pl.CoutP = pad_to(Cout, pl.cot * 32);
@@ -235,7 +249,7 @@ bool make_plan(int mode, int N, int Ho, int Wo, int Cin, int Cout, Plan& pl) {
   const int64_t nt = (int64_t)N * pl.tiles_x * pl.tiles_y;
   if (nt >= (1ll << 31)) return false;
   pl.ntiles = (int)nt;
-  const int pairs = (pl.CoutP / (pl.cot * 32)) * (pl.CinP / (pl.cit * 32));
+  const int pairs = (pl.CoutP / (pl.cot * 32)) * (pl.CinP / (pl.cit * 32)) * (mode >= 5 ? 2 : 1);   // (4x4: two tap halves per pair)
   int s = std::max(1, 256 / pairs);       // one 8-wave block per CU in a single round; fewer slabs for the reduce to read
   pl.splits = (int)std::min<int64_t>(s, nt);
   return true;
@@ -248,10 +262,19 @@ extern "C" {
 size_t odvae_conv_wgrad_bf16_workspace_bytes(int mode, int N, int Ho, int Wo, int Cin, int Cout) {
   Plan pl;
   if (!make_plan(mode, N, Ho, Wo, Cin, Cout, pl)) return 0;
-  return ((size_t)pl.splits * (mode == 4 ? 1 : 9) * pl.CoutP * pl.CinP + (size_t)pl.splits * pl.CoutP) * sizeof(float);
+  return ((size_t)pl.splits * taps_of(mode) * pl.CoutP * pl.CinP + (size_t)pl.splits * pl.CoutP) * sizeof(float);
 }
 
-// dw f32 OIHW [Cout][Cin][k][k] (k*k = 9, or 1 for mode 4) from x bf16 [N][Hi][Wi][Cin] and dy bf16 [N][Ho][Wo][Cout];
+// How the kernel divides the work (host only): out = {splits, output-pixel tiles, tile height, tile width}.  Block s of the split
+// dimension reduces tiles s, s + splits, ...: with tiles % splits != 0 the last splits walk one tile fewer.
+int odvae_conv_wgrad_bf16_plan(int mode, int N, int Ho, int Wo, int Cin, int Cout, int out[4]) {
+  Plan pl;
+  ODVAE_CHECK_ARG(out && N > 0 && Ho > 0 && Wo > 0 && Cin > 0 && Cout > 0 && make_plan(mode, N, Ho, Wo, Cin, Cout, pl), "conv_wgrad_bf16_plan: bad arguments");
+  out[0] = pl.splits; out[1] = pl.ntiles; out[2] = pl.th; out[3] = TW;
+  return ODVAE_OK;
+}
+
+// dw f32 OIHW [Cout][Cin][k][k] (k*k = 9, 1 for mode 4, 16 for modes 5 / 6 = Conv2d(k=4, pad=1) at stride 1 / 2) from x bf16 [N][Hi][Wi][Cin] and dy bf16 [N][Ho][Wo][Cout];
 // Cin % 8 == 0 and Cout % 8 == 0 (16-byte channel vectors).  db f32 [Cout] = per-channel sum of dy (bias gradient) or NULL: it rides
 // along in the same pass over dy.  Deterministic (fixed slab order).
 int odvae_conv_wgrad_bf16(int mode, const void* x, const void* dy, int N, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout,
@@ -263,8 +286,10 @@ int odvae_conv_wgrad_bf16(int mode, const void* x, const void* dy, int N, int Hi
   int eh, ew;
   if (mode == 0 || mode == 4) { eh = Hi; ew = Wi; }
   else if (mode == 1) { eh = (Hi - 2) / 2 + 1; ew = (Wi - 2) / 2 + 1; }
+  else if (mode == 5) { eh = Hi - 1; ew = Wi - 1; }
+  else if (mode == 6) { eh = Hi >= 2 ? (Hi - 2) / 2 + 1 : -1; ew = Wi >= 2 ? (Wi - 2) / 2 + 1 : -1; }
   else { eh = 2 * Hi; ew = 2 * Wi; }
-  ODVAE_CHECK_ARG(Ho == eh && Wo == ew, "conv_wgrad_bf16(mode %d): dy %dx%d does not match x %dx%d", mode, Ho, Wo, Hi, Wi);
+  ODVAE_CHECK_ARG(eh > 0 && ew > 0 && Ho == eh && Wo == ew, "conv_wgrad_bf16(mode %d): dy %dx%d does not match x %dx%d", mode, Ho, Wo, Hi, Wi);
   ODVAE_CHECK_ARG((int64_t)Hi * Wi * Cin * 2 < 0x7FFFFFF0ll && (int64_t)Ho * Wo * Cout * 2 < 0x7FFFFFF0ll,
                   "conv_wgrad_bf16: one image exceeds the 2 GiB buffer-descriptor range");
   ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0, "conv_wgrad_bf16: misaligned operand");
@@ -275,11 +300,11 @@ int odvae_conv_wgrad_bf16(int mode, const void* x, const void* dy, int N, int Hi
   }
   WgradB p;
   p.x = static_cast<const bf16_t*>(x); p.dy = static_cast<const bf16_t*>(dy); p.slab = static_cast<float*>(workspace);
-  p.bslab = db ? p.slab + (size_t)pl.splits * (mode == 4 ? 1 : 9) * pl.CoutP * pl.CinP : nullptr;
+  p.bslab = db ? p.slab + (size_t)pl.splits * taps_of(mode) * pl.CoutP * pl.CinP : nullptr;
   p.N = N; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.CinP = pl.CinP; p.CoutP = pl.CoutP;
   p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.ntiles = pl.ntiles; p.splits = pl.splits;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid(pl.splits, pl.CoutP / (pl.cot * 32), pl.CinP / (pl.cit * 32));
+  const dim3 grid(pl.splits, pl.CoutP / (pl.cot * 32), pl.CinP / (pl.cit * 32) * (mode >= 5 ? 2 : 1));
 #define ODVAE_WG(MODE, TH)                                                                                                 \
   if (pl.cot == 4) launch_wgrad<MODE, TH, 4, 2>(p, grid, st);                                                             \
   else launch_wgrad<MODE, TH, 1, 4>(p, grid, st)
@@ -287,11 +312,13 @@ int odvae_conv_wgrad_bf16(int mode, const void* x, const void* dy, int N, int Hi
     case 0: ODVAE_WG(0, 8); break;
     case 1: ODVAE_WG(1, 4); break;
     case 2: ODVAE_WG(2, 8); break;
+    case 5: ODVAE_WG(5, 8); break;
+    case 6: ODVAE_WG(6, 4); break;
     default: ODVAE_WG(4, 8); break;
   }
 #undef ODVAE_WG
   ODVAE_LAUNCH_CHECK("conv_wgrad_bf16");
-  const int taps = mode == 4 ? 1 : 9;
+  const int taps = taps_of(mode);
   const int64_t per = (int64_t)taps * pl.CoutP * pl.CinP;
   hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(per, 256), 4096)), dim3(256), 0, st,
                      p.slab, pl.splits, taps, Cout, Cin, pl.CoutP, pl.CinP, dw, p.bslab, db);

@@ -37,8 +37,12 @@ class Conv4x4(nn.Conv2d):
 
     def __init__(self, cin, cout, stride, bias=True):
         super().__init__(cin, cout, kernel_size=4, stride=stride, padding=1, bias=bias)
+        self.compute_dtype = torch.float32     # NLayerDiscriminator.set_precision
+        self.fused_lrelu = None                # bf16 only: slope of the LeakyReLU that rides in this conv's epilogue
 
     def forward(self, x):
+        if self.compute_dtype == torch.bfloat16:
+            return ops.conv4x4_bf16(x, self.weight, self.bias, self.stride[0], lrelu=self.fused_lrelu)
         return ops.conv4x4(x, self.weight, self.bias, self.stride[0])
 
 
@@ -103,7 +107,11 @@ class ActNormLReLU(nn.Module):
 
 
 class LeakyReLU(nn.LeakyReLU):
+    fused = False      # bf16 discriminator: applied in the epilogue of the conv in front (NLayerDiscriminator.set_precision)
+
     def forward(self, x):
+        if self.fused:
+            return x
         return ops.leaky_relu(x, self.negative_slope)
 
 
@@ -125,9 +133,38 @@ class NLayerDiscriminator(nn.Module):
         seq += [Conv4x4(ndf * prev, ndf * mult, 1, bias=use_bias), norm(ndf * mult), _Fused()]
         seq += [Conv4x4(ndf * mult, 1, 1, bias=True)]
         self.main = nn.Sequential(*seq)
+        self.use_actnorm = bool(use_actnorm)
+        self.compute_dtype = torch.float32     # see set_precision
 
     def forward(self, input):
         return self.main(input)
+
+    def set_precision(self, precision):
+        """32 (default) or "bf16": the 4x4 convolutions as implicit GEMMs on the bf16 MFMA kernels (no cols matrix), bf16 activations, the
+        first layer's LeakyReLU in its conv's epilogue, BatchNorm + LeakyReLU on the bf16 kernels with f32 statistics, f32 logits -- what
+        torch.autocast makes of the discriminator under the reference's `precision: bf16`.  The f32 image goes in and its f32 gradient
+        comes out.  Parameters, buffers and the state_dict stay f32."""
+        p = str(precision).lower()
+        if p in ("32", "32-true", "fp32"):
+            dt = torch.float32
+        elif p in ("bf16", "bf16-mixed"):
+            dt = torch.bfloat16
+        else:
+            raise ValueError("precision %r: the discriminator computes in 32 (f32) or bf16" % (precision,))
+        if dt == torch.bfloat16 and self.use_actnorm:
+            raise ValueError("precision %r with use_actnorm=True: there are no bf16 ActNorm + LeakyReLU kernels (only the BatchNorm "
+                             "discriminator runs in bf16); keep this discriminator at 32" % (precision,))
+        mods = list(self.main)
+        for i, m in enumerate(mods):
+            if isinstance(m, Conv4x4):
+                nxt = mods[i + 1] if i + 1 < len(mods) else None
+                fuse = dt == torch.bfloat16 and isinstance(nxt, LeakyReLU) and m.stride[0] == 2 and m.out_channels % 8 == 0
+                m.compute_dtype = dt
+                m.fused_lrelu = nxt.negative_slope if fuse else None
+                if isinstance(nxt, LeakyReLU):
+                    nxt.fused = fuse
+        self.compute_dtype = dt
+        return self
 
     def actnorm_layers(self):
         return [m for m in self.main if isinstance(m, ActNormLReLU)]

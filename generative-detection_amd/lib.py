@@ -138,6 +138,11 @@ PROTOTYPES = {
     "odvae_conv_bf16_relu": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     "odvae_conv_bf16_masked": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     "odvae_conv_wgrad_bf16_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "odvae_conv_wgrad_bf16_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
+    "odvae_conv4x4_bf16": (_I, [_I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P]),
+    "odvae_batchnorm_lrelu_fwd_bf16": (_I, [_P, _L, _I, _P, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "odvae_batchnorm_lrelu_bwd_bf16": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _Z, _P]),
+    "odvae_leaky_relu_bwd_bf16": (_I, [_P, _P, _P, _F, _L, _P]),
     "odvae_conv_wgrad_bf16": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "odvae_flash_attn_supported": (_I, [_I, _I, _I]),
     "odvae_flash_attn_fwd_bf16": (_I, [_P, _I, _I, _I, _F, _P, _P, _P]),
@@ -248,6 +253,13 @@ def conv3x3_wgrad_plan(mode, n, hi, wi, cin, cout):
     plan = dict(zip(WGRAD_PLAN_FIELDS, out))
     plan["kind"] = WGRAD_KINDS[plan["kind"]]
     return plan
+
+
+def conv_wgrad_bf16_plan(mode, n, ho, wo, cin, cout):
+    """odvae_conv_wgrad_bf16_plan as a dict; host only, needs no device.  ho, wo are the OUTPUT's (dy's)."""
+    out = (_I * 4)()
+    check(load().odvae_conv_wgrad_bf16_plan(mode, n, ho, wo, cin, cout, out), "odvae_conv_wgrad_bf16_plan")
+    return dict(zip(("nsplit", "ntiles", "tile_rows", "tile_cols"), out))
 
 
 def stream_ptr():

@@ -148,12 +148,25 @@ class _PackCache:
 
     def __init__(self):
         self.epoch = 0
+        self.generation = 0      # bumps that named no parameters (see bump)
         self._trainable = {}     # id -> weak reference (an id is reused once its tensor is gone: a frozen weight must not inherit it)
         self.store = {}
         self._tables = {}
 
-    def bump(self):
+    def bump(self, stepped=None):
+        """Every pack tagged with the epoch is stale from here on.  stepped: the parameters an optimizer step has just written (FusedAdam);
+        without it -- a load_state_dict, a broadcast -- any parameter may have changed.  The packs of kind "bf16v" are tagged per weight
+        (`weight_tag`): they go stale only when their own weight was stepped, or on a bump that names no parameters."""
         self.epoch += 1
+        if stepped is None:
+            self.generation += 1
+        else:
+            for p in stepped:
+                p._odvae_steps = getattr(p, "_odvae_steps", 0) + 1
+
+    def weight_tag(self, weight):
+        """What identifies the VALUES of this weight: storage, torch's version counter, the optimizer steps that wrote it, unnamed bumps"""
+        return (weight.data_ptr(), weight._version, getattr(weight, "_odvae_steps", 0), self.generation)
 
     def _epoch_of(self, weight):
         """The optimizer epoch a pack of this weight is valid for, or -1 for a weight that has never been trainable while this cache saw it
@@ -168,14 +181,16 @@ class _PackCache:
         seen = self._trainable.get(id(weight))
         return self.epoch if (seen is not None and seen() is weight) else -1
 
-    def _tag(self, weight):
+    def _tag(self, weight, kind="direct"):
+        if kind == "bf16v":      # tagged per weight: the discriminator's packs outlive the generator's optimizer step
+            return self.weight_tag(weight)
         # (a frozen weight -- the LPIPS-style VGG stack -- is in no optimizer: its packs do not go stale with the optimizer epoch, only with a
         # write to the tensor itself (load_state_dict: version counter))
         return (weight.data_ptr(), weight._version, self._epoch_of(weight))
 
     def get(self, weight, want_dgrad, kind="direct"):
         key = (id(weight), kind)
-        tag = self._tag(weight)
+        tag = self._tag(weight, kind)
         hit = self.store.get(key)
         same = hit is not None and hit[0]() is weight
         if same and hit[1] == tag and (hit[3] is not None or not want_dgrad):
@@ -267,7 +282,7 @@ def _pack_conv3x3_now(weight, want_fwd=True, want_dgrad=False, kind="direct", in
     w = weight.detach().contiguous()
     _lib.require_device(w)
     cout, cin = w.shape[0], w.shape[1]
-    if kind == "bf16":   # bf16 MFMA-fragment packs of a 3x3 or 1x1 conv (conv_bf16.hip); master weights stay f32
+    if kind in ("bf16", "bf16v"):   # bf16 MFMA-fragment packs of a 3x3, 1x1 or 4x4 conv (conv_bf16.hip); master weights stay f32; "bf16v": tagged per weight
         taps = w.shape[2] * w.shape[3]
         fwd = (ifwd if ifwd is not None else torch.empty(L.odvae_conv_bf16_pack_elems(cin, cout, taps), dtype=BF16, device=w.device)) if want_fwd else None
         dgr = (idgr if idgr is not None else torch.empty(L.odvae_conv_bf16_pack_elems(cout, cin, taps), dtype=BF16, device=w.device)) if want_dgrad else None
@@ -1696,6 +1711,8 @@ def batchnorm_lrelu(x, bn, slope):
     if train and bn.track_running_stats and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     momentum = 0.1 if bn.momentum is None else bn.momentum
+    if x.dtype == BF16:     # the bf16 discriminator: activations bf16, statistics and parameters f32
+        return _BatchNormLReLUB.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, slope, train)
     return _BatchNormLReLU.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, slope, train)
 
 
@@ -2340,6 +2357,178 @@ def to_bf16(x, pad_channels_to=None):
     c = x.shape[1]
     cp = c if pad_channels_to is None else max(c, (c + pad_channels_to - 1) // pad_channels_to * pad_channels_to)
     return _ToBF16.apply(x, cp)
+
+
+# ---- the PatchGAN discriminator on bf16 activations (opt-in: NLayerDiscriminator.set_precision("bf16"); conv_bf16.hip modes 5 / 6 / 7,
+# conv_wgrad_bf16.hip modes 5 / 6, gan_bf16.hip) ----
+# ODVAE_DISC_BF16=1: `precision: bf16` takes the discriminator along (AutoencoderKL.set_precision); default 0 = it stays f32.
+DISC_BF16 = os.environ.get("ODVAE_DISC_BF16", "0") == "1"
+
+
+def _conv4x4_b_raw(stride, dgrad, x, pack, cout, bias, ho, wo, out_f32, slope=0.0, cin_alg=None):
+    """One odvae_conv4x4_bf16 call: x bf16 [N, C, H, W] -> [N, cout, ho, wo] in bf16 or f32"""
+    L = _L()
+    n, cx, hi, wi = x.shape
+    y = _new_cl(n, cout, ho, wo, x, dtype=torch.float32 if out_f32 else BF16)
+    tag = KERNEL_EVENTS.begin(secondary=True)
+    _lib.check(L.odvae_conv4x4_bf16(stride, int(dgrad), x.data_ptr(), n, hi, wi, cx, pack.data_ptr(), cout, _lib.ptr(bias), y.data_ptr(),
+                                    ho, wo, int(out_f32), float(slope), _lib.stream_ptr()),
+               "conv4x4_bf16(stride=%d, dgrad=%d)" % (stride, dgrad))
+    ca = cin_alg or cx
+    px = (hi * wi) if dgrad else (ho * wo)      # 16 taps per pixel of the conv's OUTPUT, forward and transposed alike
+    KERNEL_EVENTS.end("conv4x4_bf16", 2.0 * 16 * ca * cout * n * px, tag,
+                      2.0 * n * hi * wi * ca + (4 if out_f32 else 2) * n * ho * wo * cout + 2.0 * 16 * ca * cout)
+    return y
+
+
+class _Conv4x4B(Function):
+    """Conv2d(k=4, pad=1, stride 1|2) as an implicit GEMM on bf16 NHWC activations (no cols matrix; what is saved is the bf16 input).
+    weight / bias are the f32 master parameters (OIHW), their gradients come back in f32.
+    x f32 (the image; any channel count): cast and zero-padded to a multiple of 8 channels here, and its gradient comes back in f32
+    on the image's channels (the kernel's f32 output form), so it feeds an f32 backward unchanged.
+    Output: bf16, or f32 when cout is no multiple of 8 (the logit head).
+    slope: LeakyReLU(slope) in the conv's epilogue (stride 2, bf16 output), one rounding."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, slope):
+        L = _L()
+        cout, cin = weight.shape[0], weight.shape[1]
+        from_f32 = x.dtype != BF16
+        if from_f32:
+            x = _cl(x)
+            if x.shape[1] != cin:
+                raise ValueError("conv4x4_bf16: input has %d channels, weight expects %d" % (x.shape[1], cin))
+            xb = cast_pad_bf16(x, _pad8(cin))
+        else:
+            xb = _cl(x, BF16)
+            if xb.shape[1] != cin:
+                raise ValueError("conv4x4_bf16: input has %d channels, weight expects %d" % (xb.shape[1], cin))
+            if cin % 8:
+                raise ValueError("conv4x4_bf16: a bf16 input needs a multiple of 8 channels, got %d" % cin)
+        n, cx, hi, wi = xb.shape
+        ho, wo = _conv4x4_out(hi, stride), _conv4x4_out(wi, stride)
+        out_f32 = cout % 8 != 0
+        if slope and (out_f32 or stride != 2):
+            raise NotImplementedError("conv4x4_bf16: the LeakyReLU epilogue is built for the stride-2 conv with a bf16 output")
+        need_dx = bool(ctx.needs_input_grad[0])
+        # "bf16v": a pack is rebuilt when THIS weight was written (its optimizer's step, a load_state_dict), not at every optimizer
+        # step: the generator's step between the two phases of a GAN batch leaves the discriminator's packs valid, and the three
+        # discriminator forwards of a batch (generator side, real, fake) read one pack
+        fwd_pack, dpack = pack_conv3x3(weight, True, need_dx, "bf16v")
+        b = bias.detach().contiguous() if bias is not None else None
+        y = _conv4x4_b_raw(stride, False, xb, fwd_pack, cout, b, ho, wo, out_f32, slope or 0.0, cin_alg=cin)
+        ctx.stride, ctx.slope, ctx.has_bias, ctx.from_f32, ctx.dpack = stride, float(slope or 0.0), bias is not None, from_f32, dpack
+        ctx.pack_tag, ctx.wref = PACK_CACHE.weight_tag(weight), weakref.ref(weight)
+        ctx.wshape = tuple(weight.shape)
+        ctx.save_for_backward(xb, y if slope else None)     # (y is the next layer's saved input anyway)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        xb, y = ctx.saved_tensors
+        cout, cin = ctx.wshape[0], ctx.wshape[1]
+        n, cx, hi, wi = xb.shape
+        _, _, ho, wo = dy.shape
+        stride = ctx.stride
+        f32_dy = dy.dtype != BF16
+        if f32_dy:                       # the head's f32 upstream gradient: one cast (+ channel pad) pass
+            cp = _pad8(cout)
+            dyb = cast_pad_bf16(_cl(dy), cp)
+        else:
+            cp = cout
+            dyb = _cl(dy, BF16)
+            if ctx.slope:
+                g = torch.empty_like(dyb)
+                _lib.check(L.odvae_leaky_relu_bwd_bf16(y.data_ptr(), dyb.data_ptr(), g.data_ptr(), ctx.slope, dyb.numel(), _lib.stream_ptr()),
+                           "leaky_relu_bwd_bf16")
+                dyb = g
+        dx = dw = db = None
+        if ctx.needs_input_grad[0] and not WEIGHT_GRADIENT_ONLY:
+            wnow = ctx.wref()
+            if wnow is None or PACK_CACHE.weight_tag(wnow) != ctx.pack_tag:
+                raise RuntimeError("conv4x4_bf16 backward: the weight was updated between this graph's forward and its backward; the "
+                                   "cached data-gradient pack now holds the new weights")
+            dx = _conv4x4_b_raw(stride, True, dyb, ctx.dpack, cin, None, hi, wi, ctx.from_f32, cin_alg=cout)
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        fold_db = want_db and not f32_dy and ctx.needs_input_grad[1]
+        if ctx.needs_input_grad[1]:
+            mode = 5 if stride == 1 else 6
+            dwf = torch.empty((cp, cx, 4, 4), dtype=torch.float32, device=xb.device)
+            dbf = torch.empty(cp, dtype=torch.float32, device=xb.device) if fold_db else None
+            wp, wn = _ws(L.odvae_conv_wgrad_bf16_workspace_bytes(mode, n, ho, wo, cx, cp), xb)
+            tag = KERNEL_EVENTS.begin(secondary=True)
+            _lib.check(L.odvae_conv_wgrad_bf16(mode, xb.data_ptr(), dyb.data_ptr(), n, hi, wi, cx, ho, wo, cp, dwf.data_ptr(), _lib.ptr(dbf),
+                                               wp, wn, _lib.stream_ptr()), "conv_wgrad_bf16(mode=%d)" % mode)
+            KERNEL_EVENTS.end("conv4x4_wgrad_bf16", 2.0 * 16 * cx * cp * n * ho * wo, tag, 2.0 * n * (hi * wi * cx + ho * wo * cp))
+            dw = dwf if (cp == cout and cx == cin) else dwf[:cout, :cin].contiguous()
+            if fold_db:
+                db = dbf
+        if want_db and not fold_db:
+            if f32_dy:                   # sum the f32 values themselves
+                db = _colsum(_cl(dy), n * ho * wo, cout)
+            else:
+                db = torch.empty(cout, dtype=torch.float32, device=xb.device)
+                rows = n * ho * wo
+                wp, wn = _ws(L.odvae_colsum_bf16_workspace_bytes(rows, cout), xb)
+                _lib.check(L.odvae_colsum_bf16(dyb.data_ptr(), rows, cout, db.data_ptr(), wp, wn, _lib.stream_ptr()), "colsum_bf16")
+        return dx, dw, db, None, None
+
+
+def conv4x4_bf16(x, weight, bias, stride, lrelu=None):
+    """PatchGAN convolution on the bf16 MFMA kernels (see _Conv4x4B).  lrelu: slope of a LeakyReLU fused into the epilogue, or None."""
+    if stride not in (1, 2):
+        raise ValueError("conv4x4_bf16: stride must be 1 or 2, got %r" % (stride,))
+    if x.dim() != 4 or x.shape[2] < 2 or x.shape[3] < 2:
+        raise ValueError("conv4x4_bf16: needs an [N, C, H, W] input with H, W >= 2 (kernel 4, padding 1), got %s" % (tuple(x.shape),))
+    if tuple(weight.shape[2:]) != (4, 4):
+        raise ValueError("conv4x4_bf16: weight %s is no 4x4 kernel" % (tuple(weight.shape),))
+    return _Conv4x4B.apply(x, weight, bias, int(stride), float(lrelu) if lrelu else 0.0)
+
+
+class _BatchNormLReLUB(Function):
+    """_BatchNormLReLU on bf16 activations: x, y, dy, dx bf16; statistics, running estimates and parameter gradients f32 (gan_bf16.hip)"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, slope, train):
+        L = _L()
+        x = _cl(x, BF16)
+        n, c, h, w = x.shape
+        rows = n * h * w
+        y = _new_cl(n, c, h, w, x, dtype=BF16)
+        if train:
+            mean = torch.empty(c, dtype=torch.float32, device=x.device)
+            rstd = torch.empty(c, dtype=torch.float32, device=x.device)
+        else:
+            mean = running_mean.detach().clone()
+            rstd = torch.rsqrt(running_var.detach() + eps)
+        wp, wn = _ws(L.odvae_batchnorm_workspace_bytes(rows, c), x)
+        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        _lib.check(L.odvae_batchnorm_lrelu_fwd_bf16(x.data_ptr(), rows, c, g.data_ptr(), b.data_ptr(), float(eps), float(momentum),
+                                                    float(slope), int(train), mean.data_ptr(), rstd.data_ptr(),
+                                                    _lib.ptr(running_mean) if train else None,
+                                                    _lib.ptr(running_var) if train else None, y.data_ptr(), wp, wn,
+                                                    _lib.stream_ptr()), "batchnorm_lrelu_fwd_bf16")
+        ctx.slope, ctx.train = float(slope), int(train)
+        ctx.save_for_backward(x, gamma, beta, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        x, gamma, beta, mean, rstd = ctx.saved_tensors
+        dy = _cl(dy, BF16)
+        n, c, h, w = x.shape
+        rows = n * h * w
+        dx = _new_cl(n, c, h, w, x, dtype=BF16)
+        dg = torch.empty(c, dtype=torch.float32, device=x.device)
+        db = torch.empty(c, dtype=torch.float32, device=x.device)
+        wp, wn = _ws(L.odvae_batchnorm_workspace_bytes(rows, c), x)
+        _lib.check(L.odvae_batchnorm_lrelu_bwd_bf16(x.data_ptr(), dy.data_ptr(), rows, c, gamma.detach().contiguous().data_ptr(),
+                                                    beta.detach().contiguous().data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                    ctx.slope, ctx.train, dx.data_ptr(), dg.data_ptr(), db.data_ptr(), wp, wn,
+                                                    _lib.stream_ptr()), "batchnorm_lrelu_bwd_bf16")
+        return dx, dg, db, None, None, None, None, None, None
 
 
 def _aligned_cl(t):

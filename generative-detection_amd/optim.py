@@ -231,11 +231,11 @@ class FusedAdam(torch.optim.Optimizer):
                                              f["m"].data_ptr() + 4 * beg, f["v"].data_ptr() + 4 * beg, end - beg,
                                              float(g0["lr"]), float(g0["betas"][0]), float(g0["betas"][1]),
                                              float(g0["eps"]), count, clip, _lib.stream_ptr()), "adam_step")
+        from . import ops
+        ops.PACK_CACHE.bump(stepped=[f["params"][i] for i in self._touched])   # parameters changed under torch's version counters: conv weight packs are stale
         self._touched.clear()
         self._clip_armed = False
         self._window = False
-        from . import ops
-        ops.PACK_CACHE.bump()   # parameters changed under torch's version counters: conv weight packs are stale
         return loss
 
 

@@ -32,7 +32,7 @@ class _TrainerHandle:
 class Trainer:
     def __init__(self, model, gradient_clip_val=None, optimizer_indices=(0, 1), process_group=None, bucket_mb=None, precision=None,
                  distributed=None, comm_dtype=None, callbacks=(), logger=None, comm_f32_accumulate=False,
-                 detect_anomaly=None, accumulate_grad_batches=1, perceptual_precision=None):
+                 detect_anomaly=None, accumulate_grad_batches=1, perceptual_precision=None, discriminator_precision=None):
         """optimizer_indices: which of the model's optimizers run each batch; (0,) is the "rec+KL only" benchmark
         configuration (discriminator off, optimizer 1 skipped -- SURVEY.md 8(d)).
         comm_dtype: dtype of the gradient buckets on the wire; None = f32 in every precision -- what the reference's `strategy: ddp`
@@ -50,7 +50,8 @@ class Trainer:
         batches form a window; every batch back-propagates loss / N into gradients that are zeroed only before the window's first backward; clip,
         optimizer.step() and the global_step increment happen on the window's last batch only.  1 = a step after
         every batch.
-        perceptual_precision: 32 or "bf16" for the loss's LPIPS-style net (AutoencoderKL.set_precision); None leaves it alone."""
+        perceptual_precision: 32 or "bf16" for the loss's LPIPS-style net (AutoencoderKL.set_precision); None leaves it alone.
+        discriminator_precision: the same for the loss's PatchGAN discriminator (NLayerDiscriminator.set_precision)."""
         if isinstance(accumulate_grad_batches, bool) or not isinstance(accumulate_grad_batches, int) or accumulate_grad_batches < 1:
             raise ValueError("accumulate_grad_batches must be an integer >= 1, got %r" % (accumulate_grad_batches,))
         self.accumulate_grad_batches = accumulate_grad_batches
@@ -66,12 +67,20 @@ class Trainer:
             except AttributeError:      # a real pytorch_lightning.LightningModule: `logger` is a read-only property of its Trainer
                 model._odvae_logger = logger
         if precision is not None:   # lightning.trainer.precision of the yaml (:139): 32 or "bf16"
+            extra = {}
             if perceptual_precision is not None:
-                model.set_precision(precision, perceptual_precision=perceptual_precision)
-            else:
-                model.set_precision(precision)
-        elif perceptual_precision is not None:
-            model.loss.perceptual_loss.set_precision(perceptual_precision)
+                extra["perceptual_precision"] = perceptual_precision
+            if discriminator_precision is not None:
+                extra["discriminator_precision"] = discriminator_precision
+            model.set_precision(precision, **extra)
+        else:
+            if perceptual_precision is not None:
+                model.loss.perceptual_loss.set_precision(perceptual_precision)
+            if discriminator_precision is not None:
+                disc = getattr(model.loss, "discriminator", None)
+                if not hasattr(disc, "set_precision"):
+                    raise ValueError("discriminator_precision=%r: the loss has no discriminator" % (discriminator_precision,))
+                disc.set_precision(discriminator_precision)
         self.clip = gradient_clip_val
         self.detect_anomaly = anomaly.parse_mode(detect_anomaly)
         self.anomaly = anomaly.Detector(self.detect_anomaly, model) if self.detect_anomaly else None

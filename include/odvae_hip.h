@@ -430,7 +430,7 @@ int odvae_linear_bwd_f32(const float* x, const float* w, const float* pre, const
 int odvae_conv_bf16_reduce_pad(int c);
 int odvae_conv_bf16_out_pad(int c);
 size_t odvae_conv_bf16_pack_elems(int reduce_c, int out_c, int taps);
-/* OIHW f32 weights [Cout][Cin][k][k] (taps = k*k in {1, 9}) -> bf16 MFMA-fragment packs: fwd (reduce Cin, rows Cout) and dgrad
+/* OIHW f32 weights [Cout][Cin][k][k] (taps = k*k in {1, 9, 16}) -> bf16 MFMA-fragment packs: fwd (reduce Cin, rows Cout) and dgrad
    (reduce Cout, rows Cin, taps flipped); either may be NULL */
 int odvae_conv_pack_bf16(const float* w, int Cout, int Cin, int taps, void* fwd_pack, void* dgrad_pack, void* stream);
 /* mode 0 stride 1 pad 1 | 1 Downsample pad(0,1,0,1)+stride 2 | 2 nearest-2x + stride 1 | 3 data gradient of mode 1 | 4 = 1x1 with the
@@ -454,8 +454,24 @@ int odvae_conv_bf16_relu(const void* x, int N, int H, int W, int Cin, const void
  * the stored ReLU output of the layer below it replaces torch's conv2d data gradient followed by threshold_backward (dy * (y > 0)):
  * what reaches HBM is the gradient at that layer's pre-activation.  Cout > 32, Cout % 4 == 0. */
 int odvae_conv_bf16_masked(const void* x, int N, int H, int W, int Cin, const void* pack, int Cout, const void* mask, void* y, void* stream);
-/* ---- conv_wgrad_bf16.hip: weight gradient, dw f32 OIHW, modes 0 / 1 / 2 / 4 as above; deterministic ---------------------------- */
+/* The PatchGAN Conv2d(k=4, pad=1), stride 1 | 2, as an implicit GEMM on bf16 activations (opt-in: NLayerDiscriminator.set_precision
+ * ("bf16")); no cols matrix is formed.  Rounding chain: x bf16, weights f32 -> bf16 once in the pack (odvae_conv_pack_bf16, taps = 16),
+ * f32 accumulation, bias added in f32, one round-to-nearest-even on the store.
+ * dgrad = 0: y [N][Ho][Wo][Cout] = conv(x [N][Hi][Wi][Cin]) + bias, Ho = (Hi - 2) / stride + 1 (Hi, Wi >= 2; an odd Hi at stride 2 leaves
+ *   the last padded row unread), pack = the forward pack.  lrelu_slope != 0 (stride 2, bf16 output only): LeakyReLU on the f32
+ *   accumulator in front of the one rounding; a NaN stays a NaN.
+ * dgrad = 1: x is dy [N][Hi][Wi][Cin = the conv's Cout], pack the data-gradient pack, y = dx [N][Ho][Wo][Cout = the conv's Cin] with
+ *   (Ho - 2) / stride + 1 == Hi (checked; stride 1: Ho = Hi + 1), bias NULL.  Stride 2 is the transposed convolution walked by parity
+ *   class: every pixel of dx takes exactly its 2x2 of the 16 taps, no tap is masked.
+ * Cin % 8 == 0 (the 3-channel image comes zero-padded to 8); y bf16 (out_f32 = 0, Cout % 4 == 0) or f32 (out_f32 = 1, any Cout >= 1:
+ * the logit head, and the 3-channel data gradient of the first layer). */
+int odvae_conv4x4_bf16(int stride, int dgrad, const void* x, int N, int Hi, int Wi, int Cin, const void* pack, int Cout, const float* bias,
+                       void* y, int Ho, int Wo, int out_f32, float lrelu_slope, void* stream);
+/* ---- conv_wgrad_bf16.hip: weight gradient, dw f32 OIHW, modes 0 / 1 / 2 / 4 as above, 5 / 6 = Conv2d(k=4, pad=1) at stride 1 / 2
+ * (16 taps, Ho = (Hi - 2) / stride + 1); deterministic ------------------------------------------------------------------------ */
 size_t odvae_conv_wgrad_bf16_workspace_bytes(int mode, int N, int Ho, int Wo, int Cin, int Cout);
+/* host only: out = {splits, output-pixel tiles, tile height, tile width}; split s reduces tiles s, s + splits, ... */
+int odvae_conv_wgrad_bf16_plan(int mode, int N, int Ho, int Wo, int Cin, int Cout, int out[4]);
 /* db f32 [Cout] (bias gradient = per-channel sum of dy) or NULL, produced in the same pass */
 int odvae_conv_wgrad_bf16(int mode, const void* x, const void* dy, int N, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout,
                           float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
@@ -529,6 +545,20 @@ int odvae_upsample2x_bf16(const void* x, void* u, int N, int H, int W, int C, fl
 size_t odvae_colsum_bf16_workspace_bytes(int64_t rows, int C);
 /* out f32 [C] = column sums of x bf16 [rows][C] (bias gradients) */
 int odvae_colsum_bf16(const void* x, int64_t rows, int C, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- gan_bf16.hip: BatchNorm2d + LeakyReLU of the PatchGAN on bf16 activations -----------------------------------------------
+ * odvae_batchnorm_lrelu_fwd_f32 / _bwd_f32 with x, y, dy, dx bf16 [rows][C]; mean, rstd, running statistics, gamma, beta, dgamma, dbeta
+ * f32.  The batch statistics are those of the stored bf16 values, summed about the pivot x[0][c] as in the f32 kernels; each output
+ * element is evaluated in f32 and rounded once.  Workspace: odvae_batchnorm_workspace_bytes(rows, C). */
+int odvae_batchnorm_lrelu_fwd_bf16(const void* x, int64_t rows, int C, const float* gamma, const float* beta, float eps,
+                                   float momentum, float slope, int train, float* mean, float* rstd,
+                                   float* running_mean, float* running_var, void* y,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+int odvae_batchnorm_lrelu_bwd_bf16(const void* x, const void* dy, int64_t rows, int C, const float* gamma, const float* beta,
+                                   const float* mean, const float* rstd, float slope, int train,
+                                   void* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+/* dx = dy * (y > 0 ? 1 : slope), all bf16, y the LeakyReLU's OUTPUT (slope > 0): the backward of odvae_conv4x4_bf16's epilogue */
+int odvae_leaky_relu_bwd_bf16(const void* y, const void* dy, void* dx, float slope, int64_t n, void* stream);
 
 /* ---- lpips_bf16.hip: the LPIPS-style perceptual distance on bf16 features (opt-in: LPIPSStyle.set_precision("bf16")) -------------
  * Features and feature gradients are bf16 NHWC, rounded to nearest even once per store; all arithmetic in between is f32.  A ReLU's

@@ -1,8 +1,9 @@
 """Which allocations reach hipMalloc in steady state?  Runs the bf16 (or f32) training step, then records the caching allocator's
 history over a few more steps and prints every `segment_alloc` (= a device allocation: a synchronising call) with the python frames of
 the request that caused it, plus per-step device-allocation counts.  --gan: PatchGAN + LPIPS-style loss, both optimizers (BASELINE configs[3]);
---lpips-bf16: the perceptual net on its bf16 kernels too (Trainer(perceptual_precision="bf16")).
-usage: python tools/alloc_probe.py [--f32] [--gan] [--lpips-bf16] [--gc-off] [--steps N] [--history]"""
+--lpips-bf16: the perceptual net on its bf16 kernels too (Trainer(perceptual_precision="bf16"));
+--disc-bf16: the PatchGAN discriminator on its bf16 kernels too (Trainer(discriminator_precision="bf16")).
+usage: python tools/alloc_probe.py [--f32] [--gan] [--lpips-bf16] [--disc-bf16] [--gc-off] [--steps N] [--history]"""
 import gc
 import os
 import sys
@@ -28,7 +29,8 @@ def main():
     model = synthetic.build_model(YAML, batch_size_for_lr=12, latent_hw=16, **kw).to(dev).train()
     model._global_step = 1
     trainer = Trainer(model, gradient_clip_val=1.0, optimizer_indices=(0, 1) if gan else (0,), precision=None if f32 else "bf16",
-                      perceptual_precision="bf16" if "--lpips-bf16" in sys.argv else None)
+                      perceptual_precision="bf16" if "--lpips-bf16" in sys.argv else None,
+                      discriminator_precision="bf16" if "--disc-bf16" in sys.argv else None)
     data = synthetic.make_batch(32, 256, seed=23)
     data = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in data.items()}
 
