@@ -3,7 +3,7 @@
 Mirrors src/models/autoencoder.py (PoseAutoencoder :34-443, Autoencoder :29-32) and the [UPSTREAM]
 ldm/models/autoencoder.py AutoencoderKL it derives from (encode / decode / get_input / get_last_layer /
 init_from_ckpt / configure_optimizers).  Constructor signature, attribute names, state_dict keys, batch-dict keys,
-global_step thresholds and logged names are the reference's; the arithmetic is in generative-detection_amd/ops.py.
+global_step thresholds and logged names are the reference's; the arithmetic is in generative-detection_amd/ops/.
 """
 import logging
 

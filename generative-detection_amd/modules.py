@@ -5,7 +5,7 @@ ldm/modules/diffusionmodules/model.py (Encoder, Decoder, ResnetBlock, AttnBlock,
 Downsample) as the reference subclasses them in src/modules/autoencodermodules/feat_encoder.py:4-6 and
 feat_decoder.py:4-6, so a reference checkpoint's state_dict loads unchanged.
 torch.nn.Conv2d / GroupNorm objects are used as parameter containers only (default init, OIHW weights);
-their forward is never called -- all arithmetic goes through generative-detection_amd/ops.py.
+their forward is never called -- all arithmetic goes through generative-detection_amd/ops/.
 """
 import contextlib
 

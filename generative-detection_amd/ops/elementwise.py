@@ -1,0 +1,326 @@
+"""Streaming ops: tanh, input rescale, Gaussian sample / KL, masked L1, layout copy, masks, the pose losses and the pose MLPs' dense layer."""
+import torch
+from torch.autograd import Function
+
+from .. import lib as _lib
+from ._base import CL, KERNEL_EVENTS, _L, _cl, _new_cl, _ws
+from .gemm import _colsum
+
+
+class _Tanh(Function):
+    """Decoder(tanh_out=True): elementwise on the f32 reconstruction, any layout (the kernels see a flat array); the backward keeps y only."""
+
+    @staticmethod
+    def forward(ctx, x):
+        L = _L()
+        _lib.require_device(x)
+        if not (x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=CL))):
+            x = x.contiguous()
+        y = torch.empty_like(x)      # (preserve_format: the same dense layout as x)
+        if y.stride() != x.stride():
+            x = x.contiguous()
+            y = torch.empty_like(x)
+        tag = KERNEL_EVENTS.begin(secondary=True)
+        _lib.check(L.odvae_tanh_f32(x.data_ptr(), y.data_ptr(), x.numel(), _lib.stream_ptr()), "tanh")
+        KERNEL_EVENTS.end("tanh", 0.0, tag, 8.0 * x.numel(), issued=0.0)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        (y,) = ctx.saved_tensors
+        _lib.require_device(dy)
+        if dy.stride() != y.stride():
+            dy = torch.empty_like(y).copy_(dy)
+        dx = torch.empty_like(y)
+        tag = KERNEL_EVENTS.begin(secondary=True)
+        _lib.check(L.odvae_tanh_bwd_f32(y.data_ptr(), dy.data_ptr(), dx.data_ptr(), y.numel(), _lib.stream_ptr()), "tanh_bwd")
+        KERNEL_EVENTS.end("tanh", 0.0, tag, 12.0 * y.numel(), issued=0.0)
+        return dx
+
+
+def tanh(x):
+    return _Tanh.apply(x)
+
+
+# ------------------------------------------------------------------------------------------------------
+# input rescale, posterior, reconstruction term
+# ------------------------------------------------------------------------------------------------------
+def rescale_minmax(x_nchw):
+    """2(x-min)/(max-min)-1 over the whole local batch (src/models/autoencoder.py:434-436); returns NHWC memory."""
+    L = _L()
+    _lib.require_device(x_nchw)
+    x = x_nchw.detach().contiguous()
+    n, c, h, w = x.shape
+    y = _new_cl(n, c, h, w, x)
+    mm = torch.empty(2, dtype=torch.float32, device=x.device)
+    wp, wn = _ws(16384, x)
+    _lib.check(L.odvae_rescale_minmax_f32(x.data_ptr(), y.data_ptr(), n, c, h * w, mm.data_ptr(), wp, wn,
+                                          _lib.stream_ptr()), "rescale_minmax")
+    return y
+
+
+class _GaussianSample(Function):
+    @staticmethod
+    def forward(ctx, moments, eps):
+        L = _L()
+        moments = _cl(moments)
+        eps = _cl(eps)
+        n, c2, h, w = moments.shape
+        cz = c2 // 2
+        z = _new_cl(n, cz, h, w, moments)
+        _lib.check(L.odvae_gaussian_sample_f32(moments.data_ptr(), eps.data_ptr(), z.data_ptr(), n, h * w, cz,
+                                               _lib.stream_ptr()), "gaussian_sample")
+        ctx.save_for_backward(moments, eps)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        L = _L()
+        moments, eps = ctx.saved_tensors
+        dz = _cl(dz)
+        n, c2, h, w = moments.shape
+        dm = _new_cl(n, c2, h, w, moments)
+        _lib.check(L.odvae_gaussian_bwd_f32(moments.data_ptr(), eps.data_ptr(), dz.data_ptr(), None, dm.data_ptr(),
+                                            n, h * w, c2 // 2, _lib.stream_ptr()), "gaussian_bwd(sample)")
+        return dm, None
+
+
+class _GaussianKL(Function):
+    @staticmethod
+    def forward(ctx, moments):
+        L = _L()
+        moments = _cl(moments)
+        n, c2, h, w = moments.shape
+        kl = torch.empty(n, dtype=torch.float32, device=moments.device)
+        _lib.check(L.odvae_gaussian_kl_f32(moments.data_ptr(), kl.data_ptr(), n, h * w, c2 // 2, _lib.stream_ptr()),
+                   "gaussian_kl")
+        ctx.save_for_backward(moments)
+        return kl
+
+    @staticmethod
+    def backward(ctx, dkl):
+        L = _L()
+        (moments,) = ctx.saved_tensors
+        n, c2, h, w = moments.shape
+        dkl = dkl.contiguous()
+        dm = _new_cl(n, c2, h, w, moments)
+        _lib.check(L.odvae_gaussian_bwd_f32(moments.data_ptr(), None, None, dkl.data_ptr(), dm.data_ptr(),
+                                            n, h * w, c2 // 2, _lib.stream_ptr()), "gaussian_bwd(kl)")
+        return dm
+
+
+def gaussian_sample(moments, eps):
+    return _GaussianSample.apply(moments, eps)
+
+
+def gaussian_kl(moments):
+    return _GaussianKL.apply(moments)
+
+
+class _L1MaskedSum(Function):
+    """per-sample sum |x*m - xr*m| (contperceptual.py:137 with the mask_2d_bbox products of :252-255 folded in)."""
+
+    @staticmethod
+    def forward(ctx, x, xr, mask):
+        L = _L()
+        x = _cl(x)
+        xr = _cl(xr)
+        n, c, h, w = x.shape
+        m = mask.detach().reshape(n, h * w).contiguous() if mask is not None else None
+        _lib.require_device(m)
+        out = torch.empty(n, dtype=torch.float32, device=x.device)
+        wp, wn = _ws(n * 1024, x)
+        _lib.check(L.odvae_l1_masked_sum_f32(x.data_ptr(), xr.data_ptr(), _lib.ptr(m), out.data_ptr(), n, h * w, c,
+                                             wp, wn, _lib.stream_ptr()), "l1_masked_sum")
+        ctx.save_for_backward(x, xr, m)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        L = _L()
+        x, xr, m = ctx.saved_tensors
+        n, c, h, w = x.shape
+        g = g.contiguous()
+        dxr = _new_cl(n, c, h, w, x)
+        _lib.check(L.odvae_l1_masked_bwd_f32(x.data_ptr(), xr.data_ptr(), _lib.ptr(m), g.data_ptr(), dxr.data_ptr(),
+                                             n, h * w, c, _lib.stream_ptr()), "l1_masked_bwd")
+        return None, dxr, None
+
+
+def l1_masked_sum(x, xr, mask=None):
+    return _L1MaskedSum.apply(x, xr, mask)
+
+
+def nhwc_to_nchw(x):
+    """Contiguous NCHW copy of an NHWC-in-memory tensor (hand-off to NCHW consumers)."""
+    L = _L()
+    x = _cl(x)
+    n, c, h, w = x.shape
+    y = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
+    _lib.check(L.odvae_nhwc_to_nchw_f32(x.data_ptr(), y.data_ptr(), n, c, h * w, _lib.stream_ptr()), "nhwc_to_nchw")
+    return y
+
+
+class _MulMask(Function):
+    @staticmethod
+    def forward(ctx, x, mask):
+        L = _L()
+        x = _cl(x)
+        n, c, h, w = x.shape
+        m = mask.detach().to(x.device).float().reshape(n, h * w).contiguous()
+        y = _new_cl(n, c, h, w, x)
+        _lib.check(L.odvae_mul_mask_f32(x.data_ptr(), m.data_ptr(), y.data_ptr(), n * h * w, c, _lib.stream_ptr()), "mul_mask")
+        ctx.save_for_backward(m)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        (m,) = ctx.saved_tensors
+        dy = _cl(dy)
+        n, c, h, w = dy.shape
+        dx = _new_cl(n, c, h, w, dy)
+        _lib.check(L.odvae_mul_mask_f32(dy.data_ptr(), m.data_ptr(), dx.data_ptr(), n * h * w, c, _lib.stream_ptr()), "mul_mask bwd")
+        return dx, None
+
+
+def mul_mask(x, mask):
+    """x * mask_2d_bbox ([B,1,H,W]); identity when mask is None."""
+    return x if mask is None else _MulMask.apply(x, mask)
+
+
+class _LatentCombine(Function):
+    """z * mask + add on the latent (dropout keep-mask already scaled by 1/(1-p); noise or enc_pose as `add`)."""
+
+    @staticmethod
+    def forward(ctx, z, mask, add):
+        L = _L()
+        z = _cl(z)
+        m = _cl(mask) if mask is not None else None
+        a = _cl(add) if add is not None else None
+        n, c, h, w = z.shape
+        out = _new_cl(n, c, h, w, z)
+        _lib.check(L.odvae_latent_combine_f32(z.data_ptr(), _lib.ptr(m), _lib.ptr(a), out.data_ptr(), z.numel(),
+                                              _lib.stream_ptr()), "latent_combine")
+        ctx.save_for_backward(m)
+        ctx.has_add = add is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _L()
+        (m,) = ctx.saved_tensors
+        dout = _cl(dout)
+        dz = dout
+        if m is not None and ctx.needs_input_grad[0]:
+            n, c, h, w = dout.shape
+            dz = _new_cl(n, c, h, w, dout)
+            _lib.check(L.odvae_latent_combine_f32(dout.data_ptr(), m.data_ptr(), None, dz.data_ptr(), dout.numel(),
+                                                  _lib.stream_ptr()), "latent_combine bwd")
+        return dz, None, (dout if ctx.has_add and ctx.needs_input_grad[2] else None)
+
+
+def latent_combine(z, mask=None, add=None):
+    return _LatentCombine.apply(z, mask, add)
+
+
+# ------------------------------------------------------------------------------------------------------
+# pose head: every loss term in one launch (pose_f32.hip)
+# ------------------------------------------------------------------------------------------------------
+class _PoseLosses(Function):
+    """out[9] = pose, class, bbox, fill, kl_bbox losses + the logged per-component means (t1, t2, t3, v3) of
+    src/modules/losses/contperceptual.py:111-132,176-212.  Differentiable w.r.t. dec_pose and the box-posterior moments."""
+
+    @staticmethod
+    def forward(ctx, dec_pose, moments, pose_gt, bbox_gt, fill_gt, class_gt, prior, prior_idx, bg_idx, l2, yaw, gamma, alpha):
+        L = _L()
+        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+        dec_pose, moments, pose_gt, bbox_gt, fill_gt, prior = (f32(t) for t in (dec_pose, moments, pose_gt, bbox_gt, fill_gt, prior))
+        _lib.require_device(dec_pose, moments, pose_gt, bbox_gt, fill_gt, prior)
+        class_gt = class_gt.detach().to(torch.int64).contiguous()
+        prior_idx = prior_idx.detach().to(torch.int32).contiguous()
+        b, w = dec_pose.shape
+        nc = w - 8
+        if moments.shape != (b, 16) or pose_gt.shape != (b, 4) or bbox_gt.shape != (b, 3) or fill_gt.numel() != b or prior.shape[1:] != (3, 8):
+            raise ValueError("pose_losses: unexpected shapes %s %s %s %s %s %s" % tuple(tuple(t.shape) for t in (dec_pose, moments, pose_gt, bbox_gt, fill_gt, prior)))
+        out = torch.empty(9, dtype=torch.float32, device=dec_pose.device)
+        jac_pose = torch.empty(4, b, w, dtype=torch.float32, device=dec_pose.device)
+        jac_mom = torch.empty(b, 16, dtype=torch.float32, device=dec_pose.device)
+        _lib.check(L.odvae_pose_losses_f32(dec_pose.data_ptr(), pose_gt.data_ptr(), bbox_gt.data_ptr(), fill_gt.data_ptr(), class_gt.data_ptr(),
+                                           moments.data_ptr(), prior.data_ptr(), prior_idx.data_ptr(), b, nc, prior.shape[0], int(bg_idx), int(l2),
+                                           int(yaw), float(gamma), float(alpha), out.data_ptr(), jac_pose.data_ptr(), jac_mom.data_ptr(),
+                                           _lib.stream_ptr()), "pose_losses")
+        ctx.save_for_backward(jac_pose, jac_mom)
+        ctx.dims = (b, nc)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        L = _L()
+        jac_pose, jac_mom = ctx.saved_tensors
+        b, nc = ctx.dims
+        g = g.contiguous()
+        d_pose = torch.empty(b, 8 + nc, dtype=torch.float32, device=g.device)
+        d_mom = torch.empty(b, 16, dtype=torch.float32, device=g.device)
+        _lib.check(L.odvae_pose_losses_bwd_f32(g.data_ptr(), jac_pose.data_ptr(), jac_mom.data_ptr(), b, nc, d_pose.data_ptr(), d_mom.data_ptr(),
+                                               _lib.stream_ptr()), "pose_losses_bwd")
+        return (d_pose, d_mom) + (None,) * 11
+
+
+def pose_losses(dec_pose, moments, pose_gt, bbox_gt, fill_gt, class_gt, prior, prior_idx, bg_idx=1, l2=False, yaw=True, gamma=2.0, alpha=0.25):
+    return _PoseLosses.apply(dec_pose, moments, pose_gt, bbox_gt, fill_gt, class_gt, prior, prior_idx, bg_idx, l2, yaw, gamma, alpha)
+
+
+# ------------------------------------------------------------------------------------------------------
+# pose head MLPs: skinny dense layers (linear_f32.hip)
+# ------------------------------------------------------------------------------------------------------
+LINEAR_ACTS = {None: 0, "none": 0, "tanh": 1, "swish": 2, "silu": 2, "relu": 3}
+
+
+class _LinearAct(Function):
+    """y = act(x . W^T + b) for the batch-sized rows of the pose MLPs (pose_encoder.py:59-131, pose_decoder.py:60-97); the
+    epilogue kernel fuses the split-K sum, the bias and the activation and keeps the pre-activation for the backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act):
+        L = _L()
+        x2 = x.detach().to(torch.float32).reshape(-1, x.shape[-1]).contiguous()
+        w = weight.detach().contiguous()
+        b = None if bias is None else bias.detach().contiguous()
+        _lib.require_device(x2, w, *(() if b is None else (b,)))
+        m, k = x2.shape
+        n = w.shape[0]
+        if w.shape[1] != k or (b is not None and b.numel() != n):
+            raise ValueError("linear_act: x %s, weight %s, bias %s" % (tuple(x.shape), tuple(w.shape), None if b is None else tuple(b.shape)))
+        y = torch.empty(m, n, dtype=torch.float32, device=x2.device)
+        pre = torch.empty_like(y) if act else None
+        wp, wn = _ws(L.odvae_linear_workspace_bytes(m, n, k), y)
+        _lib.check(L.odvae_linear_fwd_f32(x2.data_ptr(), w.data_ptr(), _lib.ptr(b), m, n, k, act, y.data_ptr(), _lib.ptr(pre), wp, wn,
+                                          _lib.stream_ptr()), "linear_fwd")
+        ctx.save_for_backward(x2, w, pre)
+        ctx.act, ctx.has_bias, ctx.x_shape = act, b is not None, x.shape
+        return y.reshape(x.shape[:-1] + (n,))
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        x2, w, pre = ctx.saved_tensors
+        m, k = x2.shape
+        n = w.shape[0]
+        dy = dy.to(torch.float32).reshape(m, n).contiguous()
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        dpre = torch.empty_like(dy)
+        dx = torch.empty(m, k, dtype=torch.float32, device=dy.device) if need_x else None
+        dw = torch.empty(n, k, dtype=torch.float32, device=dy.device) if need_w else None
+        wp, wn = _ws(L.odvae_linear_workspace_bytes(m, n, k), dy)
+        _lib.check(L.odvae_linear_bwd_f32(x2.data_ptr(), w.data_ptr(), _lib.ptr(pre), dy.data_ptr(), m, n, k, ctx.act, dpre.data_ptr(),
+                                          _lib.ptr(dx), _lib.ptr(dw), wp, wn, _lib.stream_ptr()), "linear_bwd")
+        db = _colsum(dpre, m, n) if need_b else None
+        return (dx.reshape(ctx.x_shape) if need_x else None), dw, db, None
+
+
+def linear_act(x, weight, bias=None, act=None):
+    """act(x @ weight.T + bias) on the small-batch MFMA kernel; act in LINEAR_ACTS."""
+    return _LinearAct.apply(x, weight, bias, LINEAR_ACTS[act])

@@ -52,7 +52,11 @@ def test_product_path_fails_loudly_without_gpu(built_lib):
 
 def test_no_product_module_imports_the_oracle():
     pkg = os.path.join(ROOT, "generative-detection_amd")
-    for fn in os.listdir(pkg):
-        if fn.endswith(".py"):
-            text = open(os.path.join(pkg, fn)).read()
-            assert "import oracle" not in text and "from oracle" not in text, fn
+    seen = 0
+    for where, _, files in os.walk(pkg):      # sub-packages too (ops/)
+        for fn in files:
+            if fn.endswith(".py"):
+                text = open(os.path.join(where, fn)).read()
+                assert "import oracle" not in text and "from oracle" not in text, os.path.join(where, fn)
+                seen += 1
+    assert seen > len([fn for fn in os.listdir(pkg) if fn.endswith(".py")]), "the walk did not reach the sub-packages"

@@ -349,7 +349,7 @@ def count_packs(monkeypatch, ops):
     def counted(weight, *a, **k):
         seen.append(id(weight))
         return real(weight, *a, **k)
-    monkeypatch.setattr(ops, "_pack_conv3x3_now", counted)
+    monkeypatch.setattr(ops.packs, "_pack_conv3x3_now", counted)     # where the pack cache looks it up
     return seen
 
 
