@@ -40,6 +40,13 @@ template <> struct Halo<2> { static constexpr int H = TH / 2 + 2, W = TW / 2 + 2
 template <> struct Halo<3> { static constexpr int H = TH / 2 + 1, W = TW / 2 + 1; };
 template <> struct Halo<5> { static constexpr int H = TH + 2, W = TW + 2; };          // tile = low-res pixels
 template <> struct Halo<6> { static constexpr int H = 2 * TH + 2, W = 2 * TW + 2; };  // halo over dy at 2x resolution
+// Conv2d(k=4, pad=1) of the PatchGAN discriminator (odvae_conv4x4_f32; the 3x3 entry point cannot reach these).  Its stride-2 forward IS
+// MODE 6's geometry with Ho, Wo free.  MODE 7 / 9: stride 1, 4x4 taps, halo origin -1 (forward) / -2 (data gradient on flipped taps);
+// MODE 8: the stride-2 data gradient by output parity class -- MODE 5's geometry over dy, the tile grid is ceil(Ho/2) x ceil(Wo/2)
+// low-res pixels and a store at a row / column past an odd Ho / Wo is dropped.
+template <> struct Halo<7> { static constexpr int H = TH + 3, W = TW + 3; };
+template <> struct Halo<8> { static constexpr int H = TH + 2, W = TW + 2; };
+template <> struct Halo<9> { static constexpr int H = TH + 3, W = TW + 3; };
 
 // halo pixel index for output pixel (r,c) of the tile and tap (kh,kw)
 template <int MODE>
@@ -57,6 +64,8 @@ __device__ __forceinline__ void halo_origin(int oy0, int ox0, int& iy0, int& ix0
   else if (MODE == 1) { iy0 = 2 * oy0; ix0 = 2 * ox0; }
   else if (MODE == 5) { iy0 = oy0 - 1; ix0 = ox0 - 1; }
   else if (MODE == 6) { iy0 = 2 * oy0 - 1; ix0 = 2 * ox0 - 1; }
+  else if (MODE == 7 || MODE == 8) { iy0 = oy0 - 1; ix0 = ox0 - 1; }
+  else if (MODE == 9) { iy0 = oy0 - 2; ix0 = ox0 - 2; }
   else { iy0 = oy0 / 2 - 1; ix0 = ox0 / 2 - 1; }
 }
 
@@ -77,7 +86,7 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_kernel_v2(ConvParams p) {
   constexpr int NG = KC / 8;
   constexpr int HALO_F4 = HPIX * QC;
   constexpr int HALO_IT = (HALO_F4 + 255) / 256;
-  constexpr int KW = MODE == 5 ? 2 : (MODE == 6 ? 4 : 3);   // taps per row; TAPS = KW * KW
+  constexpr int KW = (MODE == 5 || MODE == 8) ? 2 : ((MODE == 6 || MODE == 7 || MODE == 9) ? 4 : 3);   // taps per row; TAPS = KW * KW
   constexpr int TAPS = KW * KW;
   __shared__ __attribute__((aligned(16))) float smem[2 * HPIX * HS];
 
@@ -86,7 +95,7 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_kernel_v2(ConvParams p) {
   const int li = lane & 31, h = lane >> 5;
   // MODE 5: blockIdx.z = output parity class (py, px); the tile is 8x16 LOW-RES pixels and pixel (y, x) of it produces
   // output pixel (2y + py, 2x + px) from input pixels (y + py - 1 + a, x + px - 1 + b), a, b in {0, 1}
-  const int cls = MODE == 5 ? (int)blockIdx.z : 0, py = cls >> 1, px = cls & 1;
+  const int cls = (MODE == 5 || MODE == 8) ? (int)blockIdx.z : 0, py = cls >> 1, px = cls & 1;
 
   int t = blockIdx.x;
   const int tx = t % p.tiles_x; t /= p.tiles_x;
@@ -126,6 +135,10 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_kernel_v2(ConvParams p) {
     if (MODE == 5) {
       const int ly = oy0 + pr, lx = ox0 + pc;
       return (ly < p.Hi && lx < p.Wi) ? (unsigned)(((2 * ly + py) * p.Wo + 2 * lx + px) * p.Cout) * 4u : OOB;
+    }
+    if (MODE == 8) {
+      const int oy = 2 * (oy0 + pr) + py, ox = 2 * (ox0 + pc) + px;
+      return (oy < p.Ho && ox < p.Wo) ? (unsigned)((oy * p.Wo + ox) * p.Cout) * 4u : OOB;
     }
     const int oy = oy0 + pr, ox = ox0 + pc;
     return (oy < p.Ho && ox < p.Wo) ? (unsigned)((oy * p.Wo + ox) * p.Cout) * 4u : OOB;
@@ -233,7 +246,8 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_kernel_v2(ConvParams p) {
       int pr, pc;
       tile_pixel(wm * WMT + mt, li, pr, pc);
       int hp;
-      if (MODE == 5) hp = (pr + py + tap / KW) * Halo<5>::W + (pc + px + tap % KW);
+      if (MODE == 5 || MODE == 8) hp = (pr + py + tap / KW) * Halo<5>::W + (pc + px + tap % KW);
+      else if (MODE == 7 || MODE == 9) hp = (pr + tap / KW) * Halo<7>::W + (pc + tap % KW);
       else if (MODE == 6) hp = (2 * pr + tap / KW) * Halo<6>::W + (2 * pc + tap % KW);
       else hp = halo_index<(MODE <= 3 ? MODE : 0)>(pr, pc, tap / 3, tap % 3);
       const int off = hp * HS + 4 * h + 8 * g;
@@ -369,6 +383,41 @@ __global__ void conv3x3_pack_up_kernel(const float* __restrict__ w, int Cout, in
       const int lo_h = u == 0 ? 2 : (u == 1 ? 1 : 0), hi_h = u == 0 ? 2 : (u == 1 ? 2 : (u == 2 ? 1 : 0));
       const int lo_w = v == 0 ? 2 : (v == 1 ? 1 : 0), hi_w = v == 0 ? 2 : (v == 1 ? 2 : (v == 2 ? 1 : 0));
       dgr[idx - nf] = (co < Cout && ci < Cin) ? up_row_sum(w + ((int64_t)co * Cin + ci) * 9, lo_h, hi_h, lo_w, hi_w) : 0.f;
+    }
+  }
+}
+
+// Conv2d(k=4, pad=1, stride 1|2), OIHW [Cout][Cin][4][4] -> 16-tap packs [16][reduce/4][out][4].
+// fwd: tap = kh * 4 + kw.  dgrad, stride 1: tap t holds w[..][3 - kh][3 - kw] (the flipped taps a pad-2 conv over dy walks).
+// dgrad, stride 2: entry cls * 4 + a * 2 + b, cls = 2 py + px, holds w[..][3 - py - 2a][3 - px - 2b]: the four taps the blocks of
+// parity class (py, px) walk, from dy pixel (y + py - 1 + a, x + px - 1 + b) to dx pixel (2y + py, 2x + px).
+__global__ void conv4x4_pack_kernel(const float* __restrict__ w, int Cout, int Cin, int stride,
+                                    float* __restrict__ fwd, int CinP_f, int CoutP_f,
+                                    float* __restrict__ dgr, int CoutP_d, int CinP_d) {
+  const int64_t nf = fwd ? (int64_t)16 * CinP_f * CoutP_f : 0;
+  const int64_t nd = dgr ? (int64_t)16 * CoutP_d * CinP_d : 0;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < nf + nd;
+       idx += (int64_t)gridDim.x * blockDim.x) {
+    if (idx < nf) {
+      int64_t r = idx;
+      const int j = r & 3; r >>= 2;
+      const int co = (int)(r % CoutP_f); r /= CoutP_f;
+      const int q = (int)(r % (CinP_f / 4)); const int tap = (int)(r / (CinP_f / 4));
+      const int ci = 4 * q + j;
+      fwd[idx] = (co < Cout && ci < Cin) ? w[((int64_t)co * Cin + ci) * 16 + tap] : 0.f;
+    } else {
+      int64_t r = idx - nf;
+      const int j = r & 3; r >>= 2;
+      const int ci = (int)(r % CinP_d); r /= CinP_d;
+      const int q = (int)(r % (CoutP_d / 4)); const int t16 = (int)(r / (CoutP_d / 4));
+      const int co = 4 * q + j;
+      int src;
+      if (stride == 1) src = 15 - t16;
+      else {
+        const int cls = t16 >> 2, a = (t16 >> 1) & 1, b = t16 & 1;
+        src = (3 - (cls >> 1) - 2 * a) * 4 + (3 - (cls & 1) - 2 * b);
+      }
+      dgr[idx - nf] = (co < Cout && ci < Cin) ? w[((int64_t)co * Cin + ci) * 16 + src] : 0.f;
     }
   }
 }
@@ -626,6 +675,76 @@ int odvae_conv3x3_f32(int mode, const float* x, int N, int Hi, int Wi, int Cin,
   }
 #undef ODVAE_CONV_LAUNCH
   ODVAE_LAUNCH_CHECK("conv3x3");
+  return ODVAE_OK;
+}
+
+// ---- Conv2d(k=4, pad=1, stride 1|2) of the PatchGAN discriminator as an implicit GEMM (no cols matrix) ----------------------
+// 1 when odvae_conv4x4_f32 / odvae_conv4x4_wgrad_f32 take a layer x [N][Hi][Wi][Cin] -> y [N][Ho][Wo][Cout], forward and gradients
+int odvae_conv4x4_f32_supported(int stride, int N, int Hi, int Wi, int Cin, int Cout) {
+  if ((stride != 1 && stride != 2) || N <= 0 || Hi < 2 || Wi < 2 || Cin <= 0 || Cout <= 0) return 0;
+  const int64_t Ho = (Hi - 2) / stride + 1, Wo = (Wi - 2) / stride + 1;
+  if ((int64_t)Hi * Wi * Cin * 4 >= 0x7FFFFFF0ll || Ho * Wo * Cout * 4 >= 0x7FFFFFF0ll) return 0;
+  if ((int64_t)ceil_div(Hi, 8) * ceil_div(Wi, 16) * N >= (1ll << 31)) return 0;
+  return 1;
+}
+
+size_t odvae_conv4x4_pack_floats(int c_reduce, int c_out) {
+  return (size_t)16 * odvae_conv3x3_pack_reduce_pad(c_reduce) * odvae_conv3x3_pack_out_pad(c_out);
+}
+
+// w: OIHW [Cout][Cin][4][4].  fwd_pack (may be null): odvae_conv4x4_pack_floats(Cin, Cout) floats; dgrad_pack (may be null):
+// odvae_conv4x4_pack_floats(Cout, Cin) floats, ordered for the data gradient of that stride.
+int odvae_conv4x4_pack_f32(const float* w, int Cout, int Cin, int stride, float* fwd_pack, float* dgrad_pack, void* stream) {
+  ODVAE_CHECK_ARG(w && Cout > 0 && Cin > 0, "conv4x4_pack: bad arguments");
+  ODVAE_CHECK_ARG(stride == 1 || stride == 2, "conv4x4_pack: stride %d", stride);
+  const int CinP_f = odvae_conv3x3_pack_reduce_pad(Cin), CoutP_f = odvae_conv3x3_pack_out_pad(Cout);
+  const int CoutP_d = odvae_conv3x3_pack_reduce_pad(Cout), CinP_d = odvae_conv3x3_pack_out_pad(Cin);
+  const int64_t total = (fwd_pack ? (int64_t)16 * CinP_f * CoutP_f : 0) + (dgrad_pack ? (int64_t)16 * CoutP_d * CinP_d : 0);
+  if (total == 0) return ODVAE_OK;
+  const int blocks = (int)std::min<int64_t>(ceil_div64(total, 256), 2048);
+  hipLaunchKernelGGL(conv4x4_pack_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     w, Cout, Cin, stride, fwd_pack, CinP_f, CoutP_f, dgrad_pack, CoutP_d, CinP_d);
+  ODVAE_LAUNCH_CHECK("conv4x4_pack");
+  return ODVAE_OK;
+}
+
+// dgrad = 0: y = conv4x4(x) (+bias), Ho = (Hi - 2) / stride + 1, wpk = the forward pack.
+// dgrad = 1: x = dy [N][Hi][Wi][Cin] of a layer whose input is y = dx [N][Ho][Wo][Cout]: Hi = (Ho - 2) / stride + 1, wpk = the
+// data-gradient pack of that stride (reduction axis Cin = the layer's output channels), bias null.
+int odvae_conv4x4_f32(int stride, int dgrad, const float* x, int N, int Hi, int Wi, int Cin, const float* wpk, int Cout,
+                      const float* bias, float* y, int Ho, int Wo, void* stream) {
+  ODVAE_CHECK_ARG(x && wpk && y, "conv4x4: null operand");
+  ODVAE_CHECK_ARG(stride == 1 || stride == 2, "conv4x4: stride %d", stride);
+  ODVAE_CHECK_ARG(dgrad == 0 || dgrad == 1, "conv4x4: dgrad %d", dgrad);
+  ODVAE_CHECK_ARG(N > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0 && Ho > 0 && Wo > 0, "conv4x4: empty shape");
+  if (dgrad) ODVAE_CHECK_ARG(Ho >= 2 && Wo >= 2 && Hi == (Ho - 2) / stride + 1 && Wi == (Wo - 2) / stride + 1 && !bias,
+                             "conv4x4 data gradient: need Hi = (Ho - 2) / stride + 1 and no bias");
+  else ODVAE_CHECK_ARG(Hi >= 2 && Wi >= 2 && Ho == (Hi - 2) / stride + 1 && Wo == (Wi - 2) / stride + 1,
+                       "conv4x4: need Ho = (Hi - 2) / stride + 1");
+  ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)wpk & 15) == 0, "conv4x4: x/wpk must be 16-byte aligned");
+  ODVAE_CHECK_ARG((int64_t)Hi * Wi * Cin * 4 < 0x7FFFFFF0ll && (int64_t)Ho * Wo * Cout * 4 < 0x7FFFFFF0ll,
+                  "conv4x4: one input / output image must stay below 2 GiB");
+  const bool by_class = dgrad && stride == 2;      // tiles of low-res pixels, blockIdx.z = parity class
+  ConvParams p;
+  p.x = x; p.wpk = wpk; p.bias = bias; p.residual = nullptr; p.y = y;
+  p.N = N; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout;
+  p.CinP = odvae_conv3x3_pack_reduce_pad(Cin); p.CoutP = odvae_conv3x3_pack_out_pad(Cout);
+  p.tiles_x = ceil_div(by_class ? ceil_div(Wo, 2) : Wo, TW); p.tiles_y = ceil_div(by_class ? ceil_div(Ho, 2) : Ho, TH);
+  p.act = 0;
+  const int64_t sp = (int64_t)p.tiles_x * p.tiles_y * N;
+  ODVAE_CHECK_ARG(sp < (1ll << 31), "conv4x4: too many tiles");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool narrow = Cout <= 32;
+  dim3 block(256);
+#define ODVAE_CONV4_LAUNCH(MODE, KC, Z)                                                                                           \
+  if (narrow) hipLaunchKernelGGL((conv3x3_kernel_v2<MODE, KC, 1, 1, 4, 1>), dim3((unsigned)sp, p.CoutP / 32, Z), block, 0, st, p); \
+  else hipLaunchKernelGGL((conv3x3_kernel_v2<MODE, KC, 2, 2, 2, 2>), dim3((unsigned)sp, p.CoutP / 128, Z), block, 0, st, p)
+  if (stride == 2 && !dgrad) { ODVAE_CONV4_LAUNCH(6, 8, 1); }
+  else if (stride == 2) { ODVAE_CONV4_LAUNCH(8, 32, 4); }
+  else if (!dgrad) { ODVAE_CONV4_LAUNCH(7, 32, 1); }
+  else { ODVAE_CONV4_LAUNCH(9, 32, 1); }
+#undef ODVAE_CONV4_LAUNCH
+  ODVAE_LAUNCH_CHECK("conv4x4");
   return ODVAE_OK;
 }
 

@@ -107,6 +107,13 @@ PROTOTYPES = {
     "odvae_im2col4x4_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "odvae_col2im4x4_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "odvae_weight4x4_reorder_f32": (_I, [_P, _P, _I, _I, _I, _P]),
+    "odvae_conv4x4_f32_supported": (_I, [_I, _I, _I, _I, _I, _I]),
+    "odvae_conv4x4_pack_floats": (_Z, [_I, _I]),
+    "odvae_conv4x4_pack_f32": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "odvae_conv4x4_f32": (_I, [_I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P]),
+    "odvae_conv4x4_wgrad_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "odvae_conv4x4_wgrad_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "odvae_conv4x4_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "odvae_batchnorm_workspace_bytes": (_Z, [_L, _I]),
     "odvae_batchnorm_lrelu_fwd_f32": (_I, [_P, _L, _I, _P, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "odvae_batchnorm_lrelu_bwd_f32": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _Z, _P]),

@@ -64,6 +64,9 @@ ATTN_F32_FUSED = os.environ.get("ODVAE_ATTN_F32_FUSED", "0") == "1"
 LPIPS_BF16 = os.environ.get("ODVAE_LPIPS_BF16", "0") == "1"
 # ODVAE_DISC_BF16=1: `precision: bf16` takes the discriminator along (AutoencoderKL.set_precision); default 0 = it stays f32.
 DISC_BF16 = os.environ.get("ODVAE_DISC_BF16", "0") == "1"
+# ODVAE_DISC_F32_IMPLICIT=1: the f32 PatchGAN's 4x4 convs as implicit GEMMs with their own weight-gradient kernel (_Conv4x4I: no cols
+# matrix, what a conv saves is its input); default 0 = im2col + GEMM + col2im (_Conv4x4).  A bf16 discriminator never gets here.
+DISC_F32_IMPLICIT = os.environ.get("ODVAE_DISC_F32_IMPLICIT", "0") == "1"
 
 WGRAD_1X1_GROUP = 0   # tests: force the image-group split of the 1x1 weight gradient at small sizes (0 = only past 2 GiB)
 CONV_1X1_GROUP = 0    # tests: the same for the 1x1 forward / data gradient in _conv_b_raw (images per launch; 0 = only past 2 GiB)
@@ -86,7 +89,7 @@ _ATTN_LAST_FLAG = None     # (diagnostics / tests: the device flag of the last f
 from ._base import (  # noqa: E402
     CL, _L, BF16, _cl, _new_cl, _ws, _stamp, _stamped, _KernelEvents, KERNEL_EVENTS)
 from .packs import (  # noqa: E402
-    _PackCache, _BATCH_KINDS, _batchable, PACK_CACHE, _pack_conv3x3_now, pack_conv3x3)
+    _PackCache, _PER_WEIGHT_KINDS, _BATCH_KINDS, _batchable, PACK_CACHE, _pack_conv3x3_now, pack_conv3x3)
 from .gn_link import (  # noqa: E402
     GN_GROUPS, _GnBwdLink, _gn_bwd_link_of, _gn_stats_ok, _tag_gn_partials, _gn_partials_of, _f32_gn_link, gn_fused_bwd_suspended,
     _tag_gn_output)
@@ -114,5 +117,5 @@ from .elementwise import (  # noqa: E402
     _Tanh, tanh, rescale_minmax, _GaussianSample, _GaussianKL, gaussian_sample, gaussian_kl, _L1MaskedSum, l1_masked_sum, nhwc_to_nchw,
     _MulMask, mul_mask, _LatentCombine, latent_combine, _PoseLosses, pose_losses, LINEAR_ACTS, _LinearAct, linear_act)
 from .patchgan import (  # noqa: E402
-    _conv4x4_out, _Conv4x4, conv4x4, _BatchNormLReLU, batchnorm_lrelu, _ActNormLReLU, actnorm_init, actnorm_lrelu, _LeakyReLU,
+    _conv4x4_out, _Conv4x4, _conv4x4_i_raw, _Conv4x4I, conv4x4, _BatchNormLReLU, batchnorm_lrelu, _ActNormLReLU, actnorm_init, actnorm_lrelu, _LeakyReLU,
     leaky_relu, _conv4x4_b_raw, _Conv4x4B, conv4x4_bf16, _BatchNormLReLUB)

@@ -57,7 +57,7 @@ class _PackCache:
         return self.epoch if (seen is not None and seen() is weight) else -1
 
     def _tag(self, weight, kind="direct"):
-        if kind == "bf16v":      # tagged per weight: the discriminator's packs outlive the generator's optimizer step
+        if kind in _PER_WEIGHT_KINDS:      # tagged per weight: the discriminator's packs outlive the generator's optimizer step
             return self.weight_tag(weight)
         # (a frozen weight -- the LPIPS-style VGG stack -- is in no optimizer: its packs do not go stale with the optimizer epoch, only with a
         # write to the tensor itself (load_state_dict: version counter))
@@ -130,6 +130,7 @@ class _PackCache:
                                "cached weight packs now hold the new weights" % what)
 
 
+_PER_WEIGHT_KINDS = ("bf16v", "c4x4s1", "c4x4s2")      # the PatchGAN's packs: bf16, and the f32 16-tap packs of a stride-1 / stride-2 conv
 _BATCH_KINDS = ("wino", "wino4")      # (bf16 packs: batching measured 0.3-0.65 ms per step slower, see conv_bf16.hip)
 
 
@@ -162,6 +163,11 @@ def _pack_conv3x3_now(weight, want_fwd=True, want_dgrad=False, kind="direct", in
         fwd = (ifwd if ifwd is not None else torch.empty(L.odvae_conv_bf16_pack_elems(cin, cout, taps), dtype=BF16, device=w.device)) if want_fwd else None
         dgr = (idgr if idgr is not None else torch.empty(L.odvae_conv_bf16_pack_elems(cout, cin, taps), dtype=BF16, device=w.device)) if want_dgrad else None
         _lib.check(L.odvae_conv_pack_bf16(w.data_ptr(), cout, cin, taps, _lib.ptr(fwd), _lib.ptr(dgr), _lib.stream_ptr()), "conv_pack_bf16")
+        return fwd, dgr
+    if kind in ("c4x4s1", "c4x4s2"):   # f32 16-tap packs of Conv2d(k=4, pad=1) (odvae_conv4x4_f32); the data-gradient pack's order depends on the stride
+        fwd = (ifwd if ifwd is not None else torch.empty(L.odvae_conv4x4_pack_floats(cin, cout), dtype=torch.float32, device=w.device)) if want_fwd else None
+        dgr = (idgr if idgr is not None else torch.empty(L.odvae_conv4x4_pack_floats(cout, cin), dtype=torch.float32, device=w.device)) if want_dgrad else None
+        _lib.check(L.odvae_conv4x4_pack_f32(w.data_ptr(), cout, cin, int(kind[-1]), _lib.ptr(fwd), _lib.ptr(dgr), _lib.stream_ptr()), "conv4x4_pack")
         return fwd, dgr
     floats, pack = {"direct": (L.odvae_conv3x3_pack_floats, L.odvae_conv3x3_pack_f32),
                     "up": (L.odvae_conv3x3_up_pack_floats, L.odvae_conv3x3_pack_up_f32),

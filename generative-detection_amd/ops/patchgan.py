@@ -68,10 +68,79 @@ class _Conv4x4(Function):
         return dx, dw, db, None
 
 
+def _conv4x4_i_raw(stride, dgrad, x, pack, cout, bias, ho, wo):
+    """One odvae_conv4x4_f32 call: x f32 [N, C, H, W] -> [N, cout, ho, wo]"""
+    L = _L()
+    n, cx, hi, wi = x.shape
+    y = _new_cl(n, cout, ho, wo, x)
+    tag = KERNEL_EVENTS.begin(secondary=True)
+    _lib.check(L.odvae_conv4x4_f32(stride, int(dgrad), x.data_ptr(), n, hi, wi, cx, pack.data_ptr(), cout, _lib.ptr(bias), y.data_ptr(),
+                                   ho, wo, _lib.stream_ptr()), "conv4x4_f32(stride=%d, dgrad=%d)" % (stride, dgrad))
+    px = (hi * wi) if dgrad else (ho * wo)      # 16 taps per pixel of the conv's OUTPUT, forward and transposed alike
+    KERNEL_EVENTS.end("conv4x4_f32", 2.0 * 16 * cx * cout * n * px, tag,
+                      4.0 * n * hi * wi * cx + 4.0 * n * ho * wo * cout + 4.0 * 16 * cx * cout)
+    return y
+
+
+class _Conv4x4I(Function):
+    """Conv2d(k=4, pad=1, stride 1|2) as an implicit GEMM in exact f32 (opt-in: ops.DISC_F32_IMPLICIT; conv3x3_f32.hip modes 6 - 9,
+    conv4x4_wgrad_f32.hip).  No cols matrix: what is saved is the input, which is the previous layer's output anyway.  Any Cout
+    (the logit head needs no padding round trip).  weight OIHW [Cout][Cin][4][4]."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride):
+        x = _cl(x)
+        n, cin, hi, wi = x.shape
+        cout = weight.shape[0]
+        ho, wo = _conv4x4_out(hi, stride), _conv4x4_out(wi, stride)
+        need_dx = bool(ctx.needs_input_grad[0])
+        # tagged per weight, as "bf16v": the three discriminator forwards of a GAN batch and the generator's optimizer step between
+        # them read one pack; the data-gradient pack's tap order depends on the stride, hence one kind per stride
+        fwd_pack, dpack = pack_conv3x3(weight, True, need_dx, "c4x4s%d" % stride)
+        b = bias.detach().contiguous() if bias is not None else None
+        y = _conv4x4_i_raw(stride, False, x, fwd_pack, cout, b, ho, wo)
+        ctx.stride, ctx.has_bias, ctx.dpack = stride, bias is not None, dpack
+        ctx.pack_tag, ctx.wref = _ops.PACK_CACHE.weight_tag(weight), weakref.ref(weight)
+        ctx.wshape = tuple(weight.shape)
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        (x,) = ctx.saved_tensors
+        dy = _cl(dy)
+        cout, cin = ctx.wshape[0], ctx.wshape[1]
+        n, _, hi, wi = x.shape
+        _, _, ho, wo = dy.shape
+        stride = ctx.stride
+        dx = dw = db = None
+        if ctx.needs_input_grad[0] and not _ops.WEIGHT_GRADIENT_ONLY:
+            wnow = ctx.wref()
+            if wnow is None or _ops.PACK_CACHE.weight_tag(wnow) != ctx.pack_tag:
+                raise RuntimeError("conv4x4 backward: the weight was updated between this graph's forward and its backward; the "
+                                   "cached data-gradient pack now holds the new weights")
+            dx = _conv4x4_i_raw(stride, True, dy, ctx.dpack, cin, None, hi, wi)
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty((cout, cin, 4, 4), dtype=torch.float32, device=x.device)
+            if want_db:
+                db = torch.empty(cout, dtype=torch.float32, device=x.device)
+            wp, wn = _ws(L.odvae_conv4x4_wgrad_workspace_bytes(stride, n, ho, wo, cin, cout), x)
+            tag = KERNEL_EVENTS.begin(secondary=True)
+            _lib.check(L.odvae_conv4x4_wgrad_f32(stride, x.data_ptr(), dy.data_ptr(), n, hi, wi, cin, ho, wo, cout, dw.data_ptr(), _lib.ptr(db),
+                                                 wp, wn, _lib.stream_ptr()), "conv4x4_wgrad_f32(stride=%d)" % stride)
+            KERNEL_EVENTS.end("conv4x4_wgrad_f32", 2.0 * 16 * cin * cout * n * ho * wo, tag, 4.0 * n * (hi * wi * cin + ho * wo * cout))
+        elif want_db:
+            db = _colsum(dy, n * ho * wo, cout)
+        return dx, dw, db, None
+
+
 def conv4x4(x, weight, bias, stride):
     """PatchGAN convolution.  Cout = 1 (the logit head) is zero-padded to 4 output channels for the GEMM's
     float4 staging and sliced back (torch cat/slice on [4,C,4,4] / [B,4,30,30]-sized tensors).
-    An input under 2 pixels high or wide is refused here, as torch refuses it (the padded image is smaller than the kernel)."""
+    An input under 2 pixels high or wide is refused here, as torch refuses it (the padded image is smaller than the kernel).
+    With ops.DISC_F32_IMPLICIT on, shapes odvae_conv4x4_f32_supported takes run as an implicit GEMM instead (_Conv4x4I)."""
     if stride not in (1, 2):
         raise ValueError("conv4x4: stride must be 1 or 2, got %r" % (stride,))
     if x.dim() != 4 or x.shape[2] < 2 or x.shape[3] < 2:
@@ -79,6 +148,8 @@ def conv4x4(x, weight, bias, stride):
     if tuple(weight.shape[1:]) != (x.shape[1], 4, 4):
         raise ValueError("conv4x4: weight %s does not fit an input with %d channels" % (tuple(weight.shape), x.shape[1]))
     cout = weight.shape[0]
+    if _ops.DISC_F32_IMPLICIT and _L().odvae_conv4x4_f32_supported(int(stride), x.shape[0], x.shape[2], x.shape[3], x.shape[1], cout):
+        return _Conv4x4I.apply(x, weight, bias, int(stride))
     if cout % 4 == 0:
         return _Conv4x4.apply(x, weight, bias, stride)
     pad = 4 - cout % 4

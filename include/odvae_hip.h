@@ -346,6 +346,23 @@ int odvae_latent_combine_f32(const float* z, const float* mask, const float* add
 int odvae_im2col4x4_f32(const float* x, float* cols, int N, int Hi, int Wi, int C, int Ho, int Wo, int stride, void* stream);
 int odvae_col2im4x4_f32(const float* dcols, float* dx, int N, int Hi, int Wi, int C, int Ho, int Wo, int stride, void* stream);
 int odvae_weight4x4_reorder_f32(const float* src, float* dst, int Cout, int Cin, int to_gemm, void* stream);
+/* ---- conv3x3_f32.hip, conv4x4_wgrad_f32.hip: the same Conv2d(k=4, pad=1, stride 1|2) as an implicit GEMM, exact f32, no cols matrix
+ * (opt-in: ODVAE_DISC_F32_IMPLICIT=1).  NHWC; Ho = (Hi - 2) / stride + 1, Hi and Wi may be odd.  Packs are [16][reduce_pad/4][out_pad][4]
+ * with the pads of odvae_conv3x3_pack_reduce_pad / _out_pad; the data-gradient pack (flipped taps, channel roles swapped; stride 2:
+ * ordered by output parity class) depends on the stride.
+ * odvae_conv4x4_f32, dgrad = 0: y = conv(x) + bias, wpk = forward pack.  dgrad = 1: x = dy [N][Hi][Wi][Cin = the layer's output
+ * channels], y = dx [N][Ho][Wo][Cout = the layer's input channels], Hi = (Ho - 2) / stride + 1, wpk = data-gradient pack, bias null.
+ * odvae_conv4x4_wgrad_f32: dw OIHW [Cout][Cin][4][4] and dbias [Cout] (or null), partial sums reduced in a fixed order (deterministic);
+ * odvae_conv4x4_wgrad_plan (host only): out = {kind (1), ntiles, nsplit, tiles_per_split, ci_tiles, co_tiles, tile_rows, stride}. */
+int odvae_conv4x4_f32_supported(int stride, int N, int Hi, int Wi, int Cin, int Cout);
+size_t odvae_conv4x4_pack_floats(int c_reduce, int c_out);
+int odvae_conv4x4_pack_f32(const float* w_oihw, int Cout, int Cin, int stride, float* fwd_pack, float* dgrad_pack, void* stream);
+int odvae_conv4x4_f32(int stride, int dgrad, const float* x, int N, int Hi, int Wi, int Cin, const float* wpk, int Cout,
+                      const float* bias, float* y, int Ho, int Wo, void* stream);
+size_t odvae_conv4x4_wgrad_workspace_bytes(int stride, int N, int Ho, int Wo, int Cin, int Cout);
+int odvae_conv4x4_wgrad_f32(int stride, const float* x, const float* dy, int N, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout,
+                            float* dw, float* dbias, void* workspace, size_t workspace_bytes, void* stream);
+int odvae_conv4x4_wgrad_plan(int stride, int N, int Hi, int Wi, int Cin, int Cout, int out[8]);
 /* torch.nn.BatchNorm2d (batch statistics when train=1, running-stat update with momentum) + LeakyReLU(slope), x [rows][C] */
 size_t odvae_batchnorm_workspace_bytes(int64_t rows, int C);
 int odvae_batchnorm_lrelu_fwd_f32(const float* x, int64_t rows, int C, const float* gamma, const float* beta, float eps,

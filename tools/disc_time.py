@@ -1,7 +1,10 @@
-"""The PatchGAN discriminator alone, f32 beside bf16 (NLayerDiscriminator.set_precision), B = 32 at 256 x 256, in one process:
+"""The PatchGAN discriminator alone, f32 (im2col + GEMM) beside f32 implicit (ops.DISC_F32_IMPLICIT) and bf16
+(NLayerDiscriminator.set_precision), B = 32 at 256 x 256, in one process:
   * the discriminator step -- forward on a real and a fake batch, hinge loss, backward to the weights -- and the generator-side pass --
-    forward on the reconstruction, backward to the image (no weight gradient) -- in windows that alternate between the two precisions;
-  * peak device memory of one discriminator step in each precision;
+    forward on the reconstruction, backward to the image (no weight gradient) -- in windows that alternate between the three arms;
+  * peak device memory of one discriminator step in each arm;
+  * the f32 layers one at a time, implicit (odvae_conv4x4_f32 / odvae_conv4x4_wgrad_f32 on preallocated buffers) beside the im2col form
+    (reorder + im2col + GEMM | GEMM + col2im | GEMM + reorder, the calls of ops._Conv4x4), windows alternating;
   * the bf16 layers one at a time through the C ABI on preallocated buffers (no autograd node, no allocation): forward, data gradient,
     weight gradient of each 4x4 conv, executed TFLOP/s = 2 * 16 * Cin * Cout * N * Ho * Wo / time, and BatchNorm + LeakyReLU forward /
     backward with their HBM traffic.
@@ -56,6 +59,8 @@ def whole_net(batch, res, reps, rounds):
     fake = (real + 0.3 * torch.randn(batch, 3, res, res, device=dev, generator=g)).clamp(-1, 1).contiguous(memory_format=torch.channels_last)
     rec = fake.clone().requires_grad_(True)
     params = list(net.parameters())
+    from odvae_amd import ops
+    arms = (("f32", 32, False), ("f32 implicit", 32, True), ("bf16", "bf16", False))
 
     def disc_step():
         lr, lf = net(real), net(fake)
@@ -72,12 +77,13 @@ def whole_net(batch, res, reps, rounds):
         for p in params:
             p.requires_grad_(True)
 
-    times = {(n, k): [] for n in ("f32", "bf16") for k in ("disc_step", "gen_side")}
+    times = {(n, k): [] for n, _, _ in arms for k in ("disc_step", "gen_side")}
     peak = {}
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        for name, prec in (("f32", 32), ("bf16", "bf16")):       # packs, workspaces, allocator pools; then the peak of one step
+        for name, prec, implicit in arms:       # packs, workspaces, allocator pools; then the peak of one step
             net.set_precision(prec)
+            ops.DISC_F32_IMPLICIT = implicit
             disc_step(); gen_side(); disc_step()
             torch.cuda.synchronize()
             base = torch.cuda.memory_allocated(dev)
@@ -86,11 +92,77 @@ def whole_net(batch, res, reps, rounds):
             torch.cuda.synchronize()
             peak[name] = {"peak_over_resident_mb": (torch.cuda.max_memory_allocated(dev) - base) / 1e6, "resident_mb": base / 1e6}
         for _ in range(rounds):
-            for name, prec in (("f32", 32), ("bf16", "bf16")):
+            for name, prec, implicit in arms:
                 net.set_precision(prec)
+                ops.DISC_F32_IMPLICIT = implicit
                 times[(name, "disc_step")].append(window(disc_step, reps))
                 times[(name, "gen_side")].append(window(gen_side, reps))
+    ops.DISC_F32_IMPLICIT = False
     return {"%s %s" % k: med(v) for k, v in times.items()}, peak
+
+
+def per_layer_f32(batch, res, reps, rounds):
+    """each 4x4 conv in f32: the implicit kernels through the C ABI beside the im2col form's calls, alternating windows"""
+    from odvae_amd import lib, ops
+    dev = torch.device("cuda:0")
+    L, st = lib.load(), lib.stream_ptr()
+    rows = []
+    for cin, cout, stride, si, so, post in layers_of(res):
+        g = torch.Generator(device=dev).manual_seed(cin + cout)
+        w = torch.randn(cout, cin, 4, 4, device=dev, generator=g) * 0.02
+        b = torch.zeros(cout, device=dev)
+        fwd, dgr = ops._pack_conv3x3_now(w, True, True, "c4x4s%d" % stride)
+        x = torch.randn(batch, si, si, cin, device=dev, generator=g)
+        y = torch.empty(batch, so, so, cout, device=dev)
+        dy = torch.randn(batch, so, so, cout, device=dev, generator=g)
+        dx = torch.empty(batch, si, si, cin, device=dev)
+        dw, db = torch.empty(cout, cin, 4, 4, device=dev), torch.empty(cout, device=dev)
+        need = L.odvae_conv4x4_wgrad_workspace_bytes(stride, batch, so, so, cin, cout)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        # the im2col form: Cout = 1 runs zero-padded to 4 channels (ops.conv4x4)
+        cg = cout if cout % 4 == 0 else cout + 4 - cout % 4
+        m, k = batch * so * so, 16 * cin
+        wp = torch.zeros(cg, cin, 4, 4, device=dev); wp[:cout] = w
+        bp = torch.zeros(cg, device=dev)
+        wg, cols, dcols = torch.empty(cg, k, device=dev), torch.empty(m, k, device=dev), torch.empty(m, k, device=dev)
+        yg, dyg = torch.empty(m, cg, device=dev), torch.randn(m, cg, device=dev, generator=g)
+        dwg, dwo = torch.empty(cg, k, device=dev), torch.empty(cg, cin, 4, 4, device=dev)
+
+        def i_fwd():
+            lib.check(L.odvae_conv4x4_f32(stride, 0, x.data_ptr(), batch, si, si, cin, fwd.data_ptr(), cout, b.data_ptr(), y.data_ptr(), so, so, st), "fwd")
+
+        def i_dgrad():
+            lib.check(L.odvae_conv4x4_f32(stride, 1, dy.data_ptr(), batch, so, so, cout, dgr.data_ptr(), cin, None, dx.data_ptr(), si, si, st), "dgrad")
+
+        def i_wgrad():
+            lib.check(L.odvae_conv4x4_wgrad_f32(stride, x.data_ptr(), dy.data_ptr(), batch, si, si, cin, so, so, cout, dw.data_ptr(), db.data_ptr(),
+                                                ws.data_ptr(), need, st), "wgrad")
+
+        def c_fwd():
+            lib.check(L.odvae_weight4x4_reorder_f32(wp.data_ptr(), wg.data_ptr(), cg, cin, 1, st), "reorder")
+            lib.check(L.odvae_im2col4x4_f32(x.data_ptr(), cols.data_ptr(), batch, si, si, cin, so, so, stride, st), "im2col")
+            ops.gemm(0, 1, m, cg, k, 1.0, cols, k, 0, wg, k, 0, yg, cg, 0, bp)
+
+        def c_dgrad():
+            ops.gemm(0, 0, m, k, cg, 1.0, dyg, cg, 0, wg, k, 0, dcols, k, 0)
+            lib.check(L.odvae_col2im4x4_f32(dcols.data_ptr(), dx.data_ptr(), batch, si, si, cin, so, so, stride, st), "col2im")
+
+        def c_wgrad():
+            ops.gemm(1, 0, cg, k, m, 1.0, dyg, cg, 0, cols, k, 0, dwg, k, 0)
+            lib.check(L.odvae_weight4x4_reorder_f32(dwg.data_ptr(), dwo.data_ptr(), cg, cin, 0, st), "reorder")
+            ops._colsum(dyg, m, cg)
+        flop = 2.0 * 16 * cin * cout * batch * so * so
+        row = {"cin": cin, "cout": cout, "stride": stride, "in": si, "out": so, "gflop": flop / 1e9}
+        for name, fi, fc in (("fwd", i_fwd, c_fwd), ("dgrad", i_dgrad, c_dgrad), ("wgrad", i_wgrad, c_wgrad)):
+            fi(); fc(); torch.cuda.synchronize()
+            ti, tc = [], []
+            for _ in range(rounds):
+                ti.append(window(fi, reps)); tc.append(window(fc, reps))
+            row[name], row[name + "_im2col"] = med(ti), med(tc)
+            row[name]["tflops"] = flop / row[name]["median_ms"] / 1e9
+            row[name + "_im2col"]["tflops"] = flop / row[name + "_im2col"]["median_ms"] / 1e9
+        rows.append(row)
+    return rows
 
 
 def per_layer(batch, res, reps, rounds):
@@ -171,11 +243,21 @@ def main():
     for name, r in rec["whole_net"].items():
         print("%-15s: median %8.3f ms, mean %8.3f (min %.3f .. max %.3f)" % (name, r["median_ms"], r["mean_ms"], r["min_ms"], r["max_ms"]), flush=True)
     for what in ("disc_step", "gen_side"):
-        f, b = rec["whole_net"]["f32 " + what], rec["whole_net"]["bf16 " + what]
-        print("%s: bf16 / f32 = %.3f; ranges %s" % (what, b["median_ms"] / f["median_ms"],
-                                                    "apart" if b["max_ms"] < f["min_ms"] or f["max_ms"] < b["min_ms"] else "OVERLAP"))
+        f = rec["whole_net"]["f32 " + what]
+        for arm in ("f32 implicit", "bf16"):
+            b = rec["whole_net"]["%s %s" % (arm, what)]
+            print("%s: %s / f32 = %.3f; ranges %s" % (what, arm, b["median_ms"] / f["median_ms"],
+                                                      "apart" if b["max_ms"] < f["min_ms"] or f["max_ms"] < b["min_ms"] else "OVERLAP"))
     for name, r in rec["peak_memory"].items():
-        print("peak memory of one discriminator step, %-4s: %9.1f MB over %.1f MB resident" % (name, r["peak_over_resident_mb"], r["resident_mb"]))
+        print("peak memory of one discriminator step, %-12s: %9.1f MB over %.1f MB resident" % (name, r["peak_over_resident_mb"], r["resident_mb"]))
+    rec["layers_f32"] = per_layer_f32(a.batch, a.res, max(a.reps, 10), a.rounds)
+    for r in rec["layers_f32"]:
+        line = "f32 %4d -> %4d s%d %3d -> %3d %8.1f GFLOP |" % (r["cin"], r["cout"], r["stride"], r["in"], r["out"], r["gflop"])
+        for k in ("fwd", "dgrad", "wgrad"):
+            i, c = r[k], r[k + "_im2col"]
+            line += " %s implicit %7.3f ms (%.3f .. %.3f) %5.1f TFLOP/s, im2col %7.3f ms (%.3f .. %.3f) |" % (
+                k, i["median_ms"], i["min_ms"], i["max_ms"], i["tflops"], c["median_ms"], c["min_ms"], c["max_ms"])
+        print(line, flush=True)
     rec["layers"] = per_layer(a.batch, a.res, max(a.reps, 10), a.rounds)
     for r in rec["layers"]:
         line = "%4d -> %4d s%d %3d -> %3d %8.1f GFLOP |" % (r["cin"], r["cout"], r["stride"], r["in"], r["out"], r["gflop"])
