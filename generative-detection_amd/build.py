@@ -1,4 +1,5 @@
 """Builds libodvae_hip.so (gfx950) in-tree with hipcc.  No torch headers: the library is a plain C ABI."""
+import glob
 import os
 import subprocess
 import sys
@@ -6,6 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")   # odvae_hip.h: every source compiles against the public declarations
 OBJ_DIR = os.path.join(HERE, "build")
 LIB_PATH = os.path.join(HERE, "libodvae_hip.so")
 HIP_SOURCES = ["gemm_f32.hip", "gemm_f32_split.hip", "conv3x3_f32.hip", "conv3x3_wino_f32.hip", "conv3x3_wino4_f32.hip", "conv3x3_wgrad_f32.hip", "conv4x4_wgrad_f32.hip", "conv3x3_wgrad_wino_f32.hip", "groupnorm.hip", "elementwise.hip",
@@ -14,7 +16,7 @@ HIP_SOURCES = ["gemm_f32.hip", "gemm_f32_split.hip", "conv3x3_f32.hip", "conv3x3
                "flash_attn_f32.hip", "linattn_f32.hip", "anomaly.hip"]
 CXX_SOURCES = ["runtime.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", CSRC]
+FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", CSRC, "-I", INCLUDE]
 # Per-file code-generation switches (none in use).  Tried on flash_attn_bf16.hip: `-mllvm -amdgpu-mfma-vgpr-form=1` removes the
 # 256 v_accvgpr_read/write per 32 MFMAs that hipcc's default register split puts at the loop back-edge of the attention kernels
 # (592 vs 565 TFLOP/s forward), but the D >= 256 forward kernels then return wrong results (tests/test_bf16_gpu.py), so it stays off.
@@ -31,10 +33,15 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _deps(src):
+    """What an object is rebuilt for: its source, every header there is (not a list of them: a new header cannot leave stale
+    objects behind), the public header and this file (the flags)."""
+    return [src, os.path.join(INCLUDE, "odvae_hip.h"), os.path.abspath(__file__)] + glob.glob(os.path.join(CSRC, "*.h"))
+
+
 def _compile(src):
     obj = os.path.join(OBJ_DIR, os.path.basename(src) + ".o")
-    deps = [src, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "bf16_common.h"), os.path.join(CSRC, "gn_finalize.h"), os.path.join(CSRC, "dropout_mask.h"), os.path.join(CSRC, "gemm_f32_tile.h"), os.path.join(CSRC, "resample.h"), os.path.abspath(__file__)]
-    if _stale(obj, deps):
+    if _stale(obj, _deps(src)):
         cmd = [HIPCC] + FLAGS + PER_FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
@@ -45,7 +52,10 @@ def _compile(src):
 def build_library(force=False, verbose=False):
     """Compile every kernel source for gfx950 and link the shared library.  Returns its path."""
     os.makedirs(OBJ_DIR, exist_ok=True)
-    srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES + CXX_SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES + CXX_SOURCES]
+    missing = [s for s in srcs if not os.path.exists(s)]
+    if missing:
+        raise FileNotFoundError("listed in HIP_SOURCES / CXX_SOURCES but not in %s: %s" % (CSRC, ", ".join(map(os.path.basename, missing))))
     if force:
         for f in os.listdir(OBJ_DIR):
             os.remove(os.path.join(OBJ_DIR, f))

@@ -34,8 +34,6 @@ typedef const __attribute__((address_space(1))) u32x4 gu32x4;
 typedef const __attribute__((address_space(1))) uint32_t gu32;
 typedef const __attribute__((address_space(1))) uint16_t gu16;
 
-struct OdvaeAnomalyTensor { const void* ptr; int64_t numel; int32_t dtype; int32_t output_index; };   // include/odvae_hip.h
-
 // Lane maxima of the magnitude bits.  f32: lo only.  bf16: lo holds the low halves (& 0x7fff), hi the high halves (& 0x7fff0000).
 __device__ __forceinline__ void acc_f32(const u32x4 w, uint32_t& lo) {
   lo = max(lo, max(max(w.x & 0x7fffffffu, w.y & 0x7fffffffu), max(w.z & 0x7fffffffu, w.w & 0x7fffffffu)));

@@ -13,10 +13,6 @@ struct GnB {
   int N, HW, C, G, cpg, octs, pix_per_pass, chunks, pix_per_chunk;
 };
 
-// 1 / (1 + e^-u) with v_rcp_f32 (1 ulp) instead of an IEEE division (ten instructions): these kernels carry 18-30 vector instructions per
-// element beside their loads, and the bf16 ones move two elements per 4 bytes -- the division alone was a third of the arithmetic
-__device__ __forceinline__ float sigmoid_f(float u) { return __builtin_amdgcn_rcpf(1.f + __expf(-u)); }
-__device__ __forceinline__ float swish_f(float u) { return u * sigmoid_f(u); }
 __device__ __forceinline__ float act_grad_f(float u, bool swish) {
   if (!swish) return 1.f;
   const float sg = sigmoid_f(u);
@@ -100,7 +96,6 @@ __device__ __forceinline__ void stnt(u32x4* p, u32x4 v) { __builtin_nontemporal_
 
 // ResnetBlock dropout (dropout_mask.h): a 16-byte load is exactly one octet, so a thread makes one Philox call per load.  The DROP = false
 // instantiations of the three kernels (D = GnNoDrop, an empty last argument) have the instruction streams they had before the dropout existed.
-struct GnNoDrop {};
 template <bool DROP, typename D>
 __device__ __forceinline__ void drop8(float (&a)[8], const D& d, int64_t oct) {
   if constexpr (DROP) {

@@ -5,15 +5,11 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <algorithm>
+#include "odvae_hip.h"   // include/: the one declaration of every entry point and of the ODVAE_* codes; each definition is checked against it
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-#define ODVAE_OK 0
-#define ODVAE_ERR_ARG 1
-#define ODVAE_ERR_WORKSPACE 2
-#define ODVAE_ERR_HIP 3
 
 // last error text, readable through odvae_last_error()
 extern "C" void odvae_set_error(const char* fmt, ...);
@@ -44,6 +40,12 @@ struct OdvaePackItem { const float* w; void* fwd; void* dgr; int Cout, Cin, taps
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+constexpr int round_up(int a, int b) { return (a + b - 1) / b * b; }
+// blocks of 256 threads for a grid-stride loop over `items`
+static inline int grid_1d(int64_t items, int cap = 8192) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div64(items, 256), 1), cap); }
+// blocks of the BatchNorm / ActNorm column statistics (gan_f32.hip, gan_bf16.hip): odvae_batchnorm_workspace_bytes sizes the workspace of
+// both forms by it
+static inline int stat_blocks(int64_t rows) { return (int)std::min<int64_t>(std::max<int64_t>(rows / 128, 1), 1024); }
 
 // One exact-f32 matrix-core step: D(32x32) += A(32x2) * B(2x32).
 // lane l supplies A[i = l&31][k = l>>5] and B[k = l>>5][j = l&31];
@@ -88,8 +90,9 @@ __device__ __forceinline__ float wave_min(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
   return v;
 }
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+
+// 1 / (1 + e^-u) with v_rcp_f32 (1 ulp) instead of an IEEE division (ten instructions): the GroupNorm kernels (groupnorm.hip, bf16_ops.hip)
+// carry 18-30 vector instructions per element beside their loads, and the bf16 ones move two elements per 4 bytes -- the division alone
+// was a third of the arithmetic
+__device__ __forceinline__ float sigmoid_f(float u) { return __builtin_amdgcn_rcpf(1.f + __expf(-u)); }
+__device__ __forceinline__ float swish_f(float u) { return u * sigmoid_f(u); }

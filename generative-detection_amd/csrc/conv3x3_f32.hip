@@ -566,8 +566,6 @@ __global__ __launch_bounds__(256) void conv3x3_thin_out_kernel(ConvParams p) {
   }
 }
 
-constexpr int round_up(int a, int b) { return (a + b - 1) / b * b; }
-
 }  // namespace
 
 extern "C" {

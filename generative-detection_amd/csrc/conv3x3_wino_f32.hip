@@ -526,15 +526,13 @@ __global__ void conv3x3_pack_wino_kernel(const float* __restrict__ w, int Cout, 
   }
 }
 
-constexpr int round_up_i(int a, int b) { return (a + b - 1) / b * b; }
-
 }  // namespace
 
 extern "C" {
 
 // pack sizes: reduction axis padded to 16, output axis to 64
-int odvae_conv3x3_wino_reduce_pad(int c_reduce) { return round_up_i(c_reduce, KC); }
-int odvae_conv3x3_wino_out_pad(int c_out) { return round_up_i(c_out, BN); }
+int odvae_conv3x3_wino_reduce_pad(int c_reduce) { return round_up(c_reduce, KC); }
+int odvae_conv3x3_wino_out_pad(int c_out) { return round_up(c_out, BN); }
 size_t odvae_conv3x3_wino_pack_floats(int c_reduce, int c_out) {
   return (size_t)16 * odvae_conv3x3_wino_reduce_pad(c_reduce) * odvae_conv3x3_wino_out_pad(c_out);
 }

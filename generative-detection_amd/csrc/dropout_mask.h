@@ -19,6 +19,10 @@ struct GnDrop {
   unsigned key0, key1; // the seed's low / high word
 };
 
+// What a DROP = false kernel takes in GnDrop's place: an empty last argument, so those instantiations have the instruction streams they
+// had before the dropout existed.  File-local like the kernels it parametrises (each includer keeps them in its unnamed namespace).
+namespace { struct GnNoDrop {}; }
+
 // p in [0, 1] (checked by the caller)
 static inline GnDrop make_gn_drop(double p, unsigned long long seed) {
   GnDrop d;

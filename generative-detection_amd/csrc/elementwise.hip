@@ -5,8 +5,6 @@
 
 namespace {
 
-int grid_1d(int64_t items, int cap = 8192) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div64(items, 256), 1), cap); }
-
 // block-wide sum of one float per thread (256 threads); result valid in thread 0
 __device__ __forceinline__ float block_sum(float v, float* sh) {
   v = wave_sum(v);
@@ -350,7 +348,7 @@ __global__ void rowsum_final_kernel(const float* __restrict__ part, int nblk, fl
   const int n = blockIdx.x;
   double s = 0.0;
   for (int i = threadIdx.x; i < nblk; i += 64) s += (double)part[(int64_t)n * nblk + i];
-  s = wave_sum_d(s);
+  s = wave_sum_f64(s);
   if (threadIdx.x == 0) out[n] = (float)s;
 }
 // dxr = g[n] * sign(xr*m - x*m) * m
@@ -430,7 +428,7 @@ __global__ void colsum_final_kernel(const float* __restrict__ part, int nblk, in
   if (c >= C) return;
   double s = 0.0;
   for (int b = threadIdx.x & 63; b < nblk; b += 64) s += (double)part[(int64_t)b * C + c];
-  s = wave_sum_d(s);
+  s = wave_sum_f64(s);
   if ((threadIdx.x & 63) == 0) out[c] = (float)s;
 }
 
@@ -451,7 +449,7 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restr
 __global__ void norm_final_kernel(const float* __restrict__ part, int nblk, float max_norm, float* __restrict__ out) {
   double s = 0.0;
   for (int i = threadIdx.x; i < nblk; i += 64) s += (double)part[i];
-  s = wave_sum_d(s);
+  s = wave_sum_f64(s);
   if (threadIdx.x == 0) {
     const float nrm = (float)sqrt(s);
     out[0] = nrm;

@@ -18,8 +18,6 @@
 // No atomics: every output element is written by exactly one lane, so two runs give identical bits.
 #include "common.h"
 
-extern "C" int odvae_rowdot_f32(const float* a, const float* b, int64_t rows, int cols, float* out, void* stream);  // elementwise.hip
-
 namespace {
 
 constexpr int WAVE_ROWS = 16;              // stationary rows per wave

@@ -8,13 +8,7 @@
 // The 4x4 convolutions themselves are modes 5 / 6 / 7 of conv_bf16.hip and modes 5 / 6 of conv_wgrad_bf16.hip.
 #include "bf16_common.h"
 
-extern "C" size_t odvae_batchnorm_workspace_bytes(int64_t rows, int C);   // gan_f32.hip
-
 namespace {
-
-int grid_1d(int64_t items, int cap = 8192) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div64(items, 256), 1), cap); }
-// (the same block count as gan_f32.hip: odvae_batchnorm_workspace_bytes sizes the workspace of both forms)
-int stat_blocks(int64_t rows) { return (int)std::min<int64_t>(std::max<int64_t>(rows / 128, 1), 1024); }
 
 // part[blk][2][C] as bn_colstats_kernel: MODE 0 sums of (d, d^2), d = x - x[0][c]; MODE 1 sums of (g, g * xhat).
 // V = 2 (C even): a thread keeps two adjacent channels and reads them as one dword.

@@ -13,8 +13,6 @@
 
 namespace {
 
-int grid_1d(int64_t items, int cap = 8192) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div64(items, 256), 1), cap); }
-
 // cols[(n,oy,ox)][(kh*4+kw)*C + c] = x[n][oy*S-1+kh][ox*S-1+kw][c]  (zero outside)
 __global__ __launch_bounds__(256) void im2col4x4_kernel(const float* __restrict__ x, float* __restrict__ cols,
                                                          int N, int Hi, int Wi, int C, int Ho, int Wo, int S) {
@@ -214,8 +212,6 @@ __global__ __launch_bounds__(256) void lrelu_bwd_kernel(const float* __restrict_
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     dx[i] = dy[i] * (x[i] > 0.f ? 1.f : slope);
 }
-
-int stat_blocks(int64_t rows) { return (int)std::min<int64_t>(std::max<int64_t>(rows / 128, 1), 1024); }
 
 // ---- ActNorm + LeakyReLU ([UPSTREAM] taming/modules/util.py ActNorm, NLayerDiscriminator(use_actnorm=True)) -----------------------
 // h = scale[c] * (x + loc[c]), y = lrelu(h).  loc and scale are parameters: nothing is reduced in the forward, and in the backward dx

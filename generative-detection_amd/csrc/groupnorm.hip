@@ -24,11 +24,6 @@ struct GnShape {
   int chunks, pix_per_chunk;
 };
 
-// 1 / (1 + e^-u) with v_rcp_f32 (1 ulp) instead of an IEEE division (ten instructions): these kernels carry 18-30 vector instructions per
-// element beside their loads, and the bf16 ones move two elements per 4 bytes -- the division alone was a third of the arithmetic
-__device__ __forceinline__ float sigmoid_f(float u) { return __builtin_amdgcn_rcpf(1.f + __expf(-u)); }
-__device__ __forceinline__ float swish_f(float u) { return u * sigmoid_f(u); }
-
 // streaming accesses of the apply passes: every byte is touched once by this kernel and next by another one a gigabyte later
 typedef float gn_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld_stream(const float4* p) {
@@ -116,7 +111,6 @@ __device__ __forceinline__ float4 gn_apply_quad(const float4 v, const GnQuad& k)
 
 // ResnetBlock dropout (dropout_mask.h) on a channel quad: v * keep * scale, the mask re-made from (seed, p) and the quad's index in the
 // whole tensor.  A thread computes the Philox call of its quad's octet and uses half of it (profiles/resnet_dropout.md).
-struct GnNoDrop {};      // what a DROP = false kernel takes in GnDrop's place
 template <bool DROP, typename D>
 __device__ __forceinline__ float4 gn_drop4(const float4 v, const D& d, int64_t quad) {
   if constexpr (DROP) {
@@ -705,8 +699,6 @@ int odvae_groupnorm_recentred(int add) {
   }
   return (int)v;
 }
-
-int odvae_attn_softmax_fallbacks(int add);   // elementwise.hip
 
 // Both device-side health counters in one call (synchronises the device): gn_timeouts != 0 means a GroupNorm backward ran with a team
 // barrier that gave up -- its gradients are WRONG and the run must stop; attn_fallbacks counts exact-softmax fallbacks (correct, slower).

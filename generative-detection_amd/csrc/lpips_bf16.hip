@@ -10,8 +10,6 @@
 
 namespace {
 
-int grid_1d(int64_t items, int cap = 8192) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div64(items, 256), 1), cap); }
-
 // y bf16 [npix][8] = ((x - shift[c]) / scale[c], c < C; 0 for the padding channels), x f32 [npix][C], C <= 8
 __global__ __launch_bounds__(256) void scaling_layer_bf16_kernel(const float* __restrict__ x, const float* __restrict__ shift,
                                                                  const float* __restrict__ scale, bf16_t* __restrict__ y, int64_t npix, int C) {
@@ -186,7 +184,7 @@ __global__ void lpips_mean_final_bf16_kernel(const float* __restrict__ part, int
   const int n = blockIdx.x;
   double s = 0.0;
   for (int i = threadIdx.x; i < nblk; i += 64) s += (double)part[(int64_t)n * nblk + i];
-  s = wave_sum_d(s);
+  s = wave_sum_f64(s);
   if (threadIdx.x == 0) out[n] = (float)(s * (double)inv_hw);
 }
 

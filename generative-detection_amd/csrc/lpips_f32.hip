@@ -9,8 +9,6 @@
 
 namespace {
 
-int grid_1d(int64_t items, int cap = 8192) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div64(items, 256), 1), cap); }
-
 // y = (x - shift[c]) / scale[c];  bwd (INV): y = x / scale[c]
 template <bool BWD>
 __global__ __launch_bounds__(256) void scaling_layer_kernel(const float* __restrict__ x, const float* __restrict__ shift,
@@ -126,7 +124,7 @@ __global__ void lpips_mean_final_kernel(const float* __restrict__ part, int nblk
   const int n = blockIdx.x;
   double s = 0.0;
   for (int i = threadIdx.x; i < nblk; i += 64) s += (double)part[(int64_t)n * nblk + i];
-  s = wave_sum_d(s);
+  s = wave_sum_f64(s);
   if (threadIdx.x == 0) out[n] = (float)(s * (double)inv_hw);
 }
 

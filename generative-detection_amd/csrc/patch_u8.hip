@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void patch_reduce_resize_kernel(PatchParams p)
 extern "C" int odvae_patch_table_ints(int S) { return S * TAB_INTS; }
 
 extern "C" int odvae_patch_crop_resize_u8(const void* d_images, const void* d_geom, const void* d_mask_rect, const void* d_tables,
-                                          int n_slots, int B, int S, void* patch, void* mask, hipStream_t stream) {
+                                          int n_slots, int B, int S, void* patch, void* mask, void* stream) {
   ODVAE_CHECK_ARG(d_images && d_geom && d_mask_rect && d_tables && patch && mask, "patch_crop_resize: null pointer");
   ODVAE_CHECK_ARG(B > 0 && S > 0 && S <= 4096 && n_slots > 0, "patch_crop_resize: bad sizes");   // images: >= 2 pixels each
   PatchParams p;
@@ -207,13 +207,13 @@ extern "C" int odvae_patch_crop_resize_u8(const void* d_images, const void* d_ge
   p.tables = (const int32_t*)d_tables; p.mults = nullptr; p.patch = (float*)patch; p.mask = (float*)mask;
   p.B = B; p.S = S; p.n_slots = n_slots;
   ODVAE_CHECK_ARG(B <= 65535 && (int64_t)B * S * S < (int64_t)1 << 31, "patch_crop_resize: batch too large for one launch");
-  hipLaunchKernelGGL(patch_crop_resize_kernel, dim3(ceil_div(S, 64), ceil_div(S, 4), B), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(patch_crop_resize_kernel, dim3(ceil_div(S, 64), ceil_div(S, 4), B), dim3(256), 0, static_cast<hipStream_t>(stream), p);
   ODVAE_LAUNCH_CHECK("patch_crop_resize_kernel");
   return 0;
 }
 
 extern "C" int odvae_patch_reduce_resize_u8(const void* d_images, const void* d_geom, const void* d_mask_rect, const void* d_tables,
-                                            const void* d_mults, int n_slots, int B, int S, void* patch, void* mask, hipStream_t stream) {
+                                            const void* d_mults, int n_slots, int B, int S, void* patch, void* mask, void* stream) {
   ODVAE_CHECK_ARG(d_images && d_geom && d_mask_rect && d_tables && d_mults && patch && mask, "patch_reduce_resize: null pointer");
   ODVAE_CHECK_ARG(B > 0 && S > 0 && S <= 4096 && n_slots > 0, "patch_reduce_resize: bad sizes");
   PatchParams p;
@@ -221,7 +221,7 @@ extern "C" int odvae_patch_reduce_resize_u8(const void* d_images, const void* d_
   p.tables = (const int32_t*)d_tables; p.mults = (const uint32_t*)d_mults; p.patch = (float*)patch; p.mask = (float*)mask;
   p.B = B; p.S = S; p.n_slots = n_slots;
   ODVAE_CHECK_ARG(B <= 65535 && (int64_t)B * S * S < (int64_t)1 << 31, "patch_reduce_resize: batch too large for one launch");
-  hipLaunchKernelGGL(patch_reduce_resize_kernel, dim3(ceil_div(S, 64), ceil_div(S, 4), B), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL(patch_reduce_resize_kernel, dim3(ceil_div(S, 64), ceil_div(S, 4), B), dim3(256), 0, static_cast<hipStream_t>(stream), p);
   ODVAE_LAUNCH_CHECK("patch_reduce_resize_kernel");
   return 0;
 }

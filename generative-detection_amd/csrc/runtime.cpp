@@ -2,6 +2,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+#include "odvae_hip.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -19,8 +20,8 @@ void odvae_set_error(const char* fmt, ...) {
 // text of the last failing call on this thread ("" if none)
 const char* odvae_last_error(void) { return g_err; }
 
-// ABI version of include/odvae_hip.h this library was built against
-int odvae_abi_version(void) { return 4; }
+// ABI version of include/odvae_hip.h this library was built against: the header's #define is the only place the number is written
+int odvae_abi_version(void) { return ODVAE_ABI_VERSION; }
 
 const char* odvae_target_arch(void) { return "gfx950"; }
 

@@ -1,5 +1,6 @@
-"""ctypes binding of libodvae_hip.so (include/odvae_hip.h).  The product path has no CPU fallback:
-every op raises if the library is missing or the tensors are not on a HIP device."""
+"""ctypes binding of libodvae_hip.so, derived from include/odvae_hip.h at import: the prototypes and the ABI version are
+parsed from the header, never written out here.  The product path has no CPU fallback: every op raises if the library is
+missing or the tensors are not on a HIP device."""
 import ctypes
 import os
 import re
@@ -11,202 +12,72 @@ LIB_PATH = os.path.join(_HERE, "libodvae_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "odvae_hip.h")
 
 _c = ctypes
-_P, _I, _L, _F, _Z = _c.c_void_p, _c.c_int, _c.c_int64, _c.c_float, _c.c_size_t
-_D, _U64 = _c.c_double, _c.c_uint64      # (p, seed) of the GroupNorm dropout forms
+_I = _c.c_int
 
-ABI_VERSION = 4   # == ODVAE_ABI_VERSION in include/odvae_hip.h; bumped whenever the exported surface changes
-
-# name -> (restype, argtypes); mirrors include/odvae_hip.h one to one (tests/test_abi.py checks that)
-PROTOTYPES = {
-    "odvae_last_error": (_c.c_char_p, []),
-    "odvae_abi_version": (_I, []),
-    "odvae_target_arch": (_c.c_char_p, []),
-    "odvae_gemm_f32_workspace_bytes": (_Z, [_I, _I, _I, _I]),
-    "odvae_gemm_select_staging": (_I, [_I]),
-    "odvae_gemm_f32": (_I, [_I, _I, _I, _I, _I, _F, _P, _I, _L, _P, _I, _L, _P, _I, _L, _P, _P, _I, _P, _Z, _P]),
-    "odvae_gemm_softmax_bwd_f32": (_I, [_I, _I, _I, _F, _P, _I, _L, _P, _I, _L, _P, _P, _L, _P, _I, _L, _I, _P]),
-    "odvae_rowdot_f32": (_I, [_P, _P, _L, _I, _P, _P]),
-    "odvae_attn_row_bound_f32": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
-    "odvae_gemm_exp_bound_f32": (_I, [_I, _I, _I, _F, _P, _I, _L, _P, _I, _L, _P, _L, _P, _I, _L, _I, _P]),
-    "odvae_gemm_rownorm_f32": (_I, [_I, _I, _I, _P, _I, _L, _P, _I, _L, _P, _I, _L, _P, _L, _P, _I, _P]),
-    "odvae_gemm_pred_f32": (_I, [_I, _I, _I, _I, _I, _F, _P, _I, _L, _P, _I, _L, _P, _I, _L, _I, _P, _P]),
-    "odvae_softmax_rows_pred_f32": (_I, [_P, _P, _L, _I, _F, _P, _P, _P]),
-    "odvae_rowdot_scale_f32": (_I, [_P, _P, _P, _L, _I, _P, _P, _P]),
-    "odvae_gemm_softmax_bwd_scaled_f32": (_I, [_I, _I, _I, _F, _P, _I, _L, _P, _I, _L, _P, _P, _P, _L, _P, _I, _L, _I, _P]),
-    "odvae_conv3x3_pack_reduce_pad": (_I, [_I]),
-    "odvae_conv3x3_pack_out_pad": (_I, [_I]),
-    "odvae_conv3x3_pack_floats": (_Z, [_I, _I]),
-    "odvae_conv3x3_pack_f32": (_I, [_P, _I, _I, _P, _P, _P]),
-    "odvae_conv3x3_up_pack_floats": (_Z, [_I, _I]),
-    "odvae_conv3x3_pack_up_f32": (_I, [_P, _I, _I, _P, _P, _P]),
-    "odvae_conv3x3_wino_reduce_pad": (_I, [_I]),
-    "odvae_conv3x3_wino_out_pad": (_I, [_I]),
-    "odvae_conv3x3_wino_pack_floats": (_Z, [_I, _I]),
-    "odvae_conv3x3_pack_wino_f32": (_I, [_P, _I, _I, _P, _P, _P]),
-    "odvae_conv3x3_wino_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
-    "odvae_conv3x3_wino4_reduce_pad": (_I, [_I]),
-    "odvae_conv3x3_wino4_out_pad": (_I, [_I]),
-    "odvae_conv3x3_wino4_pack_floats": (_Z, [_I, _I]),
-    "odvae_conv3x3_wino4_supported": (_I, [_I, _I, _I, _I]),
-    "odvae_conv3x3_pack_wino4_f32": (_I, [_P, _I, _I, _P, _P, _P]),
-    "odvae_conv3x3_pack_wino_batch": (_I, [_P, _I, _P]),
-    "odvae_conv3x3_pack_wino4_batch": (_I, [_P, _I, _P]),
-    "odvae_conv3x3_wino4_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
-    "odvae_conv3x3_wino4_stats_chunks": (_I, [_I, _I]),
-    "odvae_conv3x3_wino4_stats_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
-    "odvae_conv3x3_wino4_up_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
-    "odvae_conv3x3_wino4_pool_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P]),
-    "odvae_conv3x3_wino4_gnbwd_f32": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
-    "odvae_conv3x3_f32": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
-    "odvae_conv3x3_wgrad_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "odvae_conv3x3_wgrad_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
-    "odvae_conv3x3_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
-    "odvae_conv3x3_wgrad_wino_supported": (_I, [_I, _I, _I, _I, _I]),
-    "odvae_conv3x3_wgrad_wino_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
-    "odvae_conv3x3_wgrad_wino_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
-    "odvae_conv3x3_wgrad_wino_select": (_I, [_I]),
-    "odvae_groupnorm_workspace_bytes": (_Z, [_I, _I, _I, _I]),
-    "odvae_groupnorm_fwd_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _Z, _P]),
-    "odvae_groupnorm_fwd_partials_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _I, _P]),
-    "odvae_groupnorm_apply_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
-    "odvae_groupnorm_apply_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
-    "odvae_groupnorm_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P]),
-    "odvae_groupnorm_bwd_partials_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
-    "odvae_groupnorm_fwd_drop_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _D, _U64, _P, _P, _P, _P, _Z, _P]),
-    "odvae_groupnorm_fwd_partials_drop_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _D, _U64, _P, _P, _P, _P, _I, _P]),
-    "odvae_groupnorm_apply_drop_f32": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _D, _U64, _P, _P]),
-    "odvae_groupnorm_bwd_drop_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _D, _U64, _P, _P, _P, _P, _P, _Z, _P]),
-    "odvae_groupnorm_select_backward": (_I, [_I]),
-    "odvae_groupnorm_fused_timeouts": (_I, []),
-    "odvae_device_health": (_I, [_P, _P, _I, _I]),
-    "odvae_attn_softmax_fallbacks": (_I, [_I]),
-    "odvae_groupnorm_recentred": (_I, [_I]),
-    "odvae_softmax_rows_f32": (_I, [_P, _P, _L, _I, _F, _P]),
-    "odvae_softmax_rows_bwd_f32": (_I, [_P, _P, _P, _L, _I, _F, _P]),
-    "odvae_upsample2x_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "odvae_avgpool2x2_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
-    "odvae_avgpool2x2_bwd_f32": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "odvae_upsample2x_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
-    "odvae_tanh_f32": (_I, [_P, _P, _L, _P]),
-    "odvae_tanh_bwd_f32": (_I, [_P, _P, _P, _L, _P]),
-    "odvae_rescale_minmax_f32": (_I, [_P, _P, _I, _I, _I, _P, _P, _Z, _P]),
-    "odvae_gaussian_sample_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "odvae_gaussian_kl_f32": (_I, [_P, _P, _I, _I, _I, _P]),
-    "odvae_gaussian_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "odvae_l1_masked_sum_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
-    "odvae_l1_masked_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "odvae_colsum_workspace_bytes": (_Z, [_L, _I]),
-    "odvae_colsum_f32": (_I, [_P, _L, _I, _P, _P, _Z, _P]),
-    "odvae_grad_norm_f32": (_I, [_P, _L, _F, _P, _P, _Z, _P]),
-    "odvae_adam_step_f32": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _P, _P]),
-    "odvae_grad_accumulate_segments_per_launch": (_I, []),
-    "odvae_grad_accumulate_f32": (_I, [_P, _L, _P, _P, _P, _I, _P]),
-    "odvae_nhwc_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _P]),
-    "odvae_mul_mask_f32": (_I, [_P, _P, _P, _L, _I, _P]),
-    "odvae_latent_combine_f32": (_I, [_P, _P, _P, _P, _L, _P]),
-    "odvae_im2col4x4_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "odvae_col2im4x4_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "odvae_weight4x4_reorder_f32": (_I, [_P, _P, _I, _I, _I, _P]),
-    "odvae_conv4x4_f32_supported": (_I, [_I, _I, _I, _I, _I, _I]),
-    "odvae_conv4x4_pack_floats": (_Z, [_I, _I]),
-    "odvae_conv4x4_pack_f32": (_I, [_P, _I, _I, _I, _P, _P, _P]),
-    "odvae_conv4x4_f32": (_I, [_I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P]),
-    "odvae_conv4x4_wgrad_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "odvae_conv4x4_wgrad_f32": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
-    "odvae_conv4x4_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
-    "odvae_batchnorm_workspace_bytes": (_Z, [_L, _I]),
-    "odvae_batchnorm_lrelu_fwd_f32": (_I, [_P, _L, _I, _P, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
-    "odvae_batchnorm_lrelu_bwd_f32": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _Z, _P]),
-    "odvae_actnorm_workspace_bytes": (_Z, [_L, _I]),
-    "odvae_actnorm_init_f32": (_I, [_P, _L, _I, _F, _P, _P, _P, _Z, _P]),
-    "odvae_actnorm_lrelu_fwd_f32": (_I, [_P, _L, _I, _P, _P, _F, _P, _P]),
-    "odvae_actnorm_lrelu_bwd_f32": (_I, [_P, _P, _L, _I, _P, _P, _F, _P, _P, _P, _P, _Z, _P]),
-    "odvae_leaky_relu_f32": (_I, [_P, _P, _F, _L, _P]),
-    "odvae_leaky_relu_bwd_f32": (_I, [_P, _P, _P, _F, _L, _P]),
-    "odvae_scaling_layer_f32": (_I, [_P, _P, _P, _P, _L, _I, _I, _P]),
-    "odvae_maxpool2x2_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "odvae_maxpool2x2_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "odvae_lpips_distance_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
-    "odvae_lpips_distance_bwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "odvae_pose_losses_f32": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
-    "odvae_pose_losses_bwd_f32": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
-    "odvae_linear_workspace_bytes": (_Z, [_I, _I, _I]),
-    "odvae_linear_fwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
-    "odvae_linear_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
-    # bf16 mixed-precision path
-    "odvae_conv_bf16_reduce_pad": (_I, [_I]),
-    "odvae_conv_bf16_out_pad": (_I, [_I]),
-    "odvae_conv_bf16_pack_elems": (_Z, [_I, _I, _I]),
-    "odvae_conv_pack_bf16": (_I, [_P, _I, _I, _I, _P, _P, _P]),
-    "odvae_conv_bf16": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
-    "odvae_conv_bf16_stats_chunks": (_I, [_I, _I]),
-    "odvae_conv_bf16_stats_supported": (_I, [_I, _I]),
-    "odvae_conv_bf16_stats": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
-    "odvae_conv_bf16_relu": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
-    "odvae_conv_bf16_masked": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
-    "odvae_conv_wgrad_bf16_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "odvae_conv_wgrad_bf16_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
-    "odvae_conv4x4_bf16": (_I, [_I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _F, _P]),
-    "odvae_batchnorm_lrelu_fwd_bf16": (_I, [_P, _L, _I, _P, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
-    "odvae_batchnorm_lrelu_bwd_bf16": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _Z, _P]),
-    "odvae_leaky_relu_bwd_bf16": (_I, [_P, _P, _P, _F, _L, _P]),
-    "odvae_conv_wgrad_bf16": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
-    "odvae_flash_attn_supported": (_I, [_I, _I, _I]),
-    "odvae_flash_attn_fwd_bf16": (_I, [_P, _I, _I, _I, _F, _P, _P, _P]),
-    "odvae_flash_attn_bwd_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
-    "odvae_flash_attn_f32_supported": (_I, [_I, _I, _I]),
-    "odvae_flash_attn_fwd_f32": (_I, [_P, _I, _I, _I, _F, _P, _P, _P]),
-    "odvae_flash_attn_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
-    "odvae_linattn_ctx_split": (_I, []),
-    "odvae_linattn_colstats_workspace_bytes": (_Z, [_I, _I, _I]),
-    "odvae_linattn_colstats_f32": (_I, [_P, _I, _L, _I, _I, _I, _P, _P, _P, _Z, _P]),
-    "odvae_linattn_ctx_workspace_bytes": (_Z, [_I, _I, _I]),
-    "odvae_linattn_ctx_f32": (_I, [_P, _P, _I, _L, _P, _P, _I, _I, _I, _P, _P, _Z, _P]),
-    "odvae_linattn_dkv_f32": (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _L, _P]),
-    "odvae_groupnorm_bf16_workspace_bytes": (_Z, [_I, _I, _I, _I]),
-    "odvae_groupnorm_fwd_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _Z, _P]),
-    "odvae_groupnorm_fwd_partials_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P, _P, _I, _P]),
-    "odvae_groupnorm_bwd_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P]),
-    "odvae_groupnorm_fwd_drop_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _D, _U64, _P, _P, _P, _P, _Z, _P]),
-    "odvae_groupnorm_fwd_partials_drop_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _I, _D, _U64, _P, _P, _P, _P, _I, _P]),
-    "odvae_groupnorm_apply_drop_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _D, _U64, _P, _P]),
-    "odvae_groupnorm_bwd_drop_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _D, _U64, _P, _P, _P, _P, _P, _Z, _P]),
-    "odvae_cast_pad_bf16": (_I, [_P, _L, _I, _I, _P, _P]),
-    "odvae_cast_f32_from_bf16": (_I, [_P, _L, _P, _P]),
-    "odvae_upsample2x_bwd_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "odvae_avgpool2x2_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
-    "odvae_avgpool2x2_bwd_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "odvae_upsample2x_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
-    "odvae_colsum_bf16_workspace_bytes": (_Z, [_L, _I]),
-    "odvae_colsum_bf16": (_I, [_P, _L, _I, _P, _P, _Z, _P]),
-    # the LPIPS-style perceptual net on bf16 features (opt-in)
-    "odvae_scaling_layer_bf16": (_I, [_P, _P, _P, _P, _L, _I, _P]),
-    "odvae_relu_bwd_bf16": (_I, [_P, _P, _P, _L, _P]),
-    "odvae_maxpool2x2_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "odvae_maxpool2x2_bwd_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "odvae_lpips_distance_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _Z, _P]),
-    "odvae_lpips_distance_bwd_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "odvae_patch_table_ints": (_I, [_I]),
-    "odvae_patch_crop_resize_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "odvae_patch_reduce_resize_u8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
-    # device-side anomaly detection (anomaly.py); the tensor list is a host array of OdvaeAnomalyTensor
-    "odvae_anomaly_scan": (_I, [_P, _I, _L, _I, _P, _P]),
-    "odvae_anomaly_reset": (_I, [_P, _P]),
-}
+_CTYPES = {"int": _c.c_int, "int64_t": _c.c_int64, "float": _c.c_float, "double": _c.c_double, "size_t": _c.c_size_t,
+           "uint64_t": _c.c_uint64, "unsigned long long": _c.c_uint64}
+_RESTYPES = {"int": _c.c_int, "size_t": _c.c_size_t, "const char*": _c.c_char_p}
 
 
 class HipLibraryError(RuntimeError):
     """libodvae_hip.so is missing, stale or a kernel call failed."""
 
 
-_lib = None
+def _header_text(path):
+    try:
+        with open(path) as f:
+            return f.read()
+    except OSError as e:
+        raise HipLibraryError("C ABI header %s cannot be read: %s" % (path, e)) from e
+
+
+def parse_header(text):
+    """name -> (restype, argtypes) of every `ret odvae_name(params);` in the text of a C header.  Every pointer or array
+    parameter binds as c_void_p; a type the tables above do not know raises, so a new one cannot bind as int unnoticed."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([^;{}()]*?)\b(odvae_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        decl = "%s %s(%s)" % (" ".join(ret.split()), name, " ".join(params.split()))
+        ret = re.sub(r"\s*\*\s*", "*", " ".join(ret.split()))
+        if ret not in _RESTYPES or name in protos:
+            raise HipLibraryError("header declaration %r: %s" % (decl, "declared twice" if name in protos else "unknown return type"))
+        args = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            if "*" in param or "[" in param:
+                args.append(_c.c_void_p)
+                continue
+            words = param.split()
+            ctype = _CTYPES.get(" ".join(words[:-1])) or _CTYPES.get(" ".join(words))    # with or without a parameter name
+            if ctype is None:
+                raise HipLibraryError("header declaration %r: unknown parameter type %r" % (decl, " ".join(words)))
+            args.append(ctype)
+        protos[name] = (_RESTYPES[ret], args)
+    stray = set(re.findall(r"\b(odvae_[a-z0-9_]+)\s*\(", text)) - set(protos)
+    if stray:
+        raise HipLibraryError("header mentions %s outside a declaration of the form `ret odvae_name(params);`" % sorted(stray))
+    return protos
 
 
 def header_symbols(path=HEADER_PATH):
     """Function names declared in include/odvae_hip.h."""
-    text = open(path).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(odvae_[a-z0-9_]+)\s*\(", text)))
+    return sorted(parse_header(_header_text(path)))
+
+
+def _abi_version(text):
+    m = re.search(r"^[ \t]*#[ \t]*define[ \t]+ODVAE_ABI_VERSION[ \t]+(\d+)", text, flags=re.M)
+    if m is None:
+        raise HipLibraryError("%s does not #define ODVAE_ABI_VERSION" % HEADER_PATH)
+    return int(m.group(1))
+
+
+# The header is the one declaration of the C ABI: the sources compile against it (csrc/common.h includes it) and the binding
+# is derived from it here, at import.  name -> (restype, argtypes)
+PROTOTYPES = parse_header(_header_text(HEADER_PATH))
+ABI_VERSION = _abi_version(_header_text(HEADER_PATH))   # the header's #define; odvae_abi_version() returns the same macro
+
+
+_lib = None
 
 
 def load():
