@@ -62,10 +62,12 @@ __global__ __launch_bounds__(256) void pose_losses_kernel(PoseP p) {
     for (int i = 0; i < 4; ++i) {
       float g, t;
       if (i == 3 && p.yaw) {
-        const float d = __sinf(dp[3]) - __sinf(p.pose_gt[b * 4 + 3]);
+        // sinf / cosf with range reduction: dec_pose[:, 3] is a raw linear output, and the native v_sin_f32 path loses about
+        // 1e-7 |yaw| rad of phase (and its domain ends at 512 pi)
+        const float d = sinf(dp[3]) - sinf(p.pose_gt[b * 4 + 3]);
         const float ad = fabsf(d);
         t = ad < 1.f ? 0.5f * d * d : ad - 0.5f;                               // SmoothL1Loss(beta = 1)
-        g = (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * __cosf(dp[3]);
+        g = (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * cosf(dp[3]);
       } else {
         t = elem_loss(dp[i] - p.pose_gt[b * 4 + i], p.l2, g);
       }
@@ -77,14 +79,16 @@ __global__ __launch_bounds__(256) void pose_losses_kernel(PoseP p) {
     // sigmoid focal loss over the class logits; one_hot(target, NC + 1)[:, :NC]: class id NC has no positive column
     for (int k = 0; k < p.NC; ++k) {
       const float x = dp[8 + k], t = cls == k ? 1.f : 0.f;
-      const float pr = 1.f / (1.f + __expf(-x));
-      const float pt = (1.f - pr) * t + pr * (1.f - t);
+      const float pr = 1.f / (1.f + expf(-x));      // expf: with gamma == 0 nothing hides the |x| ulps of __expf at a logit of -50
+      const float pt = (1.f - pr) * t + pr * (1.f - t), qt = pr * t + (1.f - pr) * (1.f - t);      // pt and 1 - pt
       const float aw = p.alpha * t + (1.f - p.alpha) * (1.f - t);
-      const float ptg1 = p.gamma == 2.f ? pt : __powf(pt, p.gamma - 1.f);
-      const float fw = aw * ptg1 * pt;
-      const float bce = fmaxf(x, 0.f) - x * t + __logf(1.f + __expf(-fabsf(x)));
+      // pt^gamma as torch's pow has it (0^0 = 1); pt is exactly 0 for a logit past +-88.  Its derivative in the form
+      // gamma pt^gamma (1 - pt) (1 - 2t): pt^(gamma - 1) never appears, so gamma <= 1 stays finite at pt == 0
+      const float ptg = p.gamma == 2.f ? pt * pt : (p.gamma == 1.f ? pt : (p.gamma == 0.f ? 1.f : powf(pt, p.gamma)));
+      const float fw = aw * ptg;
+      const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
       s_cls += bce * fw;
-      j1[8 + k] = ((pr - t) * fw + bce * aw * p.gamma * ptg1 * (1.f - 2.f * t) * pr * (1.f - pr)) * inv_cls;
+      j1[8 + k] = ((pr - t) * fw + bce * fw * p.gamma * qt * (1.f - 2.f * t)) * inv_cls;
     }
     for (int j = 0; j < 3; ++j) {
       const float d = dp[4 + j] - p.bbox_gt[b * 3 + j];

@@ -231,7 +231,9 @@ def latent_combine(z, mask=None, add=None):
 # ------------------------------------------------------------------------------------------------------
 class _PoseLosses(Function):
     """out[9] = pose, class, bbox, fill, kl_bbox losses + the logged per-component means (t1, t2, t3, v3) of
-    src/modules/losses/contperceptual.py:111-132,176-212.  Differentiable w.r.t. dec_pose and the box-posterior moments."""
+    src/modules/losses/contperceptual.py:111-132,176-212.  Differentiable w.r.t. dec_pose and the box-posterior moments through
+    out[0:5] only: the reference logs out[5:9] (the means of t1, t2, t3, v3) and never trains on them, so the backward kernel ignores
+    their upstream gradient -- a non-zero one changes neither gradient (tests/test_pose_exact_gpu.py)."""
 
     @staticmethod
     def forward(ctx, dec_pose, moments, pose_gt, bbox_gt, fill_gt, class_gt, prior, prior_idx, bg_idx, l2, yaw, gamma, alpha):
