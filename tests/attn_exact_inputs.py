@@ -1,5 +1,5 @@
-"""Attention inputs with closed-form answers for the bf16 flash-attention kernels: generators, float64 references, the two
-preconditions, the checkers.
+"""Attention inputs with closed-form answers for the bf16 flash-attention kernels and (section "f32 routes" below) the f32 attention
+routes: generators, float64 references, the preconditions, the checkers.
 
 softmax(q k^T C^-1/2) v averages T values when q and k are Gaussian: one key is 1/T of an output, and a dropped key, a tile read from
 the wrong ring stage or a row constant of the neighbouring tile stay under any max-abs tolerance.  Here the softmax is made to SELECT:
@@ -22,6 +22,66 @@ Preconditions (`assert_preconditions`, on the very tensors used; c = C^-1/2 log2
        of its value, rounds to exactly 1 (1/g) in bf16, and x (1 +- 2^-10) rounds back to a bf16 x of <= 7 significant bits.
 
 Plain module: no fixtures, no device.  Tensors are float64 [N, T, C] on the host.
+
+f32 routes
+----------
+The same case tensors, packed as f32 (`pack_qkv(case, torch.float32)`), pin the four f32 routes of ops/attention.py: the fused kernels
+(csrc/flash_attn_f32.hip), the GEMM route with the separate and with the folded softmax, and the recompute route.  Every product of
+q, k, v, dO is a sum of small integers (family D: of multiples of 2^-3 below 2^15), exact in f32 in any order.
+  (P1) as above, with a simpler argument: the f32 kernels take the true running / row maximum, which does not lag, and 2^-160 is below
+       f32's smallest subnormal 2^-149 -- a non-selected probability is 0 whatever the flush mode.
+  (P2-f32) |z| < 2^13, z = s_sel c: ulp(|z|) <= 2^-11.  The fused backward forms p = exp2f(s sc - lse2), which hipcc contracts to an
+       fma (it does, on gfx950); lse2 = round(s sc) + log2 g then leaves the rounding residual of s sc in the exponent and a selected
+       p is 2^delta / g, |delta| <= ulp(|z|) / 2: relative error ln 2 ulp(|z|) / 2 <= 1.7e-4.  A_CODE stays 16: the largest |z| used is
+       ~1200 (C = 64, T = 4100), ulp 2^-13; the gap is what must hold.
+  (folded) slack_i = (1.000001 |q_i| max_j |k_j| - s_sel,i) c, norms over the row's own image (`folded_slack`): E_sel = 2^-slack.
+       "bound holds": slack <= 90 on every row, l >= 2^-90, a normal number far above 1e-30 ~ 2^-99.7; "bound underflows": slack >= 110
+       on some row, l <= T 2^-110 < 1e-30 there and the flag must rise.  The decoy amplitude (`make_case(decoy=...)`, 1/4 and 4) moves
+       |q|, |k| and no score; `folded_side` decides from the tensors alone.
+Bit-exact, from the code (eps = 2^-24):
+  fused forward: s sc is rounded BEFORE the maximum is taken off (mul, then sub: no contraction across the select), so the selected
+    exponent is exactly 0, p = 1, l = g, acc an integer sum, 1 / l an IEEE division: o is exact for A, B (g = 2^n) and C at T = 2^n; C at
+    other T: o = fl(fl(1 / T) S), S an integer, against fl(S / T): three half-ulp errors, the first scaled by mant(o) < 2 -- strictly
+    less than 2 ulps between two grid points, i.e. at most one step.
+  fused backward, A: dP_sel and delta = rowdot(dO, o) are the same exact integer, dS = p * 0: dq = dk = 0 whatever p is (the subtraction
+    comes before the scale: no "scale is a power of two" condition).  Family C: q = 0, dk = 0.
+  fused backward, B with g <= 2: NOT bit-exact.  dS_1 = -dS_2 = p (dP_1 - dP_2) / 2 exactly and k_1 = k_2, but the MFMA chain computes
+    fma(k, -dS, fl(k dS)) = fl(k dS) - k dS: the rounding residual of the first product, non-zero on decoy columns (k = 3, 5, ...) once
+    p = 2^delta has a full mantissa.  dq of B is toleranced on every route (0 <= bound where the products happen to be exact).
+  separate softmax / recompute: exp((s - max) scale) is exp(0) = 1 for the selected keys, P = 1 / g: o, dv exact for A, B, C at T = 2^n;
+    dP - delta is an exact 0 for A (delta an integer seeds the accumulator; the row pass forms sum_j P dP = dP): dq = dk = 0.
+  folded softmax: E = exp2((s - bound) a2) is not 1, o = fl(fl(E v) / E) is not v: everything is toleranced, also dq / dk of A (delta is
+    no integer any more).  After a fallback the result IS the separate route's.
+Bounds (`f32_rules`, `bound_f32`): per element (eps_p + k_sum eps) sum|terms|, for o once more with k_l, plus k_x eps X for dq / dk.
+  kmax = the largest number of non-zero terms in any sum of the case (keys per query, queries per key): adding an exact 0 does not round.
+  k_sum = kmax + 4: one rounding per non-zero fma of the chain, dS (2), the final scale or rinv (1), the store (0) -- one spare.
+  k_l = kmax + nt + 2: the row sum's additions, on the fused route one rescale per 32-key tile (nt = ceil(T / 32); alpha is 1 or 0 for a
+    selecting softmax, a real factor in D) and the two lane exchanges; 1 / l.
+  eps_p, the relative error of a probability as the products see it, per query row (zmag_i = max(|z_i|, |lse2_i|, 1)):
+    fused: ln 2 u ulp(zmag) + 24 eps, u by family -- only the roundings that occur together, for the contracted exponent
+      fma(s, sc, -lse2) and for the plain fl(s sc) - lse2 alike (e_x: the rounding error of fl(x sc), <= ulp / 2):
+        A  u = 1/2.  l = 1, log2f(1) = 0, lse2 = m = fl(s sc).  Contracted: the exponent is s sc - m = -e_m.  Plain: fl(s sc) - m = 0.
+        B  u = 1.    lse2 = fl(m + n), l = g = 2^n: the sum's rounding (1/2) on top of A's.
+        C  u = 1.    z = 0, m = 0, lse2 = log2f(T), within 1 ulp of log2 T (OCML's documented accuracy); nothing else rounds.
+        D  u = 3/2.  The forward's low-key exponents fl(s_low sc) - m carry e_low - e_m and make up a share w <= 1 of l.  Contracted,
+                     either level: -(1 - w) e_m - w e_low (1/2) and the sum (1/2).  Plain, low key: e_low (1/2), (1 - w) e_m and
+                     w e_low' (1/2 together), the sum (1/2); plain, level-0 key: w (e_low' - e_m) and the sum, also <= 3/2.
+      24 eps: the rounding of the exponent itself (|x| < 32: 16 eps of x, 11 of p), exp2f (1 ulp: 2), log2f of l <= 8 (3), spare.
+      D only, (kmax + nt + 20) eps more: l's own additions and rescales (its terms are no integers there), and c = fl(fl(C^-1/2)
+      fl(log2 e)) against the float64 c on the 9 log2-units between the levels (3 eps * 9 * ln 2 < 20 eps).  A, B, C: l is an exact
+      integer and c's error cancels between s sc and lse2.
+    separate, recompute: (kmax + 40) eps: (s - max) is exact, times scale (1), __expf = exp2(x log2 e) (1, and |x| <= SPREAD: 30 eps of
+      argument error), the sum (kmax), 1 / sum, the product.
+    folded: (kmax + 8) eps for A, B, C -- the members of a tie group have identical k rows, hence identical E, and P = E / (g E) does
+      not see E's error; family D's levels differ in one product of the chain s - bound, which is seeded with -bound and rounds at
+      magnitude |bound| in each of up to C steps: 2 ln 2 (C ulp(|bound|) / 2 c + 2 eps (slack + SPREAD)) more.
+  k_x eps X, X = sum P scale (dpa + sum_j P dpa) |k or q|, dpa_ij = sum_c |dO_ic| |v_jc|: the cancellation floor of dP - delta, at the
+    magnitude the two sums run at.  delta = rowdot(dO, o): 4 ceil(C / 256) products and additions per lane, 6 exchange steps, the
+    subtraction: k_delta = 4 ceil(C / 256) + 8 (fused); the GEMM routes seed the accumulator with -delta and add C products: C + k_delta;
+    the row pass forms delta as sum_j P dP from the rounded P: 2 kmax + 60 (kmax terms, eps_p / eps, the block reduction).
+  lse2 (fused): 6 eps mag for c = fl(fl(C^-1/2) fl(log2 e)) (3), m (1), the final sum (1) and a spare, + ulp(zmag) for D's low keys
+    + k_l eps / ln 2 + 2^-19 for log2f at log2 l < 16.
+Nothing here was fitted to a device result; profiles/attn_f32_exact.md lists the worst err / bound seen.
 """
 import math
 
@@ -94,9 +154,12 @@ def _group_layout(t, gsize):
     return cid, groups, groups + extra
 
 
-def make_case(family, n, t, c, seed=0, many_to_one=False, group=2, level=9, high_first=True):
+def make_case(family, n, t, c, seed=0, many_to_one=False, group=2, level=9, high_first=True, decoy=None):
     """One attention case: dict q, k, v, do [n, t, c] float64 (all bf16 numbers), cid [t] the code id of every key, qcode [n, t] the
-    code id every query selects (its keys: cid == qcode), and the recipe's parameters."""
+    code id every query selects (its keys: cid == qcode), and the recipe's parameters.
+    decoy (f32 cases; None: the recipe as it is, the seed formula does not see it): amplitude of the integer decoys on q_cols / k_cols,
+    one number or one per image.  The decoys sit on disjoint columns and change no score; they lengthen |q| and |k|, i.e. the
+    Cauchy-Schwarz row bound of the folded softmax (`folded_slack`).  Powers of two: the decoys stay exact in f32 (and bf16)."""
     fam = {"A": 1, "B": 2, "C": 3, "D": 4}[family]
     g = torch.Generator().manual_seed(1000003 * seed + 7919 * fam + 131 * c + 17 * t + n + 3 * group + 5 * level + int(many_to_one) + 2 * int(high_first))
     case = {"family": family, "n": n, "t": t, "c": c, "group": 1, "level": None}
@@ -161,13 +224,18 @@ def make_case(family, n, t, c, seed=0, many_to_one=False, group=2, level=9, high
     if family == "D":
         q[:, :, level_col] = 1.0
         k[:, :, level_col] = levels[None].expand(n, t)
+    if decoy is not None:
+        amp = torch.as_tensor(decoy, dtype=torch.float64).reshape(-1, 1, 1).expand(n, 1, 1)
+        q[:, :, q_cols] = q[:, :, q_cols] * amp
+        k[:, :, k_cols] = k[:, :, k_cols] * amp
+        case["decoy"] = decoy
     case.update(q=q, k=k, v=v, do=do, cid=cid, qcode=qcode)
     return case
 
 
-def pack_qkv(case):
-    """the packed projection the kernels read: bf16 [n, t, 3c] (q | k | v)"""
-    return torch.cat([case["q"], case["k"], case["v"]], 2).float().to(BF)
+def pack_qkv(case, dtype=BF):
+    """the packed projection the kernels read: [n, t, 3c] (q | k | v) in bf16 or f32"""
+    return torch.cat([case["q"], case["k"], case["v"]], 2).float().to(dtype)
 
 
 def member(case, b, rows=slice(None)):
@@ -178,10 +246,10 @@ def member(case, b, rows=slice(None)):
 # ------------------------------------------------------------------------------------------------------------------------------
 # the preconditions
 # ------------------------------------------------------------------------------------------------------------------------------
-def assert_preconditions(case, block=512):
+def assert_preconditions(case, block=512, dtype=BF):
     """(P1), (P2) and representability, on the tensors a test uses.  Returns (smallest gap, largest |s_sel c|)."""
     for name in ("q", "k", "v", "do"):
-        assert torch.equal(rne(case[name]).double(), case[name]), "%s is not made of bf16 numbers" % name
+        assert torch.equal(case[name].float().to(dtype).double(), case[name]), "%s is not made of %s numbers" % (name, "bf16" if dtype == BF else dtype)
     cc, t = c_of(case["c"]), case["t"]
     gap, top = float("inf"), 0.0
     for b in range(case["n"]):
@@ -230,13 +298,18 @@ def references(case, o_used=None, dense=None):
         ds = (dp - delta) * scale                                    # P = 1
         fl = (dp.abs() + delta.abs()) * scale
         r["dq"], r["dq_abs"], r["dq_floor"] = ds[:, :, None] * ksel, ds.abs()[:, :, None] * ksel.abs(), fl[:, :, None] * ksel.abs()
+        x = 2.0 * (do.abs() * vsel.abs()).sum(2) * scale            # the f32 rules' X, see below (P = 1: dpa + sum_j P dpa = 2 dpa)
+        r["dq_x"] = x[:, :, None] * ksel.abs()
         for name, src in (("dk", ds[:, :, None] * q), ("dk_abs", ds.abs()[:, :, None] * q.abs()), ("dk_floor", fl[:, :, None] * q.abs()),
-                          ("dv", do), ("dv_abs", do.abs())):
+                          ("dv", do), ("dv_abs", do.abs()), ("dk_x", x[:, :, None] * q.abs())):
             r[name] = torch.zeros(n, t, c, dtype=torch.float64).scatter_add_(1, idx, src)
+        r["k_row"] = torch.ones(n, t, dtype=torch.float64)
+        r["k_col"] = torch.zeros(n, t, dtype=torch.float64).scatter_add_(1, pi, torch.ones(n, t, dtype=torch.float64))
         return r
-    for name in ("o", "o_abs", "dq", "dq_abs", "dq_floor", "dk", "dk_abs", "dk_floor", "dv", "dv_abs"):
+    for name in ("o", "o_abs", "dq", "dq_abs", "dq_floor", "dk", "dk_abs", "dk_floor", "dv", "dv_abs", "dq_x", "dk_x"):
         r[name] = torch.empty(n, t, c, dtype=torch.float64)
-    r["lse2"], r["sel"] = torch.empty(n, t, dtype=torch.float64), torch.empty(n, t, dtype=torch.float64)
+    for name in ("lse2", "sel", "k_row", "k_col"):
+        r[name] = torch.empty(n, t, dtype=torch.float64)
     for b in range(n):
         m = member(case, b)
         z = (q[b] @ k[b].T * cc).masked_fill(~m, -float("inf"))     # non-selected keys: probability 0 by (P1)
@@ -254,6 +327,12 @@ def references(case, o_used=None, dense=None):
         r["dq"][b], r["dq_abs"][b], r["dq_floor"][b] = ds @ k[b], ds.abs() @ k[b].abs(), fl @ k[b].abs()
         r["dk"][b], r["dk_abs"][b], r["dk_floor"][b] = ds.T @ q[b], ds.abs().T @ q[b].abs(), fl.T @ q[b].abs()
         r["dv"][b], r["dv_abs"][b] = p.T @ do[b], p.T @ do[b].abs()
+        # the f32 rules: X = sum over the terms of P scale (dpa + sum_j P dpa) |k or q|, dpa_ij = sum_c |dO_ic| |v_jc| the magnitude at
+        # which the sums dP_ij and delta_i run; k_row / k_col: how many keys a query gives weight to / how many queries weigh a key
+        dpa = do[b].abs() @ v[b].abs().T
+        x = p * (dpa + (p * dpa).sum(1, keepdim=True)) * scale
+        r["dq_x"][b], r["dk_x"][b] = x @ k[b].abs(), x.T @ q[b].abs()
+        r["k_row"][b], r["k_col"][b] = m.sum(1).double(), m.sum(0).double()
     return r
 
 
@@ -392,3 +471,272 @@ def cases_for(c, t):
 
 def grid():
     return [(c, t) for c in CS for t in TS] + [(c, t) for t, c in BIG]
+
+
+# ==============================================================================================================================
+# f32: the same cases for the four f32 attention routes of ops/attention.py (module docstring: "f32 routes")
+# ==============================================================================================================================
+F32 = torch.float32
+EPS = 2.0 ** -24                    # one f32 rounding to nearest, relative to the result
+LN2 = 0.6931471805599453
+BOUND_GROW = 1.000001               # attn_bound_kernel's factor on max_j |k_j|
+SLACK_HOLDS, SLACK_UNDERFLOWS = 90.0, 110.0
+DECOY_HOLDS, DECOY_UNDERFLOWS = 0.25, 4.0
+ROUTES = ("fused", "separate", "separate_unfused", "recompute", "folded")
+
+
+def ulp32(x):
+    """the f32 grid step at |x| (normal numbers)"""
+    return 2.0 ** (math.floor(math.log2(abs(x))) - 23)
+
+
+def folded_decoy(n, underflows):
+    """Decoy amplitudes of a folded-softmax case.  Holds: 1/4 on every image.  Underflows: 4 on every image BUT the first (one image:
+    on that one), so that a row bound taken from image 0 for every image would hold everywhere and leave the flag down."""
+    if not underflows:
+        return DECOY_HOLDS
+    return DECOY_UNDERFLOWS if n == 1 else (DECOY_HOLDS,) + (DECOY_UNDERFLOWS,) * (n - 1)
+
+
+def folded_slack(case):
+    """[n, t] float64: slack_i = (1.000001 |q_i| max_j |k_j| - s_sel,i) c in log2-units, norms over the row's own image: how far the
+    folded route's Cauchy-Schwarz bound lies above the row's selected score.  E_sel = 2^-slack and l >= E_sel.  Also the bounds
+    themselves (raw score units).  The kernel's norms carry a few f32 roundings: ~2^-21 |bound| c < 0.01 log2-units here."""
+    cc = c_of(case["c"])
+    slack, bnd = torch.empty(case["n"], case["t"], dtype=torch.float64), torch.empty(case["n"], case["t"], dtype=torch.float64)
+    for b in range(case["n"]):
+        q, k = case["q"][b], case["k"][b]
+        bnd[b] = q.norm(dim=1) * (k.norm(dim=1).max() * BOUND_GROW)
+        sel = (q @ k.T).masked_fill(~member(case, b), -float("inf")).max(1).values
+        slack[b] = (bnd[b] - sel) * cc
+    return slack, bnd
+
+
+def assert_folded_precondition(case, underflows):
+    """holds: slack <= 90 on every row (l >= 2^-90, a normal number far above 1e-30 ~ 2^-99.7: the flag stays down);
+    underflows: slack >= 110 on at least one row (there every E <= 2^-110, l <= T 2^-110 < 1e-30: the flag must rise).
+    Conditions on the case's own tensors, not measurements.  Returns (smallest, largest) slack."""
+    slack, _ = folded_slack(case)
+    lo, hi = slack.min().item(), slack.max().item()
+    assert lo >= -1e-9, "the row bound lies below a selected score (slack %.3g): Cauchy-Schwarz broken" % lo
+    if underflows:
+        assert hi >= SLACK_UNDERFLOWS, "no row's bound lies >= %.0f log2-units above its selected score (largest slack %.1f)" % (SLACK_UNDERFLOWS, hi)
+        assert math.log2(case["t"]) - hi < -100.0      # T 2^-slack < 1e-30
+    else:
+        assert hi <= SLACK_HOLDS, "a row's bound lies %.1f log2-units above its selected score, more than %.0f" % (hi, SLACK_HOLDS)
+    return lo, hi
+
+
+def folded_side(case):
+    """"holds" / "underflows" / None (in between: no folded-route case) by the two conditions above, from the case's tensors alone.
+    Families A and B land where their decoy amplitude puts them (tests/test_attn_f32_exact_inputs.py shows it for every (C, T) used);
+    family C (q = 0: bound 0) always holds; family D's low keys carry the level 9 / c or 6 / c on one column, which alone lengthens
+    max_j |k_j|.  With the 1/4 decoys a level-6 D case holds at C = 32 and, but for one T, at 48, and lies in between at C = 64 (no
+    "holds" run); at level 9, and at C = 256 at either level, it underflows already.  With the 4 decoys every D case underflows, so
+    each D recipe does run as a fallback case at every T it exists for."""
+    hi = folded_slack(case)[0].max().item()
+    if hi <= SLACK_HOLDS:
+        return "holds"
+    if hi >= SLACK_UNDERFLOWS and math.log2(case["t"]) - hi < -100.0:
+        return "underflows"
+    return None
+
+
+def _bits32(t):
+    return (t.contiguous() + 0.0).view(torch.int32)
+
+
+def assert_bits_equal_f32(got, want, what):
+    """f32 tensors agree in every bit (int32 view; -0.0 counts as +0.0)"""
+    assert got.dtype == F32 and want.dtype == F32, "%s: dtypes %s, %s" % (what, got.dtype, want.dtype)
+    assert tuple(got.shape) == tuple(want.shape), "%s: shape %s, expected %s" % (what, tuple(got.shape), tuple(want.shape))
+    bad = _bits32(got) != _bits32(want)
+    nbad = int(bad.sum())
+    if nbad:
+        idx = bad.nonzero()
+        first = ["(%s): got %r, want %r" % (", ".join(str(int(x)) for x in i), got[tuple(i)].item(), want[tuple(i)].item()) for i in idx[:6]]
+        rows = sorted(set(int(i[1]) for i in idx)) if idx.shape[1] > 1 else []
+        raise AssertionError("%s: %d of %d elements differ in bits; first %s | rows %s%s" % (
+            what, nbad, bad.numel(), "; ".join(first), rows[:12], " ..." if len(rows) > 12 else ""))
+
+
+def assert_within_one_ulp_f32(got, want, what):
+    """f32 tensors at most one step of the f32 grid apart"""
+    def ordinal(x):
+        b = _bits32(x).to(torch.int64)
+        return torch.where(b < 0, -(b & 0x7FFFFFFF), b)
+    assert torch.isfinite(got).all(), what + ": non-finite values"
+    dist = (ordinal(got) - ordinal(want)).abs()
+    assert int(dist.max()) <= 1, "%s: %d elements are more than one f32 ulp off (worst %d steps)" % (what, int((dist > 1).sum()), int(dist.max()))
+
+
+FUSED_ULPS = {"A": 0.5, "B": 1.0, "C": 1.0, "D": 1.5}      # ulps of zmag in a fused-route exponent, module docstring "eps_p, fused"
+
+
+def ulp32_of(x):
+    """the f32 grid step at every element of a float64 tensor of magnitudes >= 1, a hair (2^-20) up: the kernel's own z differs from
+    the float64 one by the rounding of c and may lie in the next binade"""
+    return torch.exp2(torch.floor(torch.log2(x * (1.0 + 2.0 ** -20))) - 23.0)
+
+
+def f32_rules(case, r, route):
+    """The factors of the f32 bounds of one (case, route), every one a count of roundings (module docstring, "f32 routes"):
+    eps_p [n, t]  relative error of a probability of query row i as the products see it;  k_sum  roundings of a sum of products and its
+    tail;  k_x  roundings at the magnitude X of the difference dP - delta;  k_l  roundings of the forward's row sum;  zmag [n, t]."""
+    fam, t, c = case["family"], case["t"], case["c"]
+    kmax = max(r["k_row"].max().item(), r["k_col"].max().item())
+    zmag = torch.maximum(torch.maximum(r["sel"].abs(), r["lse2"].abs()), torch.ones_like(r["lse2"]))
+    nt = -(-t // 32) if route == "fused" else 0
+    k_delta = 4 * (-(-c // 256)) + 8
+    if route == "fused":
+        eps_p = LN2 * FUSED_ULPS[fam] * ulp32_of(zmag) + (24 + (kmax + nt + 20 if fam == "D" else 0)) * EPS
+        k_x = k_delta
+    elif route == "folded":
+        e = (kmax + 8) * EPS
+        if fam == "D":
+            slack, bnd = folded_slack(case)
+            e += 2.0 * LN2 * (c * 0.5 * ulp32(bnd.max().item()) * c_of(c) + 2.0 * EPS * (slack.max().item() + SPREAD))
+        eps_p, k_x = torch.full_like(zmag, e), c + k_delta
+    elif route == "separate_unfused":
+        eps_p, k_x = torch.full_like(zmag, (kmax + 40) * EPS), 2 * kmax + 60
+    else:
+        eps_p, k_x = torch.full_like(zmag, (kmax + 40) * EPS), c + k_delta
+    return {"eps_p": eps_p, "k_sum": kmax + 4, "k_x": k_x, "k_l": kmax + nt + 2, "zmag": zmag}
+
+
+def bound_f32(r, name, rules):
+    """The per-element bound of one toleranced quantity (module docstring, "Bounds").  o and dq are sums over the keys of ONE query:
+    that row's eps_p.  dv and dk are sums over the queries that weigh a key: the largest eps_p of the image's rows (every row of an
+    image carries nearly the same |z|; the step of ulp() is what can differ)."""
+    e = rules["eps_p"][:, :, None] if name in ("o", "dq") else rules["eps_p"].max(1).values[:, None, None]
+    b = (e + rules["k_sum"] * EPS) * r[name + "_abs"]
+    if name == "o":
+        b = b + (e + rules["k_l"] * EPS) * r["o_abs"]
+    if name in ("dq", "dk"):
+        b = b + rules["k_x"] * EPS * r[name + "_x"]
+    return b
+
+
+def lse2_tolerance_f32(case, r, rules):
+    """lse2 = m + log2f(l) of the fused forward against float64, per row (module docstring, "lse2 (fused)")"""
+    low = ulp32_of(rules["zmag"]) if case["family"] == "D" else 0.0
+    return 6.0 * EPS * rules["zmag"] + low + rules["k_l"] * EPS / LN2 + 2.0 ** -19
+
+
+def check_case_f32(case, got, route, o_used=None):
+    """Every element of every output of one f32 case against its family's rule on `route` (one of ROUTES; a folded forward whose
+    fallback ran is "separate").  got: o, dq, dk, dv f32 [n, t, c] host tensors, and lse2 f32 [n, t] on the fused route; o_used: the o
+    the backward's delta was formed from (default got["o"]; "separate_unfused" forms sum_j P dP from P itself: the exact o).
+    Returns {quantity: worst err / bound} for what is toleranced."""
+    fam, c, t = case["family"], case["c"], case["t"]
+    assert route in ROUTES
+    tag = "f32 %s family %s N=%d T=%d C=%d" % (route, fam, case["n"], t, c)
+    if route == "separate_unfused":
+        r = references(case, None)
+    else:
+        r = references(case, (got["o"] if o_used is None else o_used).double())
+    rules = f32_rules(case, r, route)
+    margins = {}
+    if route == "fused":
+        margins["lse2"] = assert_under_bound(got["lse2"], r["lse2"], lse2_tolerance_f32(case, r, rules), tag + " lse2")
+    exact_p = fam in ("A", "B") or (fam == "C" and t & (t - 1) == 0)        # every probability is 1 / 2^n
+    if route != "folded" and exact_p:
+        assert_bits_equal_f32(got["o"], r["o"].float(), tag + " o")
+    elif route == "fused" and fam == "C":
+        assert_within_one_ulp_f32(got["o"], r["o"].float(), tag + " o")
+    else:
+        margins["o"] = assert_under_bound(got["o"], r["o"], bound_f32(r, "o", rules), tag + " o")
+    if route not in ("fused", "folded") and exact_p:
+        assert_bits_equal_f32(got["dv"], r["dv"].float(), tag + " dv")
+    else:
+        margins["dv"] = assert_under_bound(got["dv"], r["dv"], bound_f32(r, "dv", rules), tag + " dv")
+    zero = torch.zeros_like(got["dq"])
+    if fam == "A" and route != "folded":
+        assert_bits_equal_f32(got["dq"], zero, tag + " dq")
+        assert_bits_equal_f32(got["dk"], zero, tag + " dk")
+    else:
+        margins["dq"] = assert_under_bound(got["dq"], r["dq"], bound_f32(r, "dq", rules), tag + " dq")
+        if fam == "C":
+            assert_bits_equal_f32(got["dk"], zero, tag + " dk")
+        else:
+            margins["dk"] = assert_under_bound(got["dk"], r["dk"], bound_f32(r, "dk", rules), tag + " dk")
+    return margins
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the shapes of the f32 GPU tests; the host models are held to the same lists
+# ------------------------------------------------------------------------------------------------------------------------------
+F32_TS = (1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 96, 97, 129, 160, 257, 300)    # a wave's 16 rows, a tile's 32 keys and a
+#                                                                      block's 64 rows from both sides, one to five blocks (fused route)
+GEMM_CS = (32, 48, 64, 256)
+GEMM_TS_EDGES = (1, 45, 127, 128, 129, 180, 257, 300)     # the 128-wide GEMM tiles from both sides
+GEMM_TS = tuple(sorted(set(GEMM_TS_EDGES + (4, 44, 124, 132, 256, 260))))     # ... and the multiples of 4 beside them: the GEMM routes
+#                                                     take T % 4 == 0 only (float4 rows of P) and must REFUSE the others, not fall back
+SPLIT_TT = dict(n=57, t=300, c=64)      # ceil(300 / 128)^2 * 57 = 513 >= 512 blocks, K = 64: the T x T products run on the bf16-split kernels
+
+
+def cases_for_f32(c, t):
+    """as `cases_for`, for the fused f32 kernels: the rotation runs over F32_TS"""
+    i = CS.index(c) + (F32_TS.index(t) if t in F32_TS else 0)
+    if (t, c) in BIG:
+        return [dict(family="A", n=1, t=t, c=c, many_to_one=(c == 256))]
+    out = [dict(family="A", n=NS[i % 3], t=t, c=c),
+           dict(family="A", n=NS[(i + 1) % 3], t=t, c=c, many_to_one=True),
+           dict(family="B", n=NS[(i + 2) % 3], t=t, c=c, group=(2, 4, 8)[i % 3]),
+           dict(family="C", n=NS[i % 3], t=t, c=c)]
+    if t in D_TS:
+        out += [dict(family="D", n=NS[(i + k) % 3], t=t, c=c, level=level, high_first=first)
+                for k, (level, first) in enumerate(((9, True), (9, False), (6, True), (6, False)))]
+    return out
+
+
+def grid_f32():
+    return [(c, t) for c in CS for t in F32_TS] + [(c, t) for t, c in BIG]
+
+
+def gemm_cases_for(c, t):
+    """the cases of one (C, T) on the GEMM routes: A (permutation, many-to-one) and B everywhere, C and D where 129 keys fit.  Cases
+    `make_case` refuses (C too narrow for the code) are left out; the gap is not weakened for them."""
+    i = GEMM_CS.index(c) + GEMM_TS.index(t)
+    out = [dict(family="A", n=NS[i % 3], t=t, c=c),
+           dict(family="A", n=NS[(i + 1) % 3], t=t, c=c, many_to_one=True),
+           dict(family="B", n=NS[(i + 2) % 3], t=t, c=c, group=(2, 4, 8)[i % 3])]
+    if t >= D_LOW_KEYS + 1:
+        out += [dict(family="C", n=NS[i % 3], t=t, c=c),
+                dict(family="D", n=NS[(i + 1) % 3], t=t, c=c, level=9, high_first=bool(i % 2)),
+                dict(family="D", n=NS[(i + 2) % 3], t=t, c=c, level=6, high_first=not i % 2)]
+    kept = []
+    for kw in out:
+        try:
+            make_case(**kw)
+        except AssertionError as e:
+            assert "too narrow" in str(e)
+            continue
+        kept.append(kw)
+    return kept
+
+
+def folded_variants(kw):
+    """[(case, side)] of one recipe for the folded route: at most one case per side, with the decoy amplitudes of `folded_decoy` and
+    the side the host arithmetic shows (`folded_side`).  A and B give both sides; C holds; D lands where its level column puts it."""
+    out = []
+    for underflows in (False, True):
+        case = make_case(decoy=folded_decoy(kw["n"], underflows), **kw)
+        side = folded_side(case)
+        if kw["family"] in ("A", "B"):
+            assert side == ("underflows" if underflows else "holds"), (kw, side)
+        if side is not None and not any(side == s for _, s in out):
+            out.append((case, side))
+    return out
+
+
+RECOMPUTE_N = 5        # budgets of 2 and of 1 image: forward groups 2 + 2 + 1 and five of 1, backward groups of 1 (the halved group)
+
+
+def recompute_cases_for(c, t):
+    """every family of `gemm_cases_for`, five images each"""
+    return [dict(kw, n=RECOMPUTE_N) for kw in gemm_cases_for(c, t)]
+
+
+def gemm_grid():
+    return [(c, t) for c in GEMM_CS for t in GEMM_TS]
