@@ -112,6 +112,47 @@ __global__ void bn_sum_partials_b_kernel(const float* __restrict__ part, int nbl
   if (lane == 0) sums[idx] = (float)a;
 }
 
+// bn_record_kernel / bn_sum_partials_f64_kernel / bn_merge_sums_kernel of gan_f32.hip (synchronised BatchNorm) with a bf16 pivot
+__global__ void bn_record_bf16_kernel(const float* __restrict__ part, const bf16_t* __restrict__ x, int nblk, int C, int64_t rows,
+                                      double* __restrict__ record) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (c >= C) return;
+  double a = 0.0, b = 0.0;
+  for (int k = lane; k < nblk; k += 64) { a += (double)part[((int64_t)k * 2 + 0) * C + c]; b += (double)part[((int64_t)k * 2 + 1) * C + c]; }
+  a = wave_sum_f64(a); b = wave_sum_f64(b);
+  if (lane != 0) return;
+  const double m = (double)rows;
+  const double dm = a / m;
+  double m2 = b - a * dm;
+  if (m2 < 0.0) m2 = 0.0;
+  record[(int64_t)c * 3 + 0] = m;
+  record[(int64_t)c * 3 + 1] = (double)bf16_to_f32(x[c]) + dm;
+  record[(int64_t)c * 3 + 2] = m2;
+}
+
+__global__ void bn_sum_partials_f64_b_kernel(const float* __restrict__ part, int nblk, int C, double* __restrict__ sums64,
+                                             float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int lane = threadIdx.x & 63;
+  const int idx = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (idx >= 2 * C) return;
+  const int which = idx / C, c = idx % C;
+  double a = 0.0;
+  for (int k = lane; k < nblk; k += 64) a += (double)part[((int64_t)k * 2 + which) * C + c];
+  a = wave_sum_f64(a);
+  if (lane != 0) return;
+  sums64[idx] = a;
+  if (which == 0) dbeta[c] = (float)a; else dgamma[c] = (float)a;
+}
+
+__global__ void bn_merge_sums_b_kernel(const double* __restrict__ sums64, int world, int C, float* __restrict__ sums) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 2 * C) return;
+  double a = sums64[idx];
+  for (int w = 1; w < world; ++w) a += sums64[(int64_t)w * 2 * C + idx];
+  sums[idx] = (float)a;
+}
+
 // V consecutive elements of one row per thread: V = 8 (one 16-byte vector; C % 8 == 0, so the eight never wrap a row) or 1
 template <int V> __device__ __forceinline__ void ld_bf16(const bf16_t* p, float (&v)[V]) {
   if (V == 8) {
@@ -149,15 +190,16 @@ __global__ __launch_bounds__(256) void bn_lrelu_apply_bf16_kernel(const bf16_t* 
   }
 }
 
-// training: dx = gamma * rstd * (g - (sum_g + xhat * sum_gxhat) / M); eval (train = 0): dx = gamma * rstd * g
+// training: dx = gamma * rstd * (g - (sum_g + xhat * sum_gxhat) / M); eval (train = 0): dx = gamma * rstd * g.  M = rows, or *m_total (device): all
+// ranks' rows with merged sums
 template <int V>
 __global__ __launch_bounds__(256) void bn_lrelu_bwd_apply_bf16_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
                                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                      const float* __restrict__ sums, float slope, int64_t rows, int C,
-                                                                      int train, bf16_t* __restrict__ dx) {
+                                                                      const float* __restrict__ sums, float slope, int64_t rows, const double* __restrict__ m_total,
+                                                                      int C, int train, bf16_t* __restrict__ dx) {
   const int64_t total = rows * C;
-  const float inv_m = 1.f / (float)rows;
+  const float inv_m = 1.f / (m_total ? (float)*m_total : (float)rows);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i * V < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t idx = i * V;
     const int c0 = (int)(idx % C);
@@ -252,10 +294,78 @@ int odvae_batchnorm_lrelu_bwd_bf16(const void* x, const void* dy, int64_t rows, 
   hipMemcpyAsync(dgamma, sums + C, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, st);
   const int64_t total = rows * C;
   if (vec8(total, C, x, dy, dx))
-    hipLaunchKernelGGL((bn_lrelu_bwd_apply_bf16_kernel<8>), dim3(grid_1d(total / 8)), dim3(256), 0, st, xb, gb, mean, rstd, gamma, beta, sums, slope, rows, C, train, static_cast<bf16_t*>(dx));
+    hipLaunchKernelGGL((bn_lrelu_bwd_apply_bf16_kernel<8>), dim3(grid_1d(total / 8)), dim3(256), 0, st, xb, gb, mean, rstd, gamma, beta, sums, slope, rows, nullptr, C, train, static_cast<bf16_t*>(dx));
   else
-    hipLaunchKernelGGL((bn_lrelu_bwd_apply_bf16_kernel<1>), dim3(grid_1d(total)), dim3(256), 0, st, xb, gb, mean, rstd, gamma, beta, sums, slope, rows, C, train, static_cast<bf16_t*>(dx));
+    hipLaunchKernelGGL((bn_lrelu_bwd_apply_bf16_kernel<1>), dim3(grid_1d(total)), dim3(256), 0, st, xb, gb, mean, rstd, gamma, beta, sums, slope, rows, nullptr, C, train, static_cast<bf16_t*>(dx));
   ODVAE_LAUNCH_CHECK("batchnorm_lrelu_bwd_bf16");
+  return ODVAE_OK;
+}
+
+// ---- synchronised BatchNorm on bf16 activations: the twins of odvae_batchnorm_sync_*_f32 (merge: odvae_batchnorm_sync_stats_merge) ----
+int odvae_batchnorm_sync_stats_record_bf16(const void* x, int64_t rows, int C, double* record, size_t record_bytes,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(x && rows > 0 && C > 0, "batchnorm_sync_stats_record_bf16: bad arguments");
+  ODVAE_CHECK_ARG(((uintptr_t)x & 3) == 0, "batchnorm_sync_stats_record_bf16: misaligned operand");
+  const size_t need_rec = odvae_batchnorm_sync_record_bytes(C);
+  if (!record || record_bytes < need_rec) { odvae_set_error("batchnorm_sync_stats_record_bf16: the record needs %zu bytes", need_rec); return ODVAE_ERR_WORKSPACE; }
+  const size_t need = odvae_batchnorm_workspace_bytes(rows, C);
+  if (!workspace || workspace_bytes < need) { odvae_set_error("batchnorm_sync_stats_record_bf16: needs %zu workspace bytes", need); return ODVAE_ERR_WORKSPACE; }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bf16_t* xb = static_cast<const bf16_t*>(x);
+  float* part = static_cast<float*>(workspace);
+  const int nblk = stat_blocks(rows);
+  const int rpb = (int)ceil_div64(rows, nblk);
+  const int nb = (int)ceil_div64(rows, rpb);
+  if (C % 2 == 0) hipLaunchKernelGGL((bn_colstats_bf16_kernel<0, 2>), dim3(nb), dim3(256), 0, st, xb, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, rows, C, rpb, part);
+  else            hipLaunchKernelGGL((bn_colstats_bf16_kernel<0, 1>), dim3(nb), dim3(256), 0, st, xb, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, rows, C, rpb, part);
+  hipLaunchKernelGGL(bn_record_bf16_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, xb, nb, C, rows, record);
+  ODVAE_LAUNCH_CHECK("batchnorm_sync_stats_record_bf16");
+  return ODVAE_OK;
+}
+
+int odvae_batchnorm_sync_bwd_sums_bf16(const void* x, const void* dy, int64_t rows, int C, const float* gamma, const float* beta,
+                                       const float* mean, const float* rstd, float slope, double* sums, size_t sums_bytes,
+                                       float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(x && dy && gamma && beta && mean && rstd && dgamma && dbeta && rows > 0 && C > 0, "batchnorm_sync_bwd_sums_bf16: bad arguments");
+  ODVAE_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy) & 3) == 0, "batchnorm_sync_bwd_sums_bf16: misaligned operand");
+  const size_t need_sums = odvae_batchnorm_sync_sums_bytes(C);
+  if (!sums || sums_bytes < need_sums) { odvae_set_error("batchnorm_sync_bwd_sums_bf16: the sums need %zu bytes", need_sums); return ODVAE_ERR_WORKSPACE; }
+  const size_t need = odvae_batchnorm_workspace_bytes(rows, C);
+  if (!workspace || workspace_bytes < need) { odvae_set_error("batchnorm_sync_bwd_sums_bf16: needs %zu workspace bytes", need); return ODVAE_ERR_WORKSPACE; }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bf16_t* xb = static_cast<const bf16_t*>(x);
+  const bf16_t* gb = static_cast<const bf16_t*>(dy);
+  float* part = static_cast<float*>(workspace);
+  const int nblk = stat_blocks(rows);
+  const int rpb = (int)ceil_div64(rows, nblk);
+  const int nb = (int)ceil_div64(rows, rpb);
+  if (C % 2 == 0) hipLaunchKernelGGL((bn_colstats_bf16_kernel<1, 2>), dim3(nb), dim3(256), 0, st, xb, gb, mean, rstd, gamma, beta, slope, rows, C, rpb, part);
+  else            hipLaunchKernelGGL((bn_colstats_bf16_kernel<1, 1>), dim3(nb), dim3(256), 0, st, xb, gb, mean, rstd, gamma, beta, slope, rows, C, rpb, part);
+  hipLaunchKernelGGL(bn_sum_partials_f64_b_kernel, dim3(ceil_div(2 * C, 4)), dim3(256), 0, st, part, nb, C, sums, dgamma, dbeta);
+  ODVAE_LAUNCH_CHECK("batchnorm_sync_bwd_sums_bf16");
+  return ODVAE_OK;
+}
+
+int odvae_batchnorm_sync_bwd_dx_bf16(const void* x, const void* dy, int64_t rows, int C, const float* gamma, const float* beta,
+                                     const float* mean, const float* rstd, float slope, const double* sums_all, size_t sums_bytes,
+                                     int world, const double* m_total, void* dx, void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(x && dy && gamma && beta && mean && rstd && dx && rows > 0 && C > 0 && world > 0 && m_total, "batchnorm_sync_bwd_dx_bf16: bad arguments");
+  ODVAE_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 3) == 0, "batchnorm_sync_bwd_dx_bf16: misaligned operand");
+  const size_t need_sums = (size_t)world * odvae_batchnorm_sync_sums_bytes(C);
+  if (!sums_all || sums_bytes < need_sums) { odvae_set_error("batchnorm_sync_bwd_dx_bf16: the sums need %zu bytes", need_sums); return ODVAE_ERR_WORKSPACE; }
+  const size_t need = odvae_batchnorm_workspace_bytes(rows, C);
+  if (!workspace || workspace_bytes < need) { odvae_set_error("batchnorm_sync_bwd_dx_bf16: needs %zu workspace bytes", need); return ODVAE_ERR_WORKSPACE; }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bf16_t* xb = static_cast<const bf16_t*>(x);
+  const bf16_t* gb = static_cast<const bf16_t*>(dy);
+  float* sums = static_cast<float*>(workspace) + (size_t)stat_blocks(rows) * 2 * C;
+  hipLaunchKernelGGL(bn_merge_sums_b_kernel, dim3(ceil_div(2 * C, 256)), dim3(256), 0, st, sums_all, world, C, sums);
+  const int64_t total = rows * C;
+  if (vec8(total, C, x, dy, dx))
+    hipLaunchKernelGGL((bn_lrelu_bwd_apply_bf16_kernel<8>), dim3(grid_1d(total / 8)), dim3(256), 0, st, xb, gb, mean, rstd, gamma, beta, sums, slope, rows, m_total, C, 1, static_cast<bf16_t*>(dx));
+  else
+    hipLaunchKernelGGL((bn_lrelu_bwd_apply_bf16_kernel<1>), dim3(grid_1d(total)), dim3(256), 0, st, xb, gb, mean, rstd, gamma, beta, sums, slope, rows, m_total, C, 1, static_cast<bf16_t*>(dx));
+  ODVAE_LAUNCH_CHECK("batchnorm_sync_bwd_dx_bf16");
   return ODVAE_OK;
 }
 

@@ -167,6 +167,82 @@ __global__ void bn_sum_partials_kernel(const float* __restrict__ part, int nblk,
   if (lane == 0) sums[idx] = (float)a;
 }
 
+// ---- synchronised BatchNorm: the statistics and the backward sums of one rank as f64 records, merged over ranks in index order -------
+// record[c] = {rows, mean_c, M2_c}, M2 = sum (x - mean_c)^2, from the partials of bn_colstats_kernel<0> about the pivot x[0][c]:
+// mean = pivot + a / m, M2 = b - a^2 / m.  One wavefront per channel, f64, the order of bn_finalize_kernel.
+__global__ void bn_record_kernel(const float* __restrict__ part, const float* __restrict__ x, int nblk, int C, int64_t rows,
+                                 double* __restrict__ record) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (c >= C) return;
+  double a = 0.0, b = 0.0;
+  for (int k = lane; k < nblk; k += 64) { a += (double)part[((int64_t)k * 2 + 0) * C + c]; b += (double)part[((int64_t)k * 2 + 1) * C + c]; }
+  a = wave_sum_f64(a); b = wave_sum_f64(b);
+  if (lane != 0) return;
+  const double m = (double)rows;
+  const double dm = a / m;
+  double m2 = b - a * dm;
+  if (m2 < 0.0) m2 = 0.0;
+  record[(int64_t)c * 3 + 0] = m;
+  record[(int64_t)c * 3 + 1] = (double)x[c] + dm;
+  record[(int64_t)c * 3 + 2] = m2;
+}
+
+// records[world][C][3] -> mean, rstd and the running estimates of the union of the ranks' rows.  The records are merged pairwise in
+// index order by Chan's update (delta = mean_b - mean_a, M2 = M2_a + M2_b + delta^2 n_a n_b / n), one thread per channel, all in f64:
+// every rank that holds the same records gets the same bits.  The running variance is the unbiased one over the TOTAL count.
+__global__ void bn_merge_records_kernel(const double* __restrict__ records, int world, int C, float eps, float momentum,
+                                        float* __restrict__ mean, float* __restrict__ rstd,
+                                        float* __restrict__ running_mean, float* __restrict__ running_var,
+                                        double* __restrict__ total_rows) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double n = records[(int64_t)c * 3 + 0], mu = records[(int64_t)c * 3 + 1], m2 = records[(int64_t)c * 3 + 2];
+  for (int w = 1; w < world; ++w) {
+    const double* r = records + ((int64_t)w * C + c) * 3;
+    const double nb = r[0], nt = n + nb;
+    const double delta = r[1] - mu;
+    mu += delta * (nb / nt);
+    m2 += r[2] + delta * delta * (n * nb / nt);
+    n = nt;
+  }
+  if (c == 0 && total_rows) *total_rows = n;      // the count is the same in every channel
+  double var = m2 / n;
+  if (var < 0.0) var = 0.0;
+  mean[c] = (float)mu;
+  rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+  if (running_mean) {
+    const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
+    running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * mu);
+    running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
+  }
+}
+
+// bn_sum_partials_kernel that keeps the f64 totals: sums64[2][C] = (sum g, sum g*xhat) for the exchange; dbeta, dgamma are their f32
+// roundings, the values the unsynchronised backward returns
+__global__ void bn_sum_partials_f64_kernel(const float* __restrict__ part, int nblk, int C, double* __restrict__ sums64,
+                                           float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int lane = threadIdx.x & 63;
+  const int idx = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (idx >= 2 * C) return;
+  const int which = idx / C, c = idx % C;
+  double a = 0.0;
+  for (int k = lane; k < nblk; k += 64) a += (double)part[((int64_t)k * 2 + which) * C + c];
+  a = wave_sum_f64(a);
+  if (lane != 0) return;
+  sums64[idx] = a;
+  if (which == 0) dbeta[c] = (float)a; else dgamma[c] = (float)a;
+}
+
+// sums[2][C] (f32, what bn_lrelu_bwd_apply_kernel reads) = the ranks' sums64[world][2][C] added in index order in f64
+__global__ void bn_merge_sums_kernel(const double* __restrict__ sums64, int world, int C, float* __restrict__ sums) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 2 * C) return;
+  double a = sums64[idx];
+  for (int w = 1; w < world; ++w) a += sums64[(int64_t)w * 2 * C + idx];
+  sums[idx] = (float)a;
+}
+
 // y = lrelu((x-mean)*rstd*gamma+beta)
 __global__ __launch_bounds__(256) void bn_lrelu_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                              const float* __restrict__ rstd, const float* __restrict__ gamma,
@@ -180,14 +256,15 @@ __global__ __launch_bounds__(256) void bn_lrelu_apply_kernel(const float* __rest
   }
 }
 
-// training: dx = gamma*rstd/M * (M*g - sum_g - xhat*sum_gxhat); eval (train=0): dx = gamma*rstd*g
+// training: dx = gamma*rstd/M * (M*g - sum_g - xhat*sum_gxhat); eval (train=0): dx = gamma*rstd*g.  M = m: the rows the sums were
+// taken over -- `rows`, or *m_total (device), all ranks' rows, when the sums are the merged ones (synchronised BatchNorm)
 __global__ __launch_bounds__(256) void bn_lrelu_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                  const float* __restrict__ mean, const float* __restrict__ rstd,
                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                 const float* __restrict__ sums, float slope, int64_t rows, int C,
-                                                                 int train, float* __restrict__ dx) {
+                                                                 const float* __restrict__ sums, float slope, int64_t rows, const double* __restrict__ m_total,
+                                                                 int C, int train, float* __restrict__ dx) {
   const int64_t total = rows * C;
-  const float inv_m = 1.f / (float)rows;
+  const float inv_m = 1.f / (m_total ? (float)*m_total : (float)rows);
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(idx % C);
@@ -415,8 +492,83 @@ int odvae_batchnorm_lrelu_bwd_f32(const float* x, const float* dy, int64_t rows,
   // dbeta = sum g ; dgamma = sum g*xhat
   hipMemcpyAsync(dbeta, sums, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, st);
   hipMemcpyAsync(dgamma, sums + C, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, st);
-  hipLaunchKernelGGL(bn_lrelu_bwd_apply_kernel, dim3(grid_1d(rows * C)), dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, sums, slope, rows, C, train, dx);
+  hipLaunchKernelGGL(bn_lrelu_bwd_apply_kernel, dim3(grid_1d(rows * C)), dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, sums, slope, rows, nullptr, C, train, dx);
   ODVAE_LAUNCH_CHECK("batchnorm_lrelu_bwd");
+  return ODVAE_OK;
+}
+
+// ---- synchronised BatchNorm + LeakyReLU: the forward and the backward cut where the ranks exchange ---------------------------------
+// forward: stats_record (each rank) -> exchange -> stats_merge -> odvae_batchnorm_lrelu_fwd_f32(train = 0) with the merged mean / rstd;
+// backward: bwd_sums (each rank) -> exchange -> bwd_dx.  Workspace of the three that take one: odvae_batchnorm_workspace_bytes(rows, C).
+size_t odvae_batchnorm_sync_record_bytes(int C) { return (size_t)C * 3 * sizeof(double); }
+size_t odvae_batchnorm_sync_sums_bytes(int C) { return (size_t)C * 2 * sizeof(double); }
+
+int odvae_batchnorm_sync_stats_record_f32(const float* x, int64_t rows, int C, double* record, size_t record_bytes,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(x && rows > 0 && C > 0, "batchnorm_sync_stats_record: bad arguments");
+  const size_t need_rec = odvae_batchnorm_sync_record_bytes(C);
+  if (!record || record_bytes < need_rec) { odvae_set_error("batchnorm_sync_stats_record: the record needs %zu bytes", need_rec); return ODVAE_ERR_WORKSPACE; }
+  const size_t need = odvae_batchnorm_workspace_bytes(rows, C);
+  if (!workspace || workspace_bytes < need) { odvae_set_error("batchnorm_sync_stats_record: needs %zu workspace bytes", need); return ODVAE_ERR_WORKSPACE; }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  const int nblk = stat_blocks(rows);
+  const int rpb = (int)ceil_div64(rows, nblk);
+  const int nb = (int)ceil_div64(rows, rpb);
+  hipLaunchKernelGGL((bn_colstats_kernel<0>), dim3(nb), dim3(256), 0, st, x, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, rows, C, rpb, part);
+  hipLaunchKernelGGL(bn_record_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, x, nb, C, rows, record);
+  ODVAE_LAUNCH_CHECK("batchnorm_sync_stats_record");
+  return ODVAE_OK;
+}
+
+// records: [world][C][3] f64, rank-major; running_mean / running_var may be NULL (no running statistics); total_rows (one f64 on the
+// device, may be NULL): the rows of all ranks, what bwd_dx divides by -- it never passes through the host.  f32 and bf16 activations alike.
+int odvae_batchnorm_sync_stats_merge(const double* records, size_t records_bytes, int world, int C, float eps, float momentum,
+                                     float* mean, float* rstd, float* running_mean, float* running_var, double* total_rows, void* stream) {
+  ODVAE_CHECK_ARG(mean && rstd && world > 0 && C > 0, "batchnorm_sync_stats_merge: bad arguments");
+  ODVAE_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "batchnorm_sync_stats_merge: running_mean and running_var are given together or not at all");
+  const size_t need = (size_t)world * odvae_batchnorm_sync_record_bytes(C);
+  if (!records || records_bytes < need) { odvae_set_error("batchnorm_sync_stats_merge: the records need %zu bytes", need); return ODVAE_ERR_WORKSPACE; }
+  hipLaunchKernelGGL(bn_merge_records_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), records, world, C, eps, momentum,
+                     mean, rstd, running_mean, running_var, total_rows);
+  ODVAE_LAUNCH_CHECK("batchnorm_sync_stats_merge");
+  return ODVAE_OK;
+}
+
+// sums: [2][C] f64 = (sum g, sum g*xhat) over this rank's rows; dbeta, dgamma: the same local sums in f32
+int odvae_batchnorm_sync_bwd_sums_f32(const float* x, const float* dy, int64_t rows, int C, const float* gamma, const float* beta,
+                                      const float* mean, const float* rstd, float slope, double* sums, size_t sums_bytes,
+                                      float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(x && dy && gamma && beta && mean && rstd && dgamma && dbeta && rows > 0 && C > 0, "batchnorm_sync_bwd_sums: bad arguments");
+  const size_t need_sums = odvae_batchnorm_sync_sums_bytes(C);
+  if (!sums || sums_bytes < need_sums) { odvae_set_error("batchnorm_sync_bwd_sums: the sums need %zu bytes", need_sums); return ODVAE_ERR_WORKSPACE; }
+  const size_t need = odvae_batchnorm_workspace_bytes(rows, C);
+  if (!workspace || workspace_bytes < need) { odvae_set_error("batchnorm_sync_bwd_sums: needs %zu workspace bytes", need); return ODVAE_ERR_WORKSPACE; }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  const int nblk = stat_blocks(rows);
+  const int rpb = (int)ceil_div64(rows, nblk);
+  const int nb = (int)ceil_div64(rows, rpb);
+  hipLaunchKernelGGL((bn_colstats_kernel<1>), dim3(nb), dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, slope, rows, C, rpb, part);
+  hipLaunchKernelGGL(bn_sum_partials_f64_kernel, dim3(ceil_div(2 * C, 4)), dim3(256), 0, st, part, nb, C, sums, dgamma, dbeta);
+  ODVAE_LAUNCH_CHECK("batchnorm_sync_bwd_sums");
+  return ODVAE_OK;
+}
+
+// sums_all: [world][2][C] f64, rank-major; m_total: the rows of all ranks, on the device (stats_merge's total_rows).  dx of this rank's rows by bn_lrelu_bwd_apply_kernel.
+int odvae_batchnorm_sync_bwd_dx_f32(const float* x, const float* dy, int64_t rows, int C, const float* gamma, const float* beta,
+                                    const float* mean, const float* rstd, float slope, const double* sums_all, size_t sums_bytes,
+                                    int world, const double* m_total, float* dx, void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(x && dy && gamma && beta && mean && rstd && dx && rows > 0 && C > 0 && world > 0 && m_total, "batchnorm_sync_bwd_dx: bad arguments");
+  const size_t need_sums = (size_t)world * odvae_batchnorm_sync_sums_bytes(C);
+  if (!sums_all || sums_bytes < need_sums) { odvae_set_error("batchnorm_sync_bwd_dx: the sums need %zu bytes", need_sums); return ODVAE_ERR_WORKSPACE; }
+  const size_t need = odvae_batchnorm_workspace_bytes(rows, C);
+  if (!workspace || workspace_bytes < need) { odvae_set_error("batchnorm_sync_bwd_dx: needs %zu workspace bytes", need); return ODVAE_ERR_WORKSPACE; }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* sums = static_cast<float*>(workspace) + (size_t)stat_blocks(rows) * 2 * C;
+  hipLaunchKernelGGL(bn_merge_sums_kernel, dim3(ceil_div(2 * C, 256)), dim3(256), 0, st, sums_all, world, C, sums);
+  hipLaunchKernelGGL(bn_lrelu_bwd_apply_kernel, dim3(grid_1d(rows * C)), dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, sums, slope, rows, m_total, C, 1, dx);
+  ODVAE_LAUNCH_CHECK("batchnorm_sync_bwd_dx");
   return ODVAE_OK;
 }
 

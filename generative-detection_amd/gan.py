@@ -47,8 +47,15 @@ class Conv4x4(nn.Conv2d):
 
 
 class BatchNormLReLU(nn.BatchNorm2d):
-    """BatchNorm2d (batch statistics in training, running statistics in eval; not synchronised across ranks,
-    as in the reference) fused with the LeakyReLU(0.2) that follows it in the PatchGAN."""
+    """BatchNorm2d (batch statistics in training, running statistics in eval) fused with the LeakyReLU(0.2) that follows it in the
+    PatchGAN.  `dist_group` = None: the statistics are this rank's own, as under the reference's default `sync_batchnorm: False`.
+    A process group of more than one rank (set by Trainer(sync_batchnorm=True)): every training-mode forward takes mean and variance
+    over all ranks' rows and the backward the two gradient sums, what torch.nn.SyncBatchNorm computes; the running estimates then
+    hold the same bits on every rank.  The attribute is no parameter and no buffer: the state_dict does not change."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.dist_group = None          # set by the Trainer in a data-parallel run with sync_batchnorm
 
     def forward(self, x):
         return ops.batchnorm_lrelu(x, self, 0.2)
@@ -168,6 +175,10 @@ class NLayerDiscriminator(nn.Module):
 
     def actnorm_layers(self):
         return [m for m in self.main if isinstance(m, ActNormLReLU)]
+
+    def batchnorm_layers(self):
+        """The BatchNorm layers (main.3/6/9; none under use_actnorm): what `sync_batchnorm` synchronises"""
+        return [m for m in self.main if isinstance(m, BatchNormLReLU)]
 
     def actnorm_uninitialized(self):
         """True while an ActNorm layer still waits for its first training forward (host-side flags only)"""

@@ -201,12 +201,101 @@ class _BatchNormLReLU(Function):
         return dx, dg, db, None, None, None, None, None, None
 
 
+def _gather_f64(local, group, world):
+    """[world, *local.shape]: every rank's `local` (f64, device), rank-major, the same bits on every rank.  A zero-filled tensor in
+    which the rank fills its own slot, summed over the group: adding zeros is exact, so this is an all-gather that runs on gloo (which
+    has no all_gather of device tensors) and on nccl alike, and on nccl it stays on the stream (no host synchronisation)."""
+    import torch.distributed as dist
+    buf = torch.zeros((world,) + tuple(local.shape), dtype=torch.float64, device=local.device)
+    buf[dist.get_rank(group)].copy_(local)
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    return buf
+
+
+class _SyncBatchNormLReLU(Function):
+    """Training-mode BatchNorm + LeakyReLU with the statistics of all ranks of `group` (torch.nn.SyncBatchNorm: BatchNorm2d on the
+    concatenated batch), f32 or bf16 activations.  Forward: local record -> one exchange -> merge (mean, rstd, running estimates, the
+    same bits on every rank) -> the eval-form apply.  Backward: local sums -> one exchange -> dx; dgamma, dbeta stay the local sums (the
+    gradient all-reduce adds them like every other parameter gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, slope, group, world):
+        L = _L()
+        bf = x.dtype == BF16
+        sfx = "bf16" if bf else "f32"
+        x = _cl(x, BF16) if bf else _cl(x)
+        n, c, h, w = x.shape
+        rows = n * h * w
+        dev = x.device
+        st = _lib.stream_ptr()
+        wp, wn = _ws(L.odvae_batchnorm_workspace_bytes(rows, c), x)
+        record = torch.empty(c, 3, dtype=torch.float64, device=dev)
+        _lib.check(getattr(L, "odvae_batchnorm_sync_stats_record_" + sfx)(x.data_ptr(), rows, c, record.data_ptr(), record.numel() * 8, wp, wn, st),
+                   "batchnorm_sync_stats_record_" + sfx)
+        records = _gather_f64(record, group, world)
+        mean = torch.empty(c, dtype=torch.float32, device=dev)
+        rstd = torch.empty(c, dtype=torch.float32, device=dev)
+        total = torch.empty(1, dtype=torch.float64, device=dev)
+        _lib.check(L.odvae_batchnorm_sync_stats_merge(records.data_ptr(), records.numel() * 8, world, c, float(eps), float(momentum),
+                                                      mean.data_ptr(), rstd.data_ptr(), _lib.ptr(running_mean), _lib.ptr(running_var),
+                                                      total.data_ptr(), st), "batchnorm_sync_stats_merge")
+        y = _new_cl(n, c, h, w, x, dtype=BF16 if bf else torch.float32)
+        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        _lib.check(getattr(L, "odvae_batchnorm_lrelu_fwd_" + sfx)(x.data_ptr(), rows, c, g.data_ptr(), b.data_ptr(), float(eps), float(momentum),
+                                                                   float(slope), 0, mean.data_ptr(), rstd.data_ptr(), None, None,
+                                                                   y.data_ptr(), None, 0, st), "batchnorm_lrelu_fwd_" + sfx)
+        ctx.slope, ctx.group, ctx.world, ctx.total, ctx.sfx = float(slope), group, world, total, sfx
+        ctx.save_for_backward(x, gamma, beta, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        x, gamma, beta, mean, rstd = ctx.saved_tensors
+        sfx, world = ctx.sfx, ctx.world
+        bf = sfx == "bf16"
+        dy = _cl(dy, BF16) if bf else _cl(dy)
+        n, c, h, w = x.shape
+        rows = n * h * w
+        dev = x.device
+        st = _lib.stream_ptr()
+        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        dg = torch.empty(c, dtype=torch.float32, device=dev)
+        db = torch.empty(c, dtype=torch.float32, device=dev)
+        sums = torch.empty(2, c, dtype=torch.float64, device=dev)
+        wp, wn = _ws(L.odvae_batchnorm_workspace_bytes(rows, c), x)
+        _lib.check(getattr(L, "odvae_batchnorm_sync_bwd_sums_" + sfx)(x.data_ptr(), dy.data_ptr(), rows, c, g.data_ptr(), b.data_ptr(),
+                                                                       mean.data_ptr(), rstd.data_ptr(), ctx.slope, sums.data_ptr(), sums.numel() * 8,
+                                                                       dg.data_ptr(), db.data_ptr(), wp, wn, st), "batchnorm_sync_bwd_sums_" + sfx)
+        sums_all = _gather_f64(sums, ctx.group, world)
+        dx = _new_cl(n, c, h, w, x, dtype=BF16 if bf else torch.float32)
+        _lib.check(getattr(L, "odvae_batchnorm_sync_bwd_dx_" + sfx)(x.data_ptr(), dy.data_ptr(), rows, c, g.data_ptr(), b.data_ptr(),
+                                                                     mean.data_ptr(), rstd.data_ptr(), ctx.slope, sums_all.data_ptr(),
+                                                                     sums_all.numel() * 8, world, ctx.total.data_ptr(), dx.data_ptr(), wp, wn, st),
+                   "batchnorm_sync_bwd_dx_" + sfx)
+        return dx, dg, db, None, None, None, None, None, None, None
+
+
+def _sync_group(bn):
+    """(group, world) when `bn` is to take its training statistics over a process group of more than one rank, else (None, 1):
+    torch.nn.SyncBatchNorm's own condition -- a training-mode module with a group; eval never exchanges anything."""
+    group = getattr(bn, "dist_group", None)
+    if group is None or not bn.training:
+        return None, 1
+    world = torch.distributed.get_world_size(group)
+    return (group, world) if world > 1 else (None, 1)
+
+
 def batchnorm_lrelu(x, bn, slope):
-    """BatchNorm2d `bn` (parameter/buffer holder) + LeakyReLU(slope); updates running stats in training mode."""
+    """BatchNorm2d `bn` (parameter/buffer holder) + LeakyReLU(slope); updates running stats in training mode.  With `bn.dist_group` a
+    process group of more than one rank, the training statistics are those of all its ranks' rows (_SyncBatchNormLReLU)."""
     train = bn.training or not bn.track_running_stats
     if train and bn.track_running_stats and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     momentum = 0.1 if bn.momentum is None else bn.momentum
+    group, world = _sync_group(bn)
+    if group is not None:
+        return _SyncBatchNormLReLU.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, slope, group, world)
     if x.dtype == BF16:     # the bf16 discriminator: activations bf16, statistics and parameters f32
         return _BatchNormLReLUB.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, slope, train)
     return _BatchNormLReLU.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, slope, train)

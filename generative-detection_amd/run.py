@@ -40,12 +40,14 @@ def parse(argv):
 
 def trainer_kwargs(trainer_cfg):
     """The `lightning.trainer` keys of the yaml this Trainer honours: gradient_clip_val, precision, detect_anomaly (yaml:138; absent
-    = None, which leaves the choice to ODVAE_DETECT_ANOMALY) and accumulate_grad_batches (yaml:134; passed on only when it is not 1)."""
+    = None, which leaves the choice to ODVAE_DETECT_ANOMALY), accumulate_grad_batches (yaml:134; passed on only when it is not 1) and sync_batchnorm (passed on only when the yaml sets it)."""
     kw = {"gradient_clip_val": trainer_cfg.get("gradient_clip_val", None), "precision": trainer_cfg.get("precision", None),
           "detect_anomaly": trainer_cfg.get("detect_anomaly", None)}
     accumulate = trainer_cfg.get("accumulate_grad_batches", 1)
     if accumulate != 1:      # (yaml:134; configure_learning_rate already multiplies the learning rate by it)
         kw["accumulate_grad_batches"] = accumulate
+    if "sync_batchnorm" in trainer_cfg:      # (PL: SyncBatchNorm over the discriminator's BatchNorm layers; Trainer refuses a non-bool)
+        kw["sync_batchnorm"] = trainer_cfg["sync_batchnorm"]
     return kw
 
 

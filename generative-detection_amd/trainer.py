@@ -32,7 +32,8 @@ class _TrainerHandle:
 class Trainer:
     def __init__(self, model, gradient_clip_val=None, optimizer_indices=(0, 1), process_group=None, bucket_mb=None, precision=None,
                  distributed=None, comm_dtype=None, callbacks=(), logger=None, comm_f32_accumulate=False,
-                 detect_anomaly=None, accumulate_grad_batches=1, perceptual_precision=None, discriminator_precision=None):
+                 detect_anomaly=None, accumulate_grad_batches=1, perceptual_precision=None, discriminator_precision=None,
+                 sync_batchnorm=False):
         """optimizer_indices: which of the model's optimizers run each batch; (0,) is the "rec+KL only" benchmark
         configuration (discriminator off, optimizer 1 skipped -- SURVEY.md 8(d)).
         comm_dtype: dtype of the gradient buckets on the wire; None = f32 in every precision -- what the reference's `strategy: ddp`
@@ -51,7 +52,14 @@ class Trainer:
         optimizer.step() and the global_step increment happen on the window's last batch only.  1 = a step after
         every batch.
         perceptual_precision: 32 or "bf16" for the loss's LPIPS-style net (AutoencoderKL.set_precision); None leaves it alone.
-        discriminator_precision: the same for the loss's PatchGAN discriminator (NLayerDiscriminator.set_precision)."""
+        discriminator_precision: the same for the loss's PatchGAN discriminator (NLayerDiscriminator.set_precision).
+        sync_batchnorm: lightning.trainer.sync_batchnorm of the yaml / `--sync_batchnorm True` (PL 1.9 runs
+        torch.nn.SyncBatchNorm.convert_sync_batchnorm over the module; its only BatchNorm layers are the discriminator's three).  True in a
+        data-parallel run over more than one rank: those layers take their training statistics and backward sums over this trainer's
+        process group (gan.BatchNormLReLU.dist_group).  Not data-parallel, one rank, or use_actnorm: nothing changes."""
+        if not isinstance(sync_batchnorm, bool):
+            raise ValueError("sync_batchnorm must be True or False, got %r" % (sync_batchnorm,))
+        self.sync_batchnorm = sync_batchnorm
         if isinstance(accumulate_grad_batches, bool) or not isinstance(accumulate_grad_batches, int) or accumulate_grad_batches < 1:
             raise ValueError("accumulate_grad_batches must be an integer >= 1, got %r" % (accumulate_grad_batches,))
         self.accumulate_grad_batches = accumulate_grad_batches
@@ -112,6 +120,16 @@ class Trainer:
                 if hasattr(m, "dist_group") and hasattr(m, "refresh_initialized"):
                     m.dist_group = process_group if process_group is not None else torch.distributed.group.WORLD
                     m.refresh_initialized()
+        # sync_batchnorm: the discriminator's BatchNorm layers get this trainer's group, or lose one a former Trainer gave them
+        group = None
+        if distributed and sync_batchnorm:
+            group = process_group if process_group is not None else torch.distributed.group.WORLD
+            if torch.distributed.get_world_size(group) < 2:
+                group = None
+        for m in model.modules():
+            if hasattr(m, "batchnorm_layers"):
+                for bn in m.batchnorm_layers():
+                    bn.dist_group = group
 
     # PL-1.9 toggle_optimizer: parameters owned by the *other* optimizers stop requiring grad; parameters in no
     # optimizer (loss.logvar, the frozen LPIPS net) are left alone

@@ -372,6 +372,32 @@ int odvae_batchnorm_lrelu_fwd_f32(const float* x, int64_t rows, int C, const flo
 int odvae_batchnorm_lrelu_bwd_f32(const float* x, const float* dy, int64_t rows, int C, const float* gamma, const float* beta,
                                   const float* mean, const float* rstd, float slope, int train,
                                   float* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+/* Synchronised BatchNorm + LeakyReLU (torch.nn.SyncBatchNorm = BatchNorm2d on the ranks' rows together): the training forward and
+ * backward cut where the ranks exchange a few KB.  The library makes no collective; the caller carries the f64 buffers between ranks.
+ *   forward : stats_record (each rank) -> gather -> stats_merge -> odvae_batchnorm_lrelu_fwd_*(train = 0) with the merged mean / rstd
+ *   backward: bwd_sums (each rank) -> gather -> bwd_dx
+ * record  : double [C][3] = {rows, mean_c, M2_c}, M2 = sum (x - mean_c)^2, from the sums about the pivot x[0][c].
+ * records : double [world][C][3], merged pairwise in index order by Chan's update in f64 (the same bits on every rank that holds the same
+ *           records) into f32 mean, rstd = 1 / sqrt(M2 / n + eps), and the momentum update of the running estimates with the unbiased
+ *           variance over the total count (running_mean = running_var = NULL: none).  One merge serves f32 and bf16 activations.
+ * sums    : double [2][C] = (sum g, sum g * xhat), g = dy * lrelu'(u); dbeta, dgamma are the same local sums in f32.
+ *           total_rows (one f64 on the device, may be NULL) receives the rows of all ranks.
+ * sums_all: double [world][2][C], added in index order in f64; m_total: the rows of all ranks ON THE DEVICE (the merge's total_rows: row
+ *           counts may differ per rank, and the total never passes through the host); dx by the unsynchronised backward's expression.
+ * A record / sums buffer smaller than odvae_batchnorm_sync_record_bytes(C) / _sums_bytes(C) (times world where all ranks' are read) is
+ * ODVAE_ERR_WORKSPACE with the needed size.  Workspace where one is taken: odvae_batchnorm_workspace_bytes(rows, C). */
+size_t odvae_batchnorm_sync_record_bytes(int C);
+size_t odvae_batchnorm_sync_sums_bytes(int C);
+int odvae_batchnorm_sync_stats_record_f32(const float* x, int64_t rows, int C, double* record, size_t record_bytes,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+int odvae_batchnorm_sync_stats_merge(const double* records, size_t records_bytes, int world, int C, float eps, float momentum,
+                                     float* mean, float* rstd, float* running_mean, float* running_var, double* total_rows, void* stream);
+int odvae_batchnorm_sync_bwd_sums_f32(const float* x, const float* dy, int64_t rows, int C, const float* gamma, const float* beta,
+                                      const float* mean, const float* rstd, float slope, double* sums, size_t sums_bytes,
+                                      float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+int odvae_batchnorm_sync_bwd_dx_f32(const float* x, const float* dy, int64_t rows, int C, const float* gamma, const float* beta,
+                                    const float* mean, const float* rstd, float slope, const double* sums_all, size_t sums_bytes,
+                                    int world, const double* m_total, float* dx, void* workspace, size_t workspace_bytes, void* stream);
 /* ActNorm ([UPSTREAM] taming ActNorm: h = scale[c] * (x + loc[c])) + LeakyReLU(slope), x [rows][C].
  * init: loc = -mean_c, scale = 1 / (std_c + eps), std_c the unbiased standard deviation over the rows (rows >= 2), written on the device.
  * bwd: dx = scale * g, dloc = scale * sum g, dscale = sum g (x + loc), g = dy * lrelu'(h); dloc = dscale = NULL: dx only, no workspace. */
@@ -574,6 +600,16 @@ int odvae_batchnorm_lrelu_fwd_bf16(const void* x, int64_t rows, int C, const flo
 int odvae_batchnorm_lrelu_bwd_bf16(const void* x, const void* dy, int64_t rows, int C, const float* gamma, const float* beta,
                                    const float* mean, const float* rstd, float slope, int train,
                                    void* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+/* odvae_batchnorm_sync_*_f32 with x, dy, dx bf16 (the merge is odvae_batchnorm_sync_stats_merge; the apply is
+ * odvae_batchnorm_lrelu_fwd_bf16 with train = 0) */
+int odvae_batchnorm_sync_stats_record_bf16(const void* x, int64_t rows, int C, double* record, size_t record_bytes,
+                                           void* workspace, size_t workspace_bytes, void* stream);
+int odvae_batchnorm_sync_bwd_sums_bf16(const void* x, const void* dy, int64_t rows, int C, const float* gamma, const float* beta,
+                                       const float* mean, const float* rstd, float slope, double* sums, size_t sums_bytes,
+                                       float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+int odvae_batchnorm_sync_bwd_dx_bf16(const void* x, const void* dy, int64_t rows, int C, const float* gamma, const float* beta,
+                                     const float* mean, const float* rstd, float slope, const double* sums_all, size_t sums_bytes,
+                                     int world, const double* m_total, void* dx, void* workspace, size_t workspace_bytes, void* stream);
 /* dx = dy * (y > 0 ? 1 : slope), all bf16, y the LeakyReLU's OUTPUT (slope > 0): the backward of odvae_conv4x4_bf16's epilogue */
 int odvae_leaky_relu_bwd_bf16(const void* y, const void* dy, void* dx, float slope, int64_t n, void* stream);
 
