@@ -53,6 +53,12 @@ class AutoencoderKL(LightningModule):
             self.monitor = monitor
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
+        # test hook: {"posterior_eps", "samples_eps"} tensors replace the host RNG draws of forward and log_images
+        self.injected_noise = None
+
+    def _noise(self, key):
+        noise = getattr(self, "injected_noise", None)
+        return None if noise is None else noise.get(key)
 
     def set_precision(self, precision, perceptual_precision=None, discriminator_precision=None):
         """The trainer's `precision` (configs/autoencoder/pose/autoencoder_kl_16x16x16.yaml:139; PL-1.9 accepts 32, "32", 16, "bf16"):
@@ -104,17 +110,18 @@ class AutoencoderKL(LightningModule):
 
     def forward(self, input, sample_posterior=True):
         posterior = self.encode(input)
-        z = posterior.sample() if sample_posterior else posterior.mode()
+        z = posterior.sample(self._noise("posterior_eps")) if sample_posterior else posterior.mode()
         return self.decode(z), posterior
 
     def get_input(self, batch, k):
+        """[N, H, W, C] (or [N, H, W]) of the batch -> f32 NCHW on the model's device"""
         x = batch[k]
         if len(x.shape) == 3:
             x = x[..., None]
-        return x.permute(0, 3, 1, 2).to(memory_format=torch.contiguous_format).float()
+        return _lib.upload(x.permute(0, 3, 1, 2).to(memory_format=torch.contiguous_format).float(), self.device)
 
     def training_step(self, batch, batch_idx, optimizer_idx):
-        inputs = self.get_input(batch, self.image_key).to(self.device)
+        inputs = self.get_input(batch, self.image_key)
         reconstructions, posterior = self(inputs)
         if optimizer_idx == 0:
             aeloss, log_dict_ae = self.loss(inputs, reconstructions, posterior, optimizer_idx, self.global_step,
@@ -127,6 +134,35 @@ class AutoencoderKL(LightningModule):
         self.log("discloss", discloss, prog_bar=True, logger=True, on_step=True, on_epoch=True)
         self.log_dict(log_dict_disc, prog_bar=False, logger=True, on_step=True, on_epoch=False)
         return discloss
+
+    def validation_step(self, batch, batch_idx):
+        inputs = self.get_input(batch, self.image_key)
+        reconstructions, posterior = self(inputs)
+        _, log_dict_ae = self.loss(inputs, reconstructions, posterior, 0, self.global_step,
+                                   last_layer=self.get_last_layer(), split="val")
+        _, log_dict_disc = self.loss(inputs, reconstructions, posterior, 1, self.global_step,
+                                     last_layer=self.get_last_layer(), split="val")
+        self.log("val/rec_loss", log_dict_ae["val/rec_loss"])
+        self.log_dict(log_dict_ae)
+        self.log_dict(log_dict_disc)
+        return self.log_dict
+
+    @torch.no_grad()
+    def log_images(self, batch, only_inputs=False, **kwargs):
+        log = dict()
+        x = self.get_input(batch, self.image_key)
+        if not only_inputs:
+            xrec, posterior = self(x)
+            if x.shape[1] > 3:      # more than three channels (label maps): both sides go through the fixed `colorize` projection
+                assert xrec.shape[1] == x.shape[1], "reconstruction has %d channels, input %d" % (xrec.shape[1], x.shape[1])
+                x, xrec = self.to_rgb(x), self.to_rgb(xrec)
+            eps = self._noise("samples_eps")
+            if eps is None:
+                eps = torch.randn(tuple(posterior.mean.shape))      # drawn on the host, as DiagonalGaussianDistribution.sample does
+            log["samples"] = self.decode(_lib.upload(eps.float(), self.device))
+            log["reconstructions"] = xrec
+        log["inputs"] = x
+        return log
 
     def configure_optimizers(self):
         lr = self.learning_rate

@@ -421,6 +421,78 @@ bool an_vec4(int C, const void* a, const void* b, const void* c, const void* d, 
   return C % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0;
 }
 
+// ---- the scalar terms of the GAN losses over the discriminator's logits ([UPSTREAM] ldm contperceptual.py LPIPSWithDiscriminator.forward,
+// taming vqperceptual.py hinge_d_loss / vanilla_d_loss) ------------------------------------------------------------------------------------
+// out6 = [mean real, mean fake, mean relu(1 - real), mean relu(1 + fake), mean softplus(-real), mean softplus(fake)].
+// The logits are a few thousand values (N x 30 x 30 at 256 x 256), so every term is taken in f64 from the f32 logit: sums of logits that
+// are multiples of 2^-k are exact, and the softplus / sigmoid terms reach the result rounded once.  Three stages, all in a fixed order (no
+// atomics): wave shuffles, LDS across the four waves of a block, partial[block][6] in the workspace, one final block.
+constexpr int kLogitBlocks = 1024;      // grid cap of the partial stage: past 1024 * 256 logits a thread loops
+int logit_blocks(int64_t n_real, int64_t n_fake) { return grid_1d(std::max(n_real, n_fake), kLogitBlocks); }
+
+// comparisons, not fmax: a NaN logit stays a NaN in each of its terms
+__device__ __forceinline__ double relu_f64(double t) { return t < 0.0 ? 0.0 : t; }
+// max(x, 0) + log1p(exp(-|x|)): no overflow at +100, no cancellation at -100 (torch's thresholded form to rounding)
+__device__ __forceinline__ double softplus_f64(double x) { return relu_f64(x) + log1p(exp(-fabs(x))); }
+__device__ __forceinline__ double sigmoid_f64(double x) {
+  if (x >= 0.0) return 1.0 / (1.0 + exp(-x));
+  const double e = exp(x);      // (a NaN comes this way and stays one)
+  return e / (1.0 + e);
+}
+
+__global__ __launch_bounds__(256) void logit_terms_partial_kernel(const float* __restrict__ real, int64_t n_real, const float* __restrict__ fake,
+                                                                  int64_t n_fake, double* __restrict__ part) {
+  __shared__ double sh[4][6];
+  double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = i0; i < n_real; i += step) {
+    const double x = (double)real[i];
+    a[0] += x; a[2] += relu_f64(1.0 - x); a[4] += softplus_f64(-x);
+  }
+  for (int64_t i = i0; i < n_fake; i += step) {
+    const double x = (double)fake[i];
+    a[1] += x; a[3] += relu_f64(1.0 + x); a[5] += softplus_f64(x);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    a[k] = wave_sum_f64(a[k]);
+    if (lane == 0) sh[wave][k] = a[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) part[(int64_t)blockIdx.x * 6 + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+}
+// one block of six waves, wave k sums term k over the blocks; the division by n in f64, then the one rounding to f32
+__global__ __launch_bounds__(384) void logit_terms_final_kernel(const double* __restrict__ part, int nblk, int64_t n_real, int64_t n_fake,
+                                                                float* __restrict__ out6) {
+  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
+  double s = 0.0;
+  for (int i = lane; i < nblk; i += 64) s += part[(int64_t)i * 6 + k];
+  s = wave_sum_f64(s);
+  if (lane != 0) return;
+  const int64_t n = (k & 1) ? n_fake : n_real;
+  out6[k] = n > 0 ? (float)(s / (double)n) : 0.f;
+}
+// d mean / d x = 1 / n; relu'(0) = 0 (strict inequalities, as torch); softplus' = sigmoid.  dout6 is read on the device.
+__global__ __launch_bounds__(256) void logit_terms_bwd_kernel(const float* __restrict__ real, int64_t n_real, const float* __restrict__ fake,
+                                                              int64_t n_fake, const float* __restrict__ dout6, float* __restrict__ dreal,
+                                                              float* __restrict__ dfake) {
+  const double d0 = (double)dout6[0], d1 = (double)dout6[1], d2 = (double)dout6[2], d3 = (double)dout6[3], d4 = (double)dout6[4], d5 = (double)dout6[5];
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+  if (dreal) {
+    for (int64_t i = i0; i < n_real; i += step) {
+      const double x = (double)real[i];
+      dreal[i] = (float)((d0 - (x < 1.0 ? d2 : 0.0) - d4 * sigmoid_f64(-x)) / (double)n_real);
+    }
+  }
+  if (dfake) {
+    for (int64_t i = i0; i < n_fake; i += step) {
+      const double x = (double)fake[i];
+      dfake[i] = (float)((d1 + (x > -1.0 ? d3 : 0.0) + d5 * sigmoid_f64(x)) / (double)n_fake);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -645,6 +717,38 @@ int odvae_leaky_relu_bwd_f32(const float* x, const float* dy, float* dx, float s
   ODVAE_CHECK_ARG(x && dy && dx && n > 0, "leaky_relu_bwd: bad arguments");
   hipLaunchKernelGGL(lrelu_bwd_kernel, dim3(grid_1d(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, dy, dx, slope, n);
   ODVAE_LAUNCH_CHECK("leaky_relu_bwd");
+  return ODVAE_OK;
+}
+
+size_t odvae_gan_logit_terms_workspace_bytes(int64_t n_real, int64_t n_fake) {
+  return (size_t)logit_blocks(n_real, n_fake) * 6 * sizeof(double);
+}
+
+int odvae_gan_logit_terms_f32(const float* real, int64_t n_real, const float* fake, int64_t n_fake, float* out6,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(fake && out6 && n_fake > 0, "gan_logit_terms: bad arguments (fake logits and out6 are needed)");
+  ODVAE_CHECK_ARG(n_real >= 0 && (real || n_real == 0), "gan_logit_terms: n_real = %lld but real is %s", (long long)n_real, real ? "given" : "null");
+  const int nblk = logit_blocks(n_real, n_fake);
+  const size_t need = (size_t)nblk * 6 * sizeof(double);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7) != 0) {
+    odvae_set_error("gan_logit_terms: needs %zu workspace bytes, 8-byte aligned", need);
+    return ODVAE_ERR_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double* part = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(logit_terms_partial_kernel, dim3(nblk), dim3(256), 0, st, real, n_real, fake, n_fake, part);
+  hipLaunchKernelGGL(logit_terms_final_kernel, dim3(1), dim3(384), 0, st, part, nblk, n_real, n_fake, out6);
+  ODVAE_LAUNCH_CHECK("gan_logit_terms");
+  return ODVAE_OK;
+}
+
+int odvae_gan_logit_terms_bwd_f32(const float* real, int64_t n_real, const float* fake, int64_t n_fake, const float* dout6,
+                                  float* dreal, float* dfake, void* stream) {
+  ODVAE_CHECK_ARG(fake && dout6 && n_fake > 0 && (dreal || dfake), "gan_logit_terms_bwd: bad arguments");
+  ODVAE_CHECK_ARG(n_real >= 0 && (real || n_real == 0) && (!dreal || n_real > 0), "gan_logit_terms_bwd: dreal needs real logits (n_real = %lld)", (long long)n_real);
+  hipLaunchKernelGGL(logit_terms_bwd_kernel, dim3(grid_1d(std::max(n_real, n_fake))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     real, n_real, fake, n_fake, dout6, dreal, dfake);
+  ODVAE_LAUNCH_CHECK("gan_logit_terms_bwd");
   return ODVAE_OK;
 }
 

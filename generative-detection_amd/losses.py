@@ -89,6 +89,10 @@ class LPIPSWithDiscriminator(nn.Module):
         self.disc_factor = disc_factor
         self.discriminator_weight = disc_weight
         self.disc_conditional = disc_conditional
+        # With the discriminator off (disc_factor == 0) upstream still evaluates D(x_rec), logs g_loss = -mean D(x_rec) and multiplies it by an
+        # exact 0 in the total.  True reproduces that logged value (one discriminator forward without a graph); False (default) skips the pass
+        # and logs 0.  Total loss, every other logged term and all gradients are the same either way.
+        self.log_exact_g_loss = False
 
     def _check_perceptual_weights(self):
         """Once per loss object: the reference cannot even be constructed without the real LPIPS weights ([UPSTREAM]
@@ -133,6 +137,111 @@ class LPIPSWithDiscriminator(nn.Module):
         d_weight = torch.norm(nll_grads) / (torch.norm(g_grads) + 1e-4)
         d_weight = torch.clamp(d_weight, 0.0, 1e4).detach()
         return d_weight * self.discriminator_weight
+
+    # ---- the plain loss ([UPSTREAM] ldm contperceptual.py LPIPSWithDiscriminator.forward) ---------------------------------------------
+    def _plain_nll(self, rec_sums, chw, weights=None):
+        """(nll_loss, weighted_nll_loss) = sum over everything / N of rec_loss / exp(logvar) + logvar, from the per-sample sums of rec_loss.
+        No +1e-8 beside exp(logvar) here (PoseLoss has one)."""
+        n = rec_sums.numel()
+        nll_sums = rec_sums / torch.exp(self.logvar) + self.logvar * chw
+        nll_loss = torch.sum(nll_sums) / n
+        if weights is None:
+            return nll_loss, nll_loss
+        w = torch.as_tensor(weights, dtype=nll_sums.dtype, device=nll_sums.device)
+        if w.numel() not in (1, n):
+            raise NotImplementedError("weights of shape %s: a per-pixel weight map is not on the HIP path (the L1 term arrives as per-sample "
+                                      "sums); a scalar or one weight per sample is" % (tuple(w.shape),))
+        return nll_loss, torch.sum(w.reshape(-1) * nll_sums) / n
+
+    def forward(self, inputs, reconstructions, posteriors, optimizer_idx, global_step, last_layer=None, cond=None, split="train",
+                weights=None):
+        if optimizer_idx == 1:
+            # the discriminator phase returns d_loss and the two logit means only: as in PoseLoss, the reconstruction (incl. LPIPS) and KL
+            # terms upstream evaluates first have no consumer and are not evaluated
+            return self._plain_discriminator_phase(inputs, reconstructions, global_step, cond, split)
+        if optimizer_idx != 0:
+            return None      # (upstream falls off the end of forward as well)
+        assert cond is None and not self.disc_conditional
+        dev = inputs.device
+        n, c, h, w = inputs.shape
+        chw = float(c * h * w)
+        rec_sums = ops.l1_masked_sum(inputs, reconstructions, None)      # per-sample sums of |x - x_rec|
+        if self.perceptual_weight > 0:
+            self._check_perceptual_weights()
+            p_loss = self.perceptual_loss(inputs, reconstructions)
+            rec_sums = rec_sums + self.perceptual_weight * p_loss.reshape(n) * chw
+        nll_loss, weighted_nll_loss = self._plain_nll(rec_sums, chw, weights)
+        rec_mean = rec_sums.detach().sum() / (n * chw)
+        kl_loss = torch.sum(posteriors.kl()) / n
+
+        if self.disc_factor > 0.0:
+            g_loss = -ops.gan_logit_terms(None, self.discriminator(reconstructions))[1]
+        elif self.log_exact_g_loss or (self.discriminator.training and self.discriminator.actnorm_uninitialized()):
+            # discriminator off: upstream still evaluates D(x_rec) (BatchNorm running statistics move, ActNorm layers initialise from this
+            # tensor on the first training batch) and multiplies the term by an exact 0; the forward runs here without a graph
+            with torch.no_grad():
+                g_loss = -ops.gan_logit_terms(None, self.discriminator(reconstructions.detach()))[1]
+            if not self.log_exact_g_loss:     # the forward ran for the initialisation alone: the logged value stays the shortcut's 0
+                g_loss = torch.zeros((), device=dev)
+        else:
+            g_loss = torch.zeros((), device=dev)
+        one_pass = None      # (g_nll, g_g) when the main backward is to start from the combined gradient at the reconstruction
+        if self.disc_factor > 0.0:
+            ll = last_layer if last_layer is not None else (self.last_layer[0] if getattr(self, "last_layer", None) else None)
+            if (self.ONE_PASS and weights is None and ll is not None and torch.is_grad_enabled() and reconstructions.requires_grad
+                    and not reconstructions.is_leaf):
+                try:
+                    d_weight, g_nll, g_g = self.adaptive_weight_one_pass(nll_loss, g_loss, reconstructions, ll)
+                    one_pass = (g_nll, g_g)
+                except RuntimeError:      # (a last layer the reconstruction's graph does not reach: upstream's fallback, as below)
+                    assert not self.training
+                    d_weight = torch.zeros((), device=dev)
+            else:
+                try:
+                    d_weight = self.calculate_adaptive_weight(nll_loss, g_loss, last_layer=last_layer)
+                except RuntimeError:
+                    assert not self.training
+                    d_weight = torch.zeros((), device=dev)
+        else:
+            d_weight = torch.zeros((), device=dev)
+        disc_factor = adopt_weight(self.disc_factor, global_step, threshold=self.discriminator_iter_start)
+
+        if one_pass is None:
+            loss = weighted_nll_loss + self.kl_weight * kl_loss + d_weight * disc_factor * g_loss
+        else:
+            # the reconstruction-dependent terms enter by VALUE (same expression, same order of additions) and their gradient through
+            # `surrogate`, whose derivative w.r.t. the reconstruction is d nll / d x_rec + d_weight * disc_factor * d g_loss / d x_rec; the
+            # value added is an exact 0.  logvar keeps its gradient through the same trick on the per-sample sums.
+            loss = weighted_nll_loss.detach() + self.kl_weight * kl_loss + d_weight * disc_factor * g_loss.detach()
+            grad_at_rec = (one_pass[0] + (d_weight * disc_factor) * one_pass[1]).detach()
+            surrogate = (reconstructions * grad_at_rec).sum()
+            nll_lv = self._plain_nll(rec_sums.detach(), chw)[0]
+            loss = loss + (surrogate - surrogate.detach()) + (nll_lv - nll_lv.detach())
+
+        log = {"{}/total_loss".format(split): loss.clone().detach().mean(),
+               "{}/logvar".format(split): self.logvar.detach(),
+               "{}/kl_loss".format(split): kl_loss.detach().mean(),
+               "{}/nll_loss".format(split): nll_loss.detach().mean(),
+               "{}/rec_loss".format(split): rec_mean,
+               "{}/d_weight".format(split): d_weight.detach(),
+               "{}/disc_factor".format(split): torch.tensor(disc_factor),
+               "{}/g_loss".format(split): g_loss.detach().mean()}
+        return loss, log
+
+    def _plain_discriminator_phase(self, inputs, reconstructions, global_step, cond, split):
+        """optimizer_idx == 1: hinge / vanilla loss of the discriminator on the target and the detached reconstruction; the two loss terms
+        and the two logged logit means come from one kernel (ops.gan_logit_terms)."""
+        assert cond is None and not self.disc_conditional
+        logits_real = self.discriminator(inputs.detach())
+        logits_fake = self.discriminator(reconstructions.detach())
+        disc_factor = adopt_weight(self.disc_factor, global_step, threshold=self.discriminator_iter_start)
+        terms = ops.gan_logit_terms(logits_real, logits_fake)
+        pair = (terms[2], terms[3]) if self.disc_loss is hinge_d_loss else (terms[4], terms[5])
+        d_loss = disc_factor * (0.5 * (pair[0] + pair[1]))
+        log = {"{}/disc_loss".format(split): d_loss.clone().detach().mean(),
+               "{}/logits_real".format(split): terms[0].detach(),
+               "{}/logits_fake".format(split): terms[1].detach()}
+        return d_loss, log
 
 
 class PoseLoss(LPIPSWithDiscriminator):

@@ -118,4 +118,4 @@ from .elementwise import (  # noqa: E402
     _MulMask, mul_mask, _LatentCombine, latent_combine, _PoseLosses, pose_losses, LINEAR_ACTS, _LinearAct, linear_act)
 from .patchgan import (  # noqa: E402
     _conv4x4_out, _Conv4x4, _conv4x4_i_raw, _Conv4x4I, conv4x4, _BatchNormLReLU, batchnorm_lrelu, _ActNormLReLU, actnorm_init, actnorm_lrelu, _LeakyReLU,
-    leaky_relu, _conv4x4_b_raw, _Conv4x4B, conv4x4_bf16, _BatchNormLReLUB, _gather_f64, _SyncBatchNormLReLU, _sync_group)
+    leaky_relu, _GanLogitTerms, gan_logit_terms, _conv4x4_b_raw, _Conv4x4B, conv4x4_bf16, _BatchNormLReLUB, _gather_f64, _SyncBatchNormLReLU, _sync_group)

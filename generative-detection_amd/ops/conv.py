@@ -304,4 +304,12 @@ def conv1x1(x, weight, bias=None, residual=None, out_f32=False):
     """out_f32: bf16 input only -- the result leaves the conv in f32 (no residual then)."""
     if x.dtype == BF16:
         return _ConvB.apply(x, weight, bias, residual, 4, bool(out_f32))
+    # (a forward-only call with output channels that are no multiple of 4 -- AutoencoderKL.to_rgb's 3 -- has always run on the GEMM and stays there)
+    needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias, residual))
+    if weight.shape[1] % 4 or (weight.shape[0] % 4 and needs_grad):
+        # The f32 GEMM stages float4 vectors along the contiguous axis of both operands: the input channels in the forward, the output
+        # channels too in the two backward products.  A layer it cannot take (the kl-f4 layout: quant_conv on 6-channel moments,
+        # post_quant_conv on the 3-channel latent) runs on the direct 3x3 kernel, which has no such rule, with the weight in the centre tap
+        # of an otherwise zero 3x3 stencil: the same sums, and nine times the multiplies of a layer that has a few dozen of them per pixel.
+        return conv3x3(x, torch.nn.functional.pad(weight, (1, 1, 1, 1)), bias, residual)
     return _Conv1x1.apply(x, weight, bias, residual)

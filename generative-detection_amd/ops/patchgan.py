@@ -1,5 +1,5 @@
 """PatchGAN discriminator pieces: the 4x4 conv, BatchNorm+LeakyReLU (f32: gan_f32.hip; bf16: conv_bf16.hip, gan_bf16.hip),
-ActNorm, LeakyReLU."""
+ActNorm, LeakyReLU, the scalar terms of the GAN losses over the logits (gan_f32.hip)."""
 import weakref
 
 import torch
@@ -380,6 +380,47 @@ class _LeakyReLU(Function):
 
 def leaky_relu(x, slope):
     return _LeakyReLU.apply(x, slope)
+
+
+class _GanLogitTerms(Function):
+    """The six scalar terms of the GAN losses over the discriminator's logits, one launch pair forward and one launch backward."""
+
+    @staticmethod
+    def forward(ctx, real, fake):
+        L = _L()
+        _lib.require_device(real, fake)
+        fake_c = fake.detach().contiguous()
+        real_c = None if real is None else real.detach().contiguous()
+        n_real = 0 if real_c is None else real_c.numel()
+        out = torch.empty(6, dtype=torch.float32, device=fake.device)
+        wp, wn = _ws(L.odvae_gan_logit_terms_workspace_bytes(n_real, fake_c.numel()), fake)
+        _lib.check(L.odvae_gan_logit_terms_f32(_lib.ptr(real_c), n_real, fake_c.data_ptr(), fake_c.numel(), out.data_ptr(), wp, wn,
+                                               _lib.stream_ptr()), "gan_logit_terms")
+        ctx.has_real = real_c is not None
+        ctx.save_for_backward(fake_c, *(() if real_c is None else (real_c,)))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _L()
+        fake, real = ctx.saved_tensors[0], (ctx.saved_tensors[1] if ctx.has_real else None)
+        dout = dout.contiguous()
+        _lib.require_device(dout)
+        dreal = torch.empty_like(real) if ctx.has_real and ctx.needs_input_grad[0] else None
+        dfake = torch.empty_like(fake) if ctx.needs_input_grad[1] else None
+        if dreal is None and dfake is None:
+            return None, None
+        _lib.check(L.odvae_gan_logit_terms_bwd_f32(_lib.ptr(real), 0 if real is None else real.numel(), fake.data_ptr(), fake.numel(),
+                                                   dout.data_ptr(), _lib.ptr(dreal), _lib.ptr(dfake), _lib.stream_ptr()),
+                   "gan_logit_terms_bwd")
+        return dreal, dfake
+
+
+def gan_logit_terms(real, fake):
+    """[mean real, mean fake, mean relu(1 - real), mean relu(1 + fake), mean softplus(-real), mean softplus(fake)] as six f32 on the device;
+    `real` may be None (generator phase: its three terms are 0).  hinge_d_loss = 0.5 (t[2] + t[3]), vanilla_d_loss = 0.5 (t[4] + t[5]),
+    g_loss = -t[1].  The logits may have any shape and different element counts."""
+    return _GanLogitTerms.apply(real, fake)
 
 
 # ---- the PatchGAN discriminator on bf16 activations (opt-in: NLayerDiscriminator.set_precision("bf16"); conv_bf16.hip modes 5 / 6 / 7,

@@ -57,15 +57,17 @@ def main(argv=None):
     config = Config.merge(*[Config.load(p) for p in opt.base], Config.from_dotlist(unknown))
     lightning = config.pop("lightning", Config.create())
     trainer_cfg = lightning.get("trainer", Config.create())
-    lp = config.model.params.lossconfig.params
-    if "dataset_stats" not in lp and not os.path.exists(lp.get("dataset_stats_path", "dataset_stats/combined/all.pkl")):
-        lp["dataset_stats"] = synthetic.dataset_stats_standin()   # the reference does not ship its stats pickle
-    latent = opt.height // 2 ** (len(config.model.params.ddconfig.ch_mult) - 1)
-    if latent != config.model.params.pose_decoder_config.params.n:
-        for key in ("pose_decoder_config", "pose_encoder_config"):
-            config.model.params[key].params["n"] = latent
-            config.model.params[key].params["m"] = latent
-        config.model.params["feat_dims"] = [config.model.params.embed_dim, latent, latent]
+    params = config.model.params
+    if "pose_decoder_config" in params:      # the pose model's keys; a plain AutoencoderKL / Autoencoder yaml has none of them
+        lp = params.lossconfig.params
+        if "dataset_stats" not in lp and not os.path.exists(lp.get("dataset_stats_path", "dataset_stats/combined/all.pkl")):
+            lp["dataset_stats"] = synthetic.dataset_stats_standin()   # the reference does not ship its stats pickle
+        latent = opt.height // 2 ** (len(params.ddconfig.ch_mult) - 1)
+        if latent != params.pose_decoder_config.params.n:
+            for key in ("pose_decoder_config", "pose_encoder_config"):
+                params[key].params["n"] = latent
+                params[key].params["m"] = latent
+            params["feat_dims"] = [params.embed_dim, latent, latent]
     model = instantiate_from_config(config.model)
     configure_learning_rate(config, model, trainer_cfg, scale_lr=opt.scale_lr, ngpu=1)
     model = model.to(opt.device).train()
@@ -79,7 +81,10 @@ def main(argv=None):
     trainer = Trainer(model, callbacks=callbacks, logger=logger, **trainer_kwargs(trainer_cfg))
     bs = config.data.params.batch_size
     for step in range(opt.steps):
-        batch = synthetic.make_batch(bs, opt.height, seed=opt.seed + step)
+        if hasattr(model, "image_key"):      # AutoencoderKL / Autoencoder: images alone
+            batch = synthetic.make_image_batch(bs, opt.height, seed=opt.seed + step, image_key=model.image_key)
+        else:
+            batch = synthetic.make_batch(bs, opt.height, seed=opt.seed + step)
         losses = trainer.training_batch(batch, step, last_in_epoch=step == opt.steps - 1)   # (closes an accumulation window)
         print("batch %d  global_step %d  aeloss %.4f  discloss %.4f  lr %.2e" %
               (step, model.global_step, losses[0].item(), losses[1].item(), model.learning_rate), flush=True)

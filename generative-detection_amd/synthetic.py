@@ -34,6 +34,13 @@ def make_batch(batch_size, height, width=None, seed=23, class_id=0):
     }
 
 
+def make_image_batch(batch_size, height, width=None, seed=23, image_key="image"):
+    """The batch dict AutoencoderKL.training_step reads: `image` ~ U[-1,1) as [N, H, W, 3] (get_input permutes it to NCHW)."""
+    width = width or height
+    g = torch.Generator().manual_seed(seed)
+    return {image_key: torch.rand(batch_size, height, width, 3, generator=g) * 2 - 1}
+
+
 def make_noise(batch_size, latent_hw, z_channels=16, dropout_p=0.7, seed=99):
     """The four host RNG draws of one forward pass, made explicit so HIP path and oracle can share them."""
     g = torch.Generator().manual_seed(seed)

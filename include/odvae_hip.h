@@ -410,6 +410,19 @@ int odvae_actnorm_lrelu_bwd_f32(const float* x, const float* dy, int64_t rows, i
 /* torch.nn.LeakyReLU(slope); the backward with slope 0 is the ReLU backward */
 int odvae_leaky_relu_f32(const float* x, float* y, float slope, int64_t n, void* stream);
 int odvae_leaky_relu_bwd_f32(const float* x, const float* dy, float* dx, float slope, int64_t n, void* stream);
+/* The scalar terms of the GAN losses over the discriminator's logits ([UPSTREAM] ldm LPIPSWithDiscriminator.forward, taming hinge_d_loss /
+ * vanilla_d_loss), one launch pair each way:
+ *   out6 = [mean real, mean fake, mean relu(1 - real), mean relu(1 + fake), mean softplus(-real), mean softplus(fake)]  (device, 6 floats)
+ * real may be NULL with n_real == 0 (generator phase: its three terms are written as 0); n_real != n_fake is allowed.  softplus(x) =
+ * max(x, 0) + log1p(exp(-|x|)); a NaN logit makes its three terms NaN.  Each term is summed in f64 in a fixed order (no atomics: the same
+ * bits on every run), divided by n in f64 and rounded to f32 once.  Workspace: odvae_gan_logit_terms_workspace_bytes, 8-byte aligned.
+ * bwd: dout6 is the upstream gradient ON THE DEVICE;  dreal_i = (d0 - d2 [real_i < 1] - d4 sigmoid(-real_i)) / n_real,
+ *      dfake_i = (d1 + d3 [fake_i > -1] + d5 sigmoid(fake_i)) / n_fake  (strict inequalities: relu'(0) = 0); dreal or dfake may be NULL. */
+size_t odvae_gan_logit_terms_workspace_bytes(int64_t n_real, int64_t n_fake);
+int odvae_gan_logit_terms_f32(const float* real, int64_t n_real, const float* fake, int64_t n_fake, float* out6,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int odvae_gan_logit_terms_bwd_f32(const float* real, int64_t n_real, const float* fake, int64_t n_fake, const float* dout6,
+                                  float* dreal, float* dfake, void* stream);
 
 /* ---- lpips_f32.hip: LPIPS-style perceptual distance ([UPSTREAM] taming lpips.py; contperceptual.py:143) ------------- */
 /* ScalingLayer (x - shift[c]) / scale[c]; backward=1 computes x / scale[c] */
