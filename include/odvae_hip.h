@@ -171,7 +171,10 @@ int odvae_conv3x3_wgrad_wino_f32(const float* x, const float* dy, int N, int H, 
 int odvae_conv3x3_wgrad_wino_select(int form);
 
 /* ---- groupnorm.hip: Normalize = GroupNorm(32, C, eps=1e-6) followed by x*sigmoid(x) -----------------
- * x,y: [N][HW][C]; mean,rstd: [N][G]; swish: 0 identity, 1 x*sigmoid(x). */
+ * x,y: [N][HW][C]; mean,rstd: [N][G]; swish: 0 identity, 1 x*sigmoid(x).
+ * Shapes every f32 entry point of this section takes (ODVAE_ERR_ARG otherwise, nothing written): C % 4 == 0, C <= 1024, G <= 256,
+ * G divides C, N <= 65535 (and HW * C / 4 < 2^31); the dropout forms also need C % 8 == 0.  x, y, dy, dx, dx_add, gamma and beta
+ * 16-byte aligned.  tests/test_groupnorm_edges_gpu.py holds both ends of each limit. */
 size_t odvae_groupnorm_workspace_bytes(int N, int HW, int C, int G);
 int odvae_groupnorm_fwd_f32(const float* x, int N, int HW, int C, int G, const float* gamma, const float* beta,
                             float eps, int swish, float* y, float* mean, float* rstd,
@@ -565,7 +568,10 @@ int odvae_linattn_ctx_f32(const float* k, const float* v, int ld, int64_t stride
  * stride_o (the k and v thirds of a packed dqkv).  k, v, mx, rinv, dctx 16-byte aligned, ld and stride multiples of 4. */
 int odvae_linattn_dkv_f32(const float* k, const float* v, int ld, int64_t stride, const float* mx, const float* rinv, const float* dctx,
                           const float* g, int N, int T, int C, float* dk, float* dv, int ldo, int64_t stride_o, void* stream);
-/* ---- bf16_ops.hip: GroupNorm(32, eps 1e-6) + swish with bf16 activations / f32 statistics, dtype hand-offs ---------------------- */
+/* ---- bf16_ops.hip: GroupNorm(32, eps 1e-6) + swish with bf16 activations / f32 statistics, dtype hand-offs ----------------------
+ * Shapes every bf16 GroupNorm entry point takes (ODVAE_ERR_ARG otherwise, nothing written): C % 8 == 0, 256 % (C / 8) == 0 (a thread
+ * keeps one channel octet: C = 8, 16, 32, ..., 2048 -- no C = 96), C <= 2048, G <= 256, G divides C, N <= 65535 (and HW * C / 8 < 2^31).
+ * x, y, dy, dx and dx_add 16-byte aligned. */
 size_t odvae_groupnorm_bf16_workspace_bytes(int N, int HW, int C, int G);
 int odvae_groupnorm_fwd_bf16(const void* x, int N, int HW, int C, int G, const float* gamma, const float* beta, float eps, int swish,
                              void* y, float* mean, float* rstd, void* workspace, size_t workspace_bytes, void* stream);
