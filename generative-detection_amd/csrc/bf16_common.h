@@ -37,6 +37,36 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float first, float second) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{first, second}, bf16x2));
 }
 
+// V consecutive bf16 of one row <-> f32, as one 2 / 4 / 8 / 16-byte access (p aligned to it for V > 1); the store rounds to nearest even once
+template <int V>
+__device__ __forceinline__ void load_run(const bf16_t* p, float (&v)[V]) {
+  if constexpr (V == 1) { v[0] = bf16_to_f32(*p); }
+  else if constexpr (V == 2) { const unsigned w = *reinterpret_cast<const unsigned*>(p); v[0] = bf16_lo(w); v[1] = bf16_hi(w); }
+  else if constexpr (V == 4) {
+    const u32x2 w = *reinterpret_cast<const u32x2*>(p);
+    v[0] = bf16_lo(w.x); v[1] = bf16_hi(w.x); v[2] = bf16_lo(w.y); v[3] = bf16_hi(w.y);
+  } else {
+    const u32x4 w = *reinterpret_cast<const u32x4*>(p);
+    v[0] = bf16_lo(w.x); v[1] = bf16_hi(w.x); v[2] = bf16_lo(w.y); v[3] = bf16_hi(w.y);
+    v[4] = bf16_lo(w.z); v[5] = bf16_hi(w.z); v[6] = bf16_lo(w.w); v[7] = bf16_hi(w.w);
+  }
+}
+template <int V>
+__device__ __forceinline__ void store_run_rne(bf16_t* p, const float (&v)[V]) {
+  if constexpr (V == 1) { *p = f32_to_bf16(v[0]); }
+  else if constexpr (V == 2) { *reinterpret_cast<unsigned*>(p) = cvt_pk_bf16(v[0], v[1]); }
+  else if constexpr (V == 4) { u32x2 w; w.x = cvt_pk_bf16(v[0], v[1]); w.y = cvt_pk_bf16(v[2], v[3]); *reinterpret_cast<u32x2*>(p) = w; }
+  else {
+    u32x4 w;
+    w.x = cvt_pk_bf16(v[0], v[1]); w.y = cvt_pk_bf16(v[2], v[3]); w.z = cvt_pk_bf16(v[4], v[5]); w.w = cvt_pk_bf16(v[6], v[7]);
+    *reinterpret_cast<u32x4*>(p) = w;
+  }
+}
+// whether a pass over n elements of [.][C] rows can take runs of 8: none wraps a row, every access is 16-byte aligned
+static inline bool vec8(int64_t n, int C, const void* a, const void* b, const void* c) {
+  return n % 8 == 0 && C % 8 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
 // The exact three-way split of f32 into bf16 (x = hi + mid + lo, round to nearest even, both differences exact in f32) that
 // gemm_f32_split.hip and the split form of conv3x3_wgrad_wino_f32.hip feed to the bf16 MFMA:
 // x[0..7] (consecutive k of one row) -> the 16 bytes of the planes hi (0), mid (1), lo (2)

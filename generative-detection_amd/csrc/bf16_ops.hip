@@ -346,6 +346,19 @@ __global__ void sumpool2x2_bf16_kernel(const bf16_t* __restrict__ du, bf16_t* __
     *reinterpret_cast<u32x4*>(dx + 8 * i) = pack8(a);
   }
 }
+// dx = dy * (y > 0 ? 1 : slope) given the POST-activation y (slope > 0: y has the sign of the pre-activation); V = 8 (vec8) or 1 per thread
+template <int V>
+__global__ __launch_bounds__(256) void lrelu_bwd_bf16_kernel(const bf16_t* __restrict__ y, const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx,
+                                                             float slope, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i * V < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float yv[V], gv[V], ov[V];
+    load_run<V>(y + i * V, yv);
+    load_run<V>(dy + i * V, gv);
+#pragma unroll
+    for (int j = 0; j < V; ++j) ov[j] = gv[j] * (yv[j] > 0.f ? 1.f : slope);
+    store_run_rne<V>(dx + i * V, ov);
+  }
+}
 // ---- conv-less resamplers on bf16 activations: f32 arithmetic, one rounding on the way out; the statistics are those of the rounded values ----
 struct RsBF16 {
   typedef bf16_t elem_t;
@@ -517,6 +530,18 @@ int odvae_cast_f32_from_bf16(const void* x, int64_t n, float* y, void* stream) {
   hipLaunchKernelGGL(cast_f32_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n / 8, 256), 8192)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(x), n / 8, y);
   ODVAE_LAUNCH_CHECK("cast_f32_from_bf16");
+  return ODVAE_OK;
+}
+
+// dx = dy * (y > 0 ? 1 : slope), all bf16, y the LeakyReLU's OUTPUT (the backward of the conv epilogue of odvae_conv4x4_bf16)
+int odvae_leaky_relu_bwd_bf16(const void* y, const void* dy, void* dx, float slope, int64_t n, void* stream) {
+  ODVAE_CHECK_ARG(y && dy && dx && n > 0 && slope > 0.f, "leaky_relu_bwd_bf16: bad arguments");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (vec8(n, 8, y, dy, dx))
+    hipLaunchKernelGGL((lrelu_bwd_bf16_kernel<8>), dim3(grid_1d(n / 8)), dim3(256), 0, st, static_cast<const bf16_t*>(y), static_cast<const bf16_t*>(dy), static_cast<bf16_t*>(dx), slope, n);
+  else
+    hipLaunchKernelGGL((lrelu_bwd_bf16_kernel<1>), dim3(grid_1d(n)), dim3(256), 0, st, static_cast<const bf16_t*>(y), static_cast<const bf16_t*>(dy), static_cast<bf16_t*>(dx), slope, n);
+  ODVAE_LAUNCH_CHECK("leaky_relu_bwd_bf16");
   return ODVAE_OK;
 }
 

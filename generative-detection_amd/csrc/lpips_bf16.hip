@@ -122,32 +122,7 @@ __global__ __launch_bounds__(256) void maxpool2x2_bwd_bf16_kernel(const bf16_t* 
   }
 }
 
-// CPL consecutive channels of one pixel per lane (C = 64 * CPL): one 2 / 4 / 8 / 16-byte access
-template <int CPL>
-__device__ __forceinline__ void load_run(const bf16_t* p, float (&v)[CPL]) {
-  if constexpr (CPL == 1) { v[0] = bf16_to_f32(*p); }
-  else if constexpr (CPL == 2) { const unsigned w = *reinterpret_cast<const unsigned*>(p); v[0] = bf16_lo(w); v[1] = bf16_hi(w); }
-  else if constexpr (CPL == 4) {
-    const u32x2 w = *reinterpret_cast<const u32x2*>(p);
-    v[0] = bf16_lo(w.x); v[1] = bf16_hi(w.x); v[2] = bf16_lo(w.y); v[3] = bf16_hi(w.y);
-  } else {
-    const u32x4 w = *reinterpret_cast<const u32x4*>(p);
-    v[0] = bf16_lo(w.x); v[1] = bf16_hi(w.x); v[2] = bf16_lo(w.y); v[3] = bf16_hi(w.y);
-    v[4] = bf16_lo(w.z); v[5] = bf16_hi(w.z); v[6] = bf16_lo(w.w); v[7] = bf16_hi(w.w);
-  }
-}
-template <int CPL>
-__device__ __forceinline__ void store_run_rne(bf16_t* p, const float (&v)[CPL]) {
-  if constexpr (CPL == 1) { *p = f32_to_bf16(v[0]); }
-  else if constexpr (CPL == 2) { *reinterpret_cast<unsigned*>(p) = cvt_pk_bf16(v[0], v[1]); }
-  else if constexpr (CPL == 4) { u32x2 w; w.x = cvt_pk_bf16(v[0], v[1]); w.y = cvt_pk_bf16(v[2], v[3]); *reinterpret_cast<u32x2*>(p) = w; }
-  else {
-    u32x4 w;
-    w.x = cvt_pk_bf16(v[0], v[1]); w.y = cvt_pk_bf16(v[2], v[3]); w.z = cvt_pk_bf16(v[4], v[5]); w.w = cvt_pk_bf16(v[6], v[7]);
-    *reinterpret_cast<u32x4*>(p) = w;
-  }
-}
-
+// A lane keeps CPL consecutive channels of one pixel (C = 64 * CPL), one load_run / store_run_rne (bf16_common.h) each.
 // One wavefront per pixel.  d(pixel) = sum_c w[c] * (f0/n0 - f1/n1)^2, n = sqrt(sum f^2) + 1e-10, in f32 as lpips_distance_kernel.
 // part[n][blk] = sum of d over the block's pixels
 template <int CPL>

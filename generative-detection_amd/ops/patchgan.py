@@ -1,5 +1,5 @@
-"""PatchGAN discriminator pieces: the 4x4 conv, BatchNorm+LeakyReLU (f32: gan_f32.hip; bf16: conv_bf16.hip, gan_bf16.hip),
-ActNorm, LeakyReLU, the scalar terms of the GAN losses over the logits (gan_f32.hip)."""
+"""PatchGAN discriminator pieces: the 4x4 conv (f32: gan_f32.hip; bf16: conv_bf16.hip), BatchNorm+LeakyReLU and ActNorm (gan_norm.hip),
+LeakyReLU, the scalar terms of the GAN losses over the logits (gan_f32.hip)."""
 import weakref
 
 import torch
@@ -14,7 +14,7 @@ from .conv_bf16 import _pad8, cast_pad_bf16
 
 
 # ------------------------------------------------------------------------------------------------------
-# PatchGAN discriminator pieces (gan_f32.hip)
+# PatchGAN discriminator pieces (gan_f32.hip, gan_norm.hip)
 # ------------------------------------------------------------------------------------------------------
 def _conv4x4_out(h, stride):
     return (h + 2 - 4) // stride + 1
@@ -82,6 +82,14 @@ def _conv4x4_i_raw(stride, dgrad, x, pack, cout, bias, ho, wo):
     return y
 
 
+def _check_pack_current(ctx, op):
+    """The data-gradient pack a 4x4 conv's forward cached (ctx.dpack) is keyed by its weight's tag: refuse a backward after the weight was written"""
+    wnow = ctx.wref()
+    if wnow is None or _ops.PACK_CACHE.weight_tag(wnow) != ctx.pack_tag:
+        raise RuntimeError("%s backward: the weight was updated between this graph's forward and its backward; the "
+                           "cached data-gradient pack now holds the new weights" % op)
+
+
 class _Conv4x4I(Function):
     """Conv2d(k=4, pad=1, stride 1|2) as an implicit GEMM in exact f32 (opt-in: ops.DISC_F32_IMPLICIT; conv3x3_f32.hip modes 6 - 9,
     conv4x4_wgrad_f32.hip).  No cols matrix: what is saved is the input, which is the previous layer's output anyway.  Any Cout
@@ -116,10 +124,7 @@ class _Conv4x4I(Function):
         stride = ctx.stride
         dx = dw = db = None
         if ctx.needs_input_grad[0] and not _ops.WEIGHT_GRADIENT_ONLY:
-            wnow = ctx.wref()
-            if wnow is None or _ops.PACK_CACHE.weight_tag(wnow) != ctx.pack_tag:
-                raise RuntimeError("conv4x4 backward: the weight was updated between this graph's forward and its backward; the "
-                                   "cached data-gradient pack now holds the new weights")
+            _check_pack_current(ctx, "conv4x4")
             dx = _conv4x4_i_raw(stride, True, dy, ctx.dpack, cin, None, hi, wi)
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
@@ -159,13 +164,18 @@ def conv4x4(x, weight, bias, stride):
 
 
 class _BatchNormLReLU(Function):
+    """BatchNorm2d + LeakyReLU on f32 or bf16 activations (x, y, dy, dx in x's dtype); statistics, running estimates and parameter
+    gradients f32 either way (gan_norm.hip)"""
+
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, slope, train):
         L = _L()
-        x = _cl(x)
+        bf = x.dtype == BF16
+        dt = BF16 if bf else torch.float32
+        x = _cl(x, dt)
         n, c, h, w = x.shape
         rows = n * h * w
-        y = _new_cl(n, c, h, w, x)
+        y = _new_cl(n, c, h, w, x, dtype=dt)
         if train:
             mean = torch.empty(c, dtype=torch.float32, device=x.device)
             rstd = torch.empty(c, dtype=torch.float32, device=x.device)
@@ -174,11 +184,11 @@ class _BatchNormLReLU(Function):
             rstd = torch.rsqrt(running_var.detach() + eps)
         wp, wn = _ws(L.odvae_batchnorm_workspace_bytes(rows, c), x)
         g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        _lib.check(L.odvae_batchnorm_lrelu_fwd_f32(x.data_ptr(), rows, c, g.data_ptr(), b.data_ptr(), float(eps), float(momentum),
-                                                   float(slope), int(train), mean.data_ptr(), rstd.data_ptr(),
-                                                   _lib.ptr(running_mean) if train else None,
-                                                   _lib.ptr(running_var) if train else None, y.data_ptr(), wp, wn,
-                                                   _lib.stream_ptr()), "batchnorm_lrelu_fwd")
+        _lib.check(getattr(L, "odvae_batchnorm_lrelu_fwd_" + ("bf16" if bf else "f32"))(x.data_ptr(), rows, c, g.data_ptr(), b.data_ptr(), float(eps), float(momentum),
+                                                                   float(slope), int(train), mean.data_ptr(), rstd.data_ptr(),
+                                                                   _lib.ptr(running_mean) if train else None,
+                                                                   _lib.ptr(running_var) if train else None, y.data_ptr(), wp, wn,
+                                                                   _lib.stream_ptr()), "batchnorm_lrelu_fwd" + ("_bf16" if bf else ""))
         ctx.slope, ctx.train = float(slope), int(train)
         ctx.save_for_backward(x, gamma, beta, mean, rstd)
         return y
@@ -187,17 +197,18 @@ class _BatchNormLReLU(Function):
     def backward(ctx, dy):
         L = _L()
         x, gamma, beta, mean, rstd = ctx.saved_tensors
-        dy = _cl(dy)
+        bf = x.dtype == BF16
+        dy = _cl(dy, x.dtype)
         n, c, h, w = x.shape
         rows = n * h * w
-        dx = _new_cl(n, c, h, w, x)
+        dx = _new_cl(n, c, h, w, x, dtype=x.dtype)
         dg = torch.empty(c, dtype=torch.float32, device=x.device)
         db = torch.empty(c, dtype=torch.float32, device=x.device)
         wp, wn = _ws(L.odvae_batchnorm_workspace_bytes(rows, c), x)
-        _lib.check(L.odvae_batchnorm_lrelu_bwd_f32(x.data_ptr(), dy.data_ptr(), rows, c, gamma.detach().contiguous().data_ptr(),
-                                                   beta.detach().contiguous().data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                   ctx.slope, ctx.train, dx.data_ptr(), dg.data_ptr(), db.data_ptr(), wp, wn,
-                                                   _lib.stream_ptr()), "batchnorm_lrelu_bwd")
+        _lib.check(getattr(L, "odvae_batchnorm_lrelu_bwd_" + ("bf16" if bf else "f32"))(x.data_ptr(), dy.data_ptr(), rows, c, gamma.detach().contiguous().data_ptr(),
+                                                                       beta.detach().contiguous().data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                                       ctx.slope, ctx.train, dx.data_ptr(), dg.data_ptr(), db.data_ptr(), wp, wn,
+                                                                       _lib.stream_ptr()), "batchnorm_lrelu_bwd" + ("_bf16" if bf else ""))
         return dx, dg, db, None, None, None, None, None, None
 
 
@@ -296,8 +307,6 @@ def batchnorm_lrelu(x, bn, slope):
     group, world = _sync_group(bn)
     if group is not None:
         return _SyncBatchNormLReLU.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, slope, group, world)
-    if x.dtype == BF16:     # the bf16 discriminator: activations bf16, statistics and parameters f32
-        return _BatchNormLReLUB.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, slope, train)
     return _BatchNormLReLU.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, slope, train)
 
 
@@ -424,7 +433,7 @@ def gan_logit_terms(real, fake):
 
 
 # ---- the PatchGAN discriminator on bf16 activations (opt-in: NLayerDiscriminator.set_precision("bf16"); conv_bf16.hip modes 5 / 6 / 7,
-# conv_wgrad_bf16.hip modes 5 / 6, gan_bf16.hip) ----
+# conv_wgrad_bf16.hip modes 5 / 6; its BatchNorm + LeakyReLU is _BatchNormLReLU above) ----
 def _conv4x4_b_raw(stride, dgrad, x, pack, cout, bias, ho, wo, out_f32, slope=0.0, cin_alg=None):
     """One odvae_conv4x4_bf16 call: x bf16 [N, C, H, W] -> [N, cout, ho, wo] in bf16 or f32"""
     L = _L()
@@ -505,10 +514,7 @@ class _Conv4x4B(Function):
                 dyb = g
         dx = dw = db = None
         if ctx.needs_input_grad[0] and not _ops.WEIGHT_GRADIENT_ONLY:
-            wnow = ctx.wref()
-            if wnow is None or _ops.PACK_CACHE.weight_tag(wnow) != ctx.pack_tag:
-                raise RuntimeError("conv4x4_bf16 backward: the weight was updated between this graph's forward and its backward; the "
-                                   "cached data-gradient pack now holds the new weights")
+            _check_pack_current(ctx, "conv4x4_bf16")
             dx = _conv4x4_b_raw(stride, True, dyb, ctx.dpack, cin, None, hi, wi, ctx.from_f32, cin_alg=cout)
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
         fold_db = want_db and not f32_dy and ctx.needs_input_grad[1]
@@ -544,48 +550,3 @@ def conv4x4_bf16(x, weight, bias, stride, lrelu=None):
     if tuple(weight.shape[2:]) != (4, 4):
         raise ValueError("conv4x4_bf16: weight %s is no 4x4 kernel" % (tuple(weight.shape),))
     return _Conv4x4B.apply(x, weight, bias, int(stride), float(lrelu) if lrelu else 0.0)
-
-
-class _BatchNormLReLUB(Function):
-    """_BatchNormLReLU on bf16 activations: x, y, dy, dx bf16; statistics, running estimates and parameter gradients f32 (gan_bf16.hip)"""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, slope, train):
-        L = _L()
-        x = _cl(x, BF16)
-        n, c, h, w = x.shape
-        rows = n * h * w
-        y = _new_cl(n, c, h, w, x, dtype=BF16)
-        if train:
-            mean = torch.empty(c, dtype=torch.float32, device=x.device)
-            rstd = torch.empty(c, dtype=torch.float32, device=x.device)
-        else:
-            mean = running_mean.detach().clone()
-            rstd = torch.rsqrt(running_var.detach() + eps)
-        wp, wn = _ws(L.odvae_batchnorm_workspace_bytes(rows, c), x)
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        _lib.check(L.odvae_batchnorm_lrelu_fwd_bf16(x.data_ptr(), rows, c, g.data_ptr(), b.data_ptr(), float(eps), float(momentum),
-                                                    float(slope), int(train), mean.data_ptr(), rstd.data_ptr(),
-                                                    _lib.ptr(running_mean) if train else None,
-                                                    _lib.ptr(running_var) if train else None, y.data_ptr(), wp, wn,
-                                                    _lib.stream_ptr()), "batchnorm_lrelu_fwd_bf16")
-        ctx.slope, ctx.train = float(slope), int(train)
-        ctx.save_for_backward(x, gamma, beta, mean, rstd)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        L = _L()
-        x, gamma, beta, mean, rstd = ctx.saved_tensors
-        dy = _cl(dy, BF16)
-        n, c, h, w = x.shape
-        rows = n * h * w
-        dx = _new_cl(n, c, h, w, x, dtype=BF16)
-        dg = torch.empty(c, dtype=torch.float32, device=x.device)
-        db = torch.empty(c, dtype=torch.float32, device=x.device)
-        wp, wn = _ws(L.odvae_batchnorm_workspace_bytes(rows, c), x)
-        _lib.check(L.odvae_batchnorm_lrelu_bwd_bf16(x.data_ptr(), dy.data_ptr(), rows, c, gamma.detach().contiguous().data_ptr(),
-                                                    beta.detach().contiguous().data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                    ctx.slope, ctx.train, dx.data_ptr(), dg.data_ptr(), db.data_ptr(), wp, wn,
-                                                    _lib.stream_ptr()), "batchnorm_lrelu_bwd_bf16")
-        return dx, dg, db, None, None, None, None, None, None

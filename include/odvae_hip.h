@@ -343,7 +343,8 @@ int odvae_mul_mask_f32(const float* x, const float* mask, float* y, int64_t npix
 /* out = z*mask + add, mask/add may be NULL (dropout on z_obj, +noise, +enc_pose: src/models/autoencoder.py:233-253) */
 int odvae_latent_combine_f32(const float* z, const float* mask, const float* add, float* out, int64_t n, void* stream);
 
-/* ---- gan_f32.hip: PatchGAN NLayerDiscriminator ([UPSTREAM] taming discriminator; contperceptual.py:285,355-356) ----
+/* ---- gan_f32.hip, gan_norm.hip: PatchGAN NLayerDiscriminator ([UPSTREAM] taming discriminator; contperceptual.py:285,355-356) ----
+ * gan_f32.hip: the convolution pieces, LeakyReLU, the logit terms; gan_norm.hip: BatchNorm2d / ActNorm + LeakyReLU (f32 here, bf16 below).
  * Conv2d(k=4, pad=1, stride 1|2) = im2col + odvae_gemm_f32 against the weight reordered to [Cout][(kh,kw,ci)];
  * cols is [N*Ho*Wo][16*C]; col2im is its adjoint (data gradient). */
 int odvae_im2col4x4_f32(const float* x, float* cols, int N, int Hi, int Wi, int C, int Ho, int Wo, int stride, void* stream);
@@ -608,7 +609,7 @@ size_t odvae_colsum_bf16_workspace_bytes(int64_t rows, int C);
 /* out f32 [C] = column sums of x bf16 [rows][C] (bias gradients) */
 int odvae_colsum_bf16(const void* x, int64_t rows, int C, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- gan_bf16.hip: BatchNorm2d + LeakyReLU of the PatchGAN on bf16 activations -----------------------------------------------
+/* ---- gan_norm.hip: BatchNorm2d + LeakyReLU of the PatchGAN on bf16 activations, the same kernels instantiated for bf16 elements -----
  * odvae_batchnorm_lrelu_fwd_f32 / _bwd_f32 with x, y, dy, dx bf16 [rows][C]; mean, rstd, running statistics, gamma, beta, dgamma, dbeta
  * f32.  The batch statistics are those of the stored bf16 values, summed about the pivot x[0][c] as in the f32 kernels; each output
  * element is evaluated in f32 and rounded once.  Workspace: odvae_batchnorm_workspace_bytes(rows, C). */
@@ -629,7 +630,7 @@ int odvae_batchnorm_sync_bwd_sums_bf16(const void* x, const void* dy, int64_t ro
 int odvae_batchnorm_sync_bwd_dx_bf16(const void* x, const void* dy, int64_t rows, int C, const float* gamma, const float* beta,
                                      const float* mean, const float* rstd, float slope, const double* sums_all, size_t sums_bytes,
                                      int world, const double* m_total, void* dx, void* workspace, size_t workspace_bytes, void* stream);
-/* dx = dy * (y > 0 ? 1 : slope), all bf16, y the LeakyReLU's OUTPUT (slope > 0): the backward of odvae_conv4x4_bf16's epilogue */
+/* bf16_ops.hip: dx = dy * (y > 0 ? 1 : slope), all bf16, y the LeakyReLU's OUTPUT (slope > 0): the backward of odvae_conv4x4_bf16's epilogue */
 int odvae_leaky_relu_bwd_bf16(const void* y, const void* dy, void* dx, float slope, int64_t n, void* stream);
 
 /* ---- lpips_bf16.hip: the LPIPS-style perceptual distance on bf16 features (opt-in: LPIPSStyle.set_precision("bf16")) -------------

@@ -1,6 +1,6 @@
 """BatchNorm inputs whose channel means lie far from zero: generators, references, host models.
 
-The channel counterpart of `gn_offset_inputs` for the PatchGAN's BatchNorm2d + LeakyReLU(0.2) (csrc/gan_f32.hip).  The PatchGAN
+The channel counterpart of `gn_offset_inputs` for the PatchGAN's BatchNorm2d + LeakyReLU(0.2) (csrc/gan_norm.hip).  The PatchGAN
 convolutions in front of BatchNorm have no bias and read LeakyReLU outputs, so nothing centres their channel means.  `make_input`
 gives x = s (randn + r sign_c) with the sign alternating from one channel to the next; `ref64` / `ref32` are `F.batch_norm` in
 training mode (momentum 0.1, unbiased running variance) followed by `F.leaky_relu(., 0.2)` in float64 and in torch f32 on the host;

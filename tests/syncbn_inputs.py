@@ -11,7 +11,7 @@ r + SEP deviations from zero: the ladder of tests/bn_offset_inputs.py, which the
 The reference everywhere is `bn_offset_inputs.ref64` / `backward_refs` on the CONCATENATED tensor (float64 F.batch_norm in training
 mode), torch f32 on it for the yardstick of `gn_offset_inputs.figure`.
 
-`model` is csrc/gan_f32.hip's synchronised route in float64 on the host: per shard a record {rows, mean, M2}, the records merged
+`model` is csrc/gan_norm.hip's synchronised route in float64 on the host: per shard a record {rows, mean, M2}, the records merged
 pairwise in index order by Chan's update, mean and rstd rounded to f32 as the merge kernel stores them, the running estimates with the
 unbiased variance over the total count, y from the merged statistics, per-shard sums (sum g, sum g xhat) added in index order, dx with
 the total count.  `fault=` plants one of FAULTS, the mistakes a synchronised BatchNorm is prone to; tests/test_syncbn_inputs.py shows

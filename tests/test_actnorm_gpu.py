@@ -1,4 +1,4 @@
-"""ActNorm + LeakyReLU(0.2) on the HIP kernels (csrc/gan_f32.hip: an_*_kernel, odvae_actnorm_*).
+"""ActNorm + LeakyReLU(0.2) on the HIP kernels (csrc/gan_norm.hip: an_*_kernel, odvae_actnorm_*).
 
 * forward and backward of an initialised layer against torch f32 on the host (tests/actnorm_ref.py) at test_batchnorm_lrelu's
   tolerances -- 2e-4 forward, 5e-4 for dx, dloc, dscale, relative to max|ref| -- over the shapes of bn_offset_inputs (they reach every

@@ -1,6 +1,6 @@
 """BatchNorm2d + LeakyReLU(0.2) held to float64 when a channel's mean is far from zero.
 
-`bn_colstats_kernel<0>` (csrc/gan_f32.hip) used to sum x and x^2 in f32 and `bn_finalize_kernel` formed var = E[x^2] - E[x]^2, which
+`bn_colstats_kernel<T, 0, V>` (csrc/gan_norm.hip) used to sum x and x^2 in f32 and `bn_finalize_kernel` formed var = E[x^2] - E[x]^2, which
 loses ~ u r^2 of the variance, r = |mean| / std of a channel.  The sums are now taken about a per-channel pivot (the channel's value in
 row 0), so what is squared is of the size of the spread, not of the mean.
 

@@ -1,5 +1,5 @@
 """The opt-in bf16 PatchGAN discriminator (gan.NLayerDiscriminator.set_precision("bf16")): the 16-tap implicit-GEMM convolutions of
-conv_bf16.hip (modes 5 / 6 / 7) and conv_wgrad_bf16.hip (modes 5 / 6), BatchNorm + LeakyReLU of gan_bf16.hip.
+conv_bf16.hip (modes 5 / 6 / 7) and conv_wgrad_bf16.hip (modes 5 / 6), BatchNorm + LeakyReLU of gan_norm.hip.
 
 Per kernel, bit for bit against float64 on exactly summable operands (tests/conv4x4_bf16_inputs.py, recipe A; recipe L for the fused
 LeakyReLU): forward, data gradient, weight gradient and bias gradient at every shape of M.CASES -- an f32 output equals the reference,
@@ -233,7 +233,9 @@ def inside(got, want, bound, what):
     assert torch.isfinite(got).all() and bool((err <= bound).all()), "%s: err / bound up to %.3f" % (what, worst)
 
 
-BN_SHAPES = [(1, 8), (1, 36), (1, 512), (63, 8), (63, 36), (63, 512), (WRAP_ROWS, 8)]
+# (63, 7): odd C, one element per thread in every pass; (63, 263): odd C past one 256-channel pass; (63, 520): C / 2 = 260 pairs, a second
+# pass 4 pairs wide, 8-element apply
+BN_SHAPES = [(1, 8), (1, 36), (1, 512), (63, 8), (63, 36), (63, 512), (WRAP_ROWS, 8), (63, 7), (63, 263), (63, 520)]
 
 
 @pytest.mark.parametrize("r", [0, 1000])

@@ -180,7 +180,7 @@ def test_buffers_one_byte_short_are_refused_with_the_needed_size(hip_lib, bf):
 
 @pytest.mark.parametrize("r", [0, 1000])
 @DTYPE
-@pytest.mark.parametrize("rows,c", [(63, 36), (63, 512), (401, 32)], ids=lambda v: str(v))
+@pytest.mark.parametrize("rows,c", [(63, 36), (63, 512), (401, 32), (63, 263), (63, 520)], ids=lambda v: str(v))      # the last two: a partial second 256-column pass
 def test_one_shard_agrees_with_the_monolithic_entry_point(hip_lib, rows, c, bf, r):
     """world = 1: the same statistics, outputs and gradients as odvae_batchnorm_lrelu_fwd / _bwd, both inside the rule against float64
     and no further from each other than the rule's bound; dx, dgamma, dbeta given the SAME mean and rstd bit for bit."""

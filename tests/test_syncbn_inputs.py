@@ -1,6 +1,6 @@
 """The acceptance rule on synchronised BatchNorm: it admits the host model of the kernels and rejects the usual mistakes; plumbing.
 
-Host only.  `syncbn_inputs.model` is the synchronised route of csrc/gan_f32.hip in float64 (record -> Chan merge in index order -> dx
+Host only.  `syncbn_inputs.model` is the synchronised route of csrc/gan_norm.hip in float64 (record -> Chan merge in index order -> dx
 with the total count); the reference is float64 BatchNorm on the concatenated shards, and the rule (`gn_offset_inputs.figure`) takes
 eight times torch f32's own error against it or the project's floors.  On the ladder r in {0, 64, 1000}, with consecutive shards on
 opposite sides of zero, every figure of the model lies inside the rule, and each of `syncbn_inputs.FAULTS` puts the figure it spoils

@@ -1,4 +1,4 @@
-"""ActNorm + LeakyReLU (ops.actnorm_lrelu, the an_* kernels of gan_f32.hip) beside training-mode BatchNorm + LeakyReLU (ops.batchnorm_lrelu)
+"""ActNorm + LeakyReLU (ops.actnorm_lrelu, the an_* kernels of gan_norm.hip) beside training-mode BatchNorm + LeakyReLU (ops.batchnorm_lrelu)
 at the PatchGAN's three normalised layers for 256 x 256 inputs, B = 32, and one generator-plus-discriminator batch of BASELINE configs[3]
 (PatchGAN + LPIPS-style loss, both optimizers) with `use_actnorm` on and off -- all in one process.
 Bytes alone say ActNorm moves 2 tensor passes forward and 3 backward against BatchNorm's 3 and 5, so at every shape its time should not
