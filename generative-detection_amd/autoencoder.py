@@ -5,6 +5,7 @@ ldm/models/autoencoder.py AutoencoderKL it derives from (encode / decode / get_i
 init_from_ckpt / configure_optimizers).  Constructor signature, attribute names, state_dict keys, batch-dict keys,
 global_step thresholds and logged names are the reference's; the arithmetic is in generative-detection_amd/ops/.
 """
+import contextlib
 import logging
 
 import torch
@@ -14,6 +15,7 @@ from . import lib as _lib
 from . import ops
 from .config import instantiate_from_config
 from .distributions import DiagonalGaussianDistribution
+from .ema import LitEma
 from .lightning import LightningModule
 from .modules import Conv1x1, Decoder, Encoder
 from .optim import make_adam
@@ -36,8 +38,9 @@ class AutoencoderKL(LightningModule):
     """[UPSTREAM] ldm.models.autoencoder.AutoencoderKL (the plain KL autoencoder BASELINE.json names)."""
 
     def __init__(self, ddconfig, lossconfig, embed_dim, ckpt_path=None, ignore_keys=[], image_key="image",
-                 colorize_nlabels=None, monitor=None):
+                 colorize_nlabels=None, monitor=None, ema_decay=None, learn_logvar=False):
         super().__init__()
+        self.learn_logvar = learn_logvar
         self.image_key = image_key
         self.encoder = Encoder(**ddconfig)
         self.decoder = Decoder(**ddconfig)
@@ -55,10 +58,50 @@ class AutoencoderKL(LightningModule):
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
         # test hook: {"posterior_eps", "samples_eps"} tensors replace the host RNG draws of forward and log_images
         self.injected_noise = None
+        self._init_ema(ema_decay)
 
     def _noise(self, key):
         noise = getattr(self, "injected_noise", None)
         return None if noise is None else noise.get(key)
+
+    # ---- exponential moving average of the weights ([UPSTREAM] the stable-diffusion revision of this class; ema.LitEma) -------------
+    def _init_ema(self, ema_decay):
+        """Last in __init__ (after init_from_ckpt): the shadows start as clones of the weights the model starts with"""
+        self.use_ema = ema_decay is not None
+        self._in_ema_scope = False
+        if self.use_ema:
+            assert 0. < ema_decay < 1.
+            self.model_ema = LitEma(self, decay=ema_decay)
+            print(f"Keeping EMAs of {len(list(self.model_ema.buffers()))}.")
+
+    @contextlib.contextmanager
+    def ema_scope(self, context=None):
+        """Inside, the parameters hold the averaged weights; on the way out -- by an exception too -- they hold exactly what they held
+        before.  One exchange kernel per parameter arena each way (upstream: store / copy_to / restore, three copies of every parameter).
+        The exchange writes parameters behind torch's version counters, so the weight packs are marked stale both times; a graph built
+        outside the scope cannot be back-propagated inside it (and the reverse)."""
+        if self.use_ema:
+            if self._in_ema_scope:
+                raise RuntimeError("ema_scope: already inside one (the parameters hold the averaged weights; a second exchange would bring the trained ones back)")
+            self.model_ema.swap(self)
+            ops.PACK_CACHE.bump()
+            self._in_ema_scope = True
+            if context is not None:
+                print(f"{context}: Switched to EMA weights")
+        try:
+            yield None
+        finally:
+            if self.use_ema:
+                self.model_ema.swap(self)
+                ops.PACK_CACHE.bump()
+                self._in_ema_scope = False
+                if context is not None:
+                    print(f"{context}: Restored training weights")
+
+    def on_train_batch_end(self, *args, **kwargs):
+        """One update of the average per training BATCH (PL calls this hook per batch, not per optimizer step)"""
+        if self.use_ema:
+            self.model_ema(self)
 
     def set_precision(self, precision, perceptual_precision=None, discriminator_precision=None):
         """The trainer's `precision` (configs/autoencoder/pose/autoencoder_kl_16x16x16.yaml:139; PL-1.9 accepts 32, "32", 16, "bf16"):
@@ -136,22 +179,30 @@ class AutoencoderKL(LightningModule):
         return discloss
 
     def validation_step(self, batch, batch_idx):
+        log_dict = self._validation_step(batch, batch_idx)
+        if self.use_ema:      # the same batch again under the averaged weights: val_ema/rec_loss and the rest
+            with self.ema_scope():
+                self._validation_step(batch, batch_idx, postfix="_ema")
+        return log_dict
+
+    def _validation_step(self, batch, batch_idx, postfix=""):
         inputs = self.get_input(batch, self.image_key)
         reconstructions, posterior = self(inputs)
         _, log_dict_ae = self.loss(inputs, reconstructions, posterior, 0, self.global_step,
-                                   last_layer=self.get_last_layer(), split="val")
+                                   last_layer=self.get_last_layer(), split="val" + postfix)
         _, log_dict_disc = self.loss(inputs, reconstructions, posterior, 1, self.global_step,
-                                     last_layer=self.get_last_layer(), split="val")
-        self.log("val/rec_loss", log_dict_ae["val/rec_loss"])
+                                     last_layer=self.get_last_layer(), split="val" + postfix)
+        self.log(f"val{postfix}/rec_loss", log_dict_ae[f"val{postfix}/rec_loss"])
         self.log_dict(log_dict_ae)
         self.log_dict(log_dict_disc)
         return self.log_dict
 
     @torch.no_grad()
-    def log_images(self, batch, only_inputs=False, **kwargs):
+    def log_images(self, batch, only_inputs=False, log_ema=False, **kwargs):
         log = dict()
         x = self.get_input(batch, self.image_key)
         if not only_inputs:
+            x_in = x
             xrec, posterior = self(x)
             if x.shape[1] > 3:      # more than three channels (label maps): both sides go through the fixed `colorize` projection
                 assert xrec.shape[1] == x.shape[1], "reconstruction has %d channels, input %d" % (xrec.shape[1], x.shape[1])
@@ -161,14 +212,28 @@ class AutoencoderKL(LightningModule):
                 eps = torch.randn(tuple(posterior.mean.shape))      # drawn on the host, as DiagonalGaussianDistribution.sample does
             log["samples"] = self.decode(_lib.upload(eps.float(), self.device))
             log["reconstructions"] = xrec
+            if log_ema or self.use_ema:
+                with self.ema_scope():
+                    xrec_ema, posterior_ema = self(x_in)
+                    if x_in.shape[1] > 3:
+                        assert xrec_ema.shape[1] == x_in.shape[1]
+                        xrec_ema = self.to_rgb(xrec_ema)
+                    eps = self._noise("samples_eps")
+                    if eps is None:
+                        eps = torch.randn(tuple(posterior_ema.mean.shape))      # the shape of the EMA pass's posterior
+                    log["samples_ema"] = self.decode(_lib.upload(eps.float(), self.device))
+                    log["reconstructions_ema"] = xrec_ema
         log["inputs"] = x
         return log
 
     def configure_optimizers(self):
         lr = self.learning_rate
-        opt_ae = make_adam(list(self.encoder.parameters()) + list(self.decoder.parameters())
-                           + list(self.quant_conv.parameters()) + list(self.post_quant_conv.parameters()),
-                           lr=lr, betas=(0.5, 0.9))
+        ae_params = (list(self.encoder.parameters()) + list(self.decoder.parameters())
+                     + list(self.quant_conv.parameters()) + list(self.post_quant_conv.parameters()))
+        if self.learn_logvar:
+            print(f"{self.__class__.__name__}: Learning logvar")
+            ae_params.append(self.loss.logvar)
+        opt_ae = make_adam(ae_params, lr=lr, betas=(0.5, 0.9))
         opt_disc = make_adam(self.loss.discriminator.parameters(), lr=lr, betas=(0.5, 0.9))
         return [opt_ae, opt_disc], []
 
@@ -195,8 +260,11 @@ class PoseAutoencoder(AutoencoderKL):
                  colorize_nlabels=None, monitor=None, activation="relu", feat_dims=[16, 16, 16],
                  pose_decoder_config=None, pose_encoder_config=None, dropout_prob_init=1.0, dropout_prob_final=0.7,
                  dropout_warmup_steps=5000, pose_conditioned_generation_steps=10000, add_noise_to_z_obj=True,
-                 train_on_yaw=True):
+                 train_on_yaw=True, ema_decay=None, learn_logvar=False):
+        """ema_decay, learn_logvar: an extension (the reference's PoseAutoencoder has neither): the two keys of the stable-diffusion
+        revision of AutoencoderKL, off by default -- None / False reproduce the reference."""
         LightningModule.__init__(self)  # the reference skips AutoencoderKL.__init__ as well (:66)
+        self.learn_logvar = learn_logvar
         self.encoder_pretrain_steps = lossconfig["params"]["encoder_pretrain_steps"]
         self.train_on_yaw = train_on_yaw
         self.dropout_prob_final, self.dropout_prob_init = dropout_prob_final, dropout_prob_init
@@ -233,6 +301,7 @@ class PoseAutoencoder(AutoencoderKL):
         self.feat_dims = feat_dims
         # test hook: {"posterior_eps", "dropout_mask", "z_noise", "bbox_eps"} tensors replace the host RNG draws
         self.injected_noise = None
+        self._init_ema(ema_decay)
 
     # ---- pose head (:126-174) ---------------------------------------------------------------------------------
     def _decode_pose_to_distribution(self, z, sample_posterior=True):
@@ -363,18 +432,18 @@ class PoseAutoencoder(AutoencoderKL):
         self.log_dict(log_dict, prog_bar=False, logger=True, on_step=True, on_epoch=False)
         return loss
 
-    def validation_step(self, batch, batch_idx):
+    def _validation_step(self, batch, batch_idx, postfix=""):
         rgb_gt, mask_gt, pose_gt, class_gt, class_gt_label, bbox_gt, fill_factor_gt, mask_2d_bbox = self._unpack(batch)
         dec_obj, dec_pose, posterior_obj, bbox_posterior = self.forward(rgb_gt)
         logs = []
         for optimizer_idx in (0, 1):
             _, log = self.loss(rgb_gt, mask_gt, pose_gt, dec_obj, dec_pose, class_gt, class_gt_label, bbox_gt,
                                fill_factor_gt, posterior_obj, bbox_posterior, optimizer_idx, self.global_step,
-                               mask_2d_bbox, last_layer=self.get_last_layer(), split="val")
+                               mask_2d_bbox, last_layer=self.get_last_layer(), split="val" + postfix)
             logs.append(log)
         log_dict_ae, log_dict_disc = logs
-        self.log("val/rec_loss", log_dict_ae["val/rec_loss"], sync_dist=True)
-        del log_dict_ae["val/rec_loss"]
+        self.log(f"val{postfix}/rec_loss", log_dict_ae[f"val{postfix}/rec_loss"], sync_dist=True)
+        del log_dict_ae[f"val{postfix}/rec_loss"]
         self.log_dict(log_dict_ae)
         self.log_dict(log_dict_disc)
         return self.log_dict
@@ -385,6 +454,8 @@ class PoseAutoencoder(AutoencoderKL):
                      + list(self.quant_conv_obj.parameters()) + list(self.quant_conv_pose.parameters())
                      + list(self.post_quant_conv.parameters()) + list(self.pose_encoder.parameters())
                      + list(self.pose_decoder.parameters()))  # loss.logvar is in no optimizer, as in the reference
+        if self.learn_logvar:
+            ae_params.append(self.loss.logvar)
         opt_ae = make_adam(ae_params, lr=lr, betas=(0.5, 0.9))
         opt_disc = make_adam(self.loss.discriminator.parameters(), lr=lr, betas=(0.5, 0.9))
         return [opt_ae, opt_disc], []
@@ -411,6 +482,9 @@ class PoseAutoencoder(AutoencoderKL):
             xrec_perturbed = self._perturbed_pose_forward(posterior_obj, poserec, batch)
             log["reconstructions_rgb"] = xrec[:, :3, :, :].clone().detach()
             log["perturbed_pose_reconstruction_rgb"] = xrec_perturbed[:, :3, :, :].clone().detach()
+            if kwargs.get("log_ema", False) or self.use_ema:
+                with self.ema_scope():
+                    log["reconstructions_rgb_ema"] = self.forward(x_rgb)[0][:, :3, :, :].clone().detach()
         log["inputs_rgb"] = x_rgb.clone().detach()
         return log
 

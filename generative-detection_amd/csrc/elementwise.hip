@@ -547,6 +547,81 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(const GradAccTable
   }
 }
 
+// ---- exponential moving average of the weights ([UPSTREAM] ldm.modules.ema.LitEma; ema.py) -------------------------------------------------
+// tick: the counter step and the decay schedule on the device, one thread; state = [1 - d, d].  num_updates < 0: the schedule is off.
+__global__ void ema_tick_kernel(const float* __restrict__ decay, int* __restrict__ num_updates, float* __restrict__ state) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const float dec = decay[0];
+  int n = num_updates[0];
+  float d = dec;
+  if (n >= 0) {
+    n += 1;
+    num_updates[0] = n;
+    const float q = __fdiv_rn((float)(1 + n), (float)(10 + n));      // torch: int32 / int32 -> both converted to f32, one rounded division
+    d = q < dec ? q : dec;
+  }
+  state[0] = __fsub_rn(1.f, d);
+  state[1] = d;
+}
+
+// How a pair of f32 arrays is walked with 16-byte accesses: `head` leading floats one by one until both pointers are 16-byte aligned (all n
+// when the two are misaligned differently), n4 float4, then the rest one by one.  Every element belongs to exactly one thread.
+struct PairSpan { int64_t head, n4, tail0, nscalar; };
+static PairSpan pair_span(const void* a, const void* b, int64_t n) {
+  PairSpan s;
+  const uintptr_t ma = (uintptr_t)a & 15, mb = (uintptr_t)b & 15;
+  s.head = ma == mb ? std::min<int64_t>(n, (int64_t)(((16 - ma) & 15) / 4)) : n;
+  s.n4 = (n - s.head) / 4;
+  s.tail0 = s.head + 4 * s.n4;
+  s.nscalar = s.head + (n - s.tail0);
+  return s;
+}
+__device__ __forceinline__ int64_t pair_scalar_index(const PairSpan& sp, int64_t j) { return j < sp.head ? j : sp.tail0 + (j - sp.head); }
+
+// s <- s - omd * (s - p): three separately rounded f32 operations, as torch's sub / mul / sub_.  hipcc contracts by default, and HIP's
+// __fmul_rn / __fsub_rn are header functions built under that default (written with them, the last two came out as one v_fma_f32, with
+// or without the pragma): plain operators under contract(off) are what keeps them apart.
+__device__ __forceinline__ float ema_one(float s, float p, float omd) {
+#pragma clang fp contract(off)
+  const float t = s - p;
+  const float u = omd * t;
+  return s - u;
+}
+
+__global__ __launch_bounds__(256) void ema_update_kernel(const float* __restrict__ p, float* __restrict__ s, const PairSpan sp,
+                                                         const float* __restrict__ state) {
+  const float omd = state[0];
+  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  const float4* p4 = reinterpret_cast<const float4*>(p + sp.head);
+  float4* s4 = reinterpret_cast<float4*>(s + sp.head);
+  for (int64_t i = t0; i < sp.n4; i += stride) {
+    const float4 pv = p4[i], sv = s4[i];
+    s4[i] = make_float4(ema_one(sv.x, pv.x, omd), ema_one(sv.y, pv.y, omd), ema_one(sv.z, pv.z, omd), ema_one(sv.w, pv.w, omd));
+  }
+  for (int64_t j = t0; j < sp.nscalar; j += stride) {
+    const int64_t i = pair_scalar_index(sp, j);
+    s[i] = ema_one(s[i], p[i], omd);
+  }
+}
+
+// a <-> b in one pass (ema_scope: the parameters take the averaged values, the shadows keep the trained ones, and back)
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ a, float* __restrict__ b, const PairSpan sp) {
+  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+  float4* a4 = reinterpret_cast<float4*>(a + sp.head);
+  float4* b4 = reinterpret_cast<float4*>(b + sp.head);
+  for (int64_t i = t0; i < sp.n4; i += stride) {
+    const float4 av = a4[i], bv = b4[i];
+    a4[i] = bv;
+    b4[i] = av;
+  }
+  for (int64_t j = t0; j < sp.nscalar; j += stride) {
+    const int64_t i = pair_scalar_index(sp, j);
+    const float av = a[i], bv = b[i];
+    a[i] = bv;
+    b[i] = av;
+  }
+}
+
 // ---- layout: NHWC -> NCHW copy (reconstructions handed back to NCHW callers) ---------------------------
 __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int C, int HW) {
   const int64_t total = (int64_t)N * C * HW;
@@ -944,6 +1019,42 @@ int odvae_grad_accumulate_f32(float* arena, int64_t arena_numel, const int64_t* 
     hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)std::min<uint64_t>(chunks, 8192)), dim3(256), 0, st, t);
     ODVAE_LAUNCH_CHECK("grad_accumulate");
   }
+  return ODVAE_OK;
+}
+
+// LitEma's counter and decay schedule, on the device: nothing is read back.  state (2 floats) receives [1 - d, d]
+int odvae_ema_tick(const float* decay, int* num_updates, float* state, void* stream) {
+  ODVAE_CHECK_ARG(decay && num_updates && state, "ema_tick: bad arguments");
+  ODVAE_CHECK_ARG((((uintptr_t)decay | (uintptr_t)num_updates | (uintptr_t)state) & 3) == 0, "ema_tick: pointers must be 4-byte aligned");
+  hipLaunchKernelGGL(ema_tick_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), decay, num_updates, state);
+  ODVAE_LAUNCH_CHECK("ema_tick");
+  return ODVAE_OK;
+}
+
+static bool f32_ranges_overlap(const float* a, const float* b, int64_t n) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
+  return x < y + len && y < x + len;
+}
+
+// shadow[i] <- shadow[i] - omd[0] * (shadow[i] - p[i]), i < n: three f32 roundings per element; omd = the state odvae_ema_tick wrote
+int odvae_ema_update_f32(const float* p, float* shadow, int64_t n, const float* omd, void* stream) {
+  ODVAE_CHECK_ARG(p && shadow && omd && n > 0, "ema_update: bad arguments");
+  ODVAE_CHECK_ARG((((uintptr_t)p | (uintptr_t)shadow | (uintptr_t)omd) & 3) == 0, "ema_update: pointers must be 4-byte aligned");
+  ODVAE_CHECK_ARG(!f32_ranges_overlap(p, shadow, n), "ema_update: the parameters and their shadow overlap");
+  const PairSpan sp = pair_span(p, shadow, n);
+  hipLaunchKernelGGL(ema_update_kernel, dim3(grid_1d(std::max(sp.n4, sp.nscalar))), dim3(256), 0, static_cast<hipStream_t>(stream), p, shadow, sp, omd);
+  ODVAE_LAUNCH_CHECK("ema_update");
+  return ODVAE_OK;
+}
+
+// a[i] <-> b[i], i < n, in one pass over two disjoint arrays
+int odvae_ema_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  ODVAE_CHECK_ARG(a && b && n > 0, "ema_swap: bad arguments");
+  ODVAE_CHECK_ARG((((uintptr_t)a | (uintptr_t)b) & 3) == 0, "ema_swap: pointers must be 4-byte aligned");
+  ODVAE_CHECK_ARG(!f32_ranges_overlap(a, b, n), "ema_swap: the two arrays overlap");
+  const PairSpan sp = pair_span(a, b, n);
+  hipLaunchKernelGGL(ema_swap_kernel, dim3(grid_1d(std::max(sp.n4, sp.nscalar))), dim3(256), 0, static_cast<hipStream_t>(stream), a, b, sp);
+  ODVAE_LAUNCH_CHECK("ema_swap");
   return ODVAE_OK;
 }
 

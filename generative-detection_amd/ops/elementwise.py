@@ -227,6 +227,52 @@ def latent_combine(z, mask=None, add=None):
 
 
 # ------------------------------------------------------------------------------------------------------
+# exponential moving average of the weights (ema.LitEma): raw launches on flat f32 storage, no autograd
+# ------------------------------------------------------------------------------------------------------
+def _flat_f32(*tensors):
+    _lib.require_device(*tensors)
+    for t in tensors:
+        if not t.is_contiguous():
+            raise ValueError("ema: needs contiguous storage, got strides %s for shape %s" % (t.stride(), tuple(t.shape)))
+
+
+def ema_tick(decay, num_updates, state):
+    """LitEma's counter step and decay schedule on the device: num_updates (int32, in place) += 1 unless negative, state <- [1 - d, d]."""
+    L = _L()
+    _lib.require_device(decay, state)
+    _lib.require_device(num_updates, dtypes=(torch.int32,))
+    if decay.numel() != 1 or num_updates.numel() != 1 or state.numel() != 2 or not state.is_contiguous():
+        raise ValueError("ema_tick: decay and num_updates are scalars, state holds two floats")
+    tag = KERNEL_EVENTS.begin(secondary=True)
+    _lib.check(L.odvae_ema_tick(decay.data_ptr(), num_updates.data_ptr(), state.data_ptr(), _lib.stream_ptr()), "ema_tick")
+    KERNEL_EVENTS.end("ema_tick", 0.0, tag, 20.0, issued=0.0)
+
+
+def ema_update(param, shadow, state, numel=None):
+    """shadow <- shadow - state[0] * (shadow - param) over `numel` floats (default: all of them) of two flat f32 tensors, in place."""
+    L = _L()
+    _flat_f32(param, shadow, state)
+    n = min(param.numel(), shadow.numel()) if numel is None else int(numel)
+    if n > param.numel() or n > shadow.numel():
+        raise ValueError("ema_update: %d floats asked of tensors holding %d and %d" % (n, param.numel(), shadow.numel()))
+    tag = KERNEL_EVENTS.begin(secondary=True)
+    _lib.check(L.odvae_ema_update_f32(param.data_ptr(), shadow.data_ptr(), n, state.data_ptr(), _lib.stream_ptr()), "ema_update")
+    KERNEL_EVENTS.end("ema_update", 0.0, tag, 12.0 * n, issued=0.0)
+
+
+def ema_swap(a, b, numel=None):
+    """Exchange the contents of two flat f32 tensors in one pass, in place (behind torch's version counters: the caller bumps PACK_CACHE)."""
+    L = _L()
+    _flat_f32(a, b)
+    n = min(a.numel(), b.numel()) if numel is None else int(numel)
+    if n > a.numel() or n > b.numel():
+        raise ValueError("ema_swap: %d floats asked of tensors holding %d and %d" % (n, a.numel(), b.numel()))
+    tag = KERNEL_EVENTS.begin(secondary=True)
+    _lib.check(L.odvae_ema_swap_f32(a.data_ptr(), b.data_ptr(), n, _lib.stream_ptr()), "ema_swap")
+    KERNEL_EVENTS.end("ema_swap", 0.0, tag, 16.0 * n, issued=0.0)
+
+
+# ------------------------------------------------------------------------------------------------------
 # pose head: every loss term in one launch (pose_f32.hip)
 # ------------------------------------------------------------------------------------------------------
 class _PoseLosses(Function):

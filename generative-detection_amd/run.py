@@ -35,6 +35,8 @@ def parse(argv):
     ap.add_argument("--height", type=int, default=256, help="synthetic crop size (the yaml's patch_height)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("-l", "--logdir", default=None, help="if given, the yaml's lightning.callbacks run and ImageLogger writes below it")
+    ap.add_argument("--checkpoint", default=None, help="with model.params.ema_decay: write a Lightning-layout checkpoint (weights, model_ema.*, "
+                    "optimizer states) here after the run; default <logdir>/checkpoints/last.ckpt when --logdir is given")
     return ap.parse_known_args(argv)
 
 
@@ -80,14 +82,23 @@ def main(argv=None):
             callbacks.append(instantiate_from_config(cb_cfg))
     trainer = Trainer(model, callbacks=callbacks, logger=logger, **trainer_kwargs(trainer_cfg))
     bs = config.data.params.batch_size
-    for step in range(opt.steps):
+
+    def make(step):
         if hasattr(model, "image_key"):      # AutoencoderKL / Autoencoder: images alone
-            batch = synthetic.make_image_batch(bs, opt.height, seed=opt.seed + step, image_key=model.image_key)
-        else:
-            batch = synthetic.make_batch(bs, opt.height, seed=opt.seed + step)
+            return synthetic.make_image_batch(bs, opt.height, seed=opt.seed + step, image_key=model.image_key)
+        return synthetic.make_batch(bs, opt.height, seed=opt.seed + step)
+    for step in range(opt.steps):
+        batch = make(step)
         losses = trainer.training_batch(batch, step, last_in_epoch=step == opt.steps - 1)   # (closes an accumulation window)
         print("batch %d  global_step %d  aeloss %.4f  discloss %.4f  lr %.2e" %
               (step, model.global_step, losses[0].item(), losses[1].item(), model.learning_rate), flush=True)
+    if getattr(model, "use_ema", False):     # model.params.ema_decay: one validation batch under the trained and the averaged weights
+        metrics = trainer.validate([make(opt.steps)])
+        print("validation  val/rec_loss %.4f  val_ema/rec_loss %.4f  ema updates %d" %
+              (metrics["val/rec_loss"].item(), metrics["val_ema/rec_loss"].item(), int(model.model_ema.num_updates)), flush=True)
+        ckpt = opt.checkpoint or (os.path.join(opt.logdir, "checkpoints", "last.ckpt") if opt.logdir else None)
+        if ckpt:
+            print("checkpoint  %s (%d model_ema.* keys)" % (trainer.save_checkpoint(ckpt), len(model.model_ema.state_dict())), flush=True)
     return model
 
 

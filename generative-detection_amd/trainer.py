@@ -98,8 +98,12 @@ class Trainer:
         for o in opts:
             if hasattr(o, "materialize"):
                 o.materialize()
+        # model.params.ema_decay: the shadows of the weights take the layout of the parameter arenas (one update launch per arena)
+        ema = getattr(model, "model_ema", None) if getattr(model, "use_ema", False) else None
+        if ema is not None and hasattr(ema, "materialize") and _device_of(model).type == "cuda":
+            ema.materialize(opts, model)
         model.trainer = _TrainerHandle(opts)
-        self.current_epoch = 0            # completed passes over the training loader (PL: trainer.current_epoch)
+        self.current_epoch = 0           # completed passes over the training loader (PL: trainer.current_epoch)
         # device-side health counters as of the last check_device_health(): GroupNorm team-barrier timeouts (fatal) and exact-softmax
         # fallbacks of the folded attention softmax (correct, slower; reported)
         self.device_health = {"gn_barrier_timeouts": 0, "attn_softmax_fallbacks": 0, "gn_recentred": 0}
@@ -115,6 +119,12 @@ class Trainer:
             self.reducers = [GradReducer(o, process_group=process_group, bucket_mb=bucket_mb, prescaled=True, comm_dtype=comm_dtype, f32_accumulate=comm_f32_accumulate)
                              for o in opts]
             self.reducers[0].broadcast_parameters(model)
+            if ema is not None:
+                # rank 0's average everywhere, once, as whole arenas: from here on every rank computes the same bits from the same
+                # parameters, with no communication
+                with torch.no_grad():
+                    for t in ema.shadow_storages(model) + [ema.decay.data, ema.num_updates.data]:
+                        torch.distributed.broadcast(t, src=0, group=process_group)
             # ActNorm layers initialise from data on their first training forward: rank 0's values then go to every rank (parallel.broadcast_actnorm)
             for m in model.modules():
                 if hasattr(m, "dist_group") and hasattr(m, "refresh_initialized"):
@@ -227,6 +237,11 @@ class Trainer:
         self._window_pos = 0 if final else self._window_pos + 1
         for cb in self.callbacks:
             cb.on_train_batch_end(self, model, losses, batch, batch_idx)
+        # PL 1.9: the callbacks' hook first, then the module's own (AutoencoderKL: one update of the weight average per batch, also inside an
+        # accumulation window).  A batch that ended in AnomalyError has left above and makes no update.
+        hook = getattr(model, "on_train_batch_end", None)
+        if hook is not None:
+            hook(losses, batch, batch_idx)
         return losses
 
     def _check_anomaly(self, an, idx, red):

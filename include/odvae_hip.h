@@ -337,6 +337,15 @@ int odvae_adam_step_f32(float* p, const float* g, float* m, float* v, int64_t n,
 int odvae_grad_accumulate_segments_per_launch(void);
 int odvae_grad_accumulate_f32(float* arena, int64_t arena_numel, const int64_t* dst_off, const float* const* src, const int64_t* numel,
                               int count, void* stream);
+/* Exponential moving average of the weights (model.params.ema_decay; [UPSTREAM] ldm.modules.ema.LitEma), all on the device.
+ * odvae_ema_tick: one thread.  num_updates >= 0: num_updates += 1, q = float(1 + num_updates) / float(10 + num_updates) (one correctly
+ * rounded f32 division), d = q < decay ? q : decay; num_updates < 0: d = decay.  state[0] = 1 - d, state[1] = d.  Nothing is read back.
+ * odvae_ema_update_f32: shadow[i] <- shadow[i] - omd[0] * (shadow[i] - p[i]) as three separately rounded f32 operations (no fused
+ * multiply-add); omd = the state the tick wrote.  odvae_ema_swap_f32: a[i] <-> b[i] in one pass.  Both walk any 4-byte aligned pair of
+ * disjoint arrays: 16-byte accesses where the two pointers share their alignment (scalar head and tail), scalar otherwise.  NaN / Inf propagate. */
+int odvae_ema_tick(const float* decay, int* num_updates, float* state, void* stream);
+int odvae_ema_update_f32(const float* p, float* shadow, int64_t n, const float* omd, void* stream);
+int odvae_ema_swap_f32(float* a, float* b, int64_t n, void* stream);
 int odvae_nhwc_to_nchw_f32(const float* x, float* y, int N, int C, int HW, void* stream);
 /* y = x * mask[n][hw] broadcast over channels (inputs*mask_2d_bbox, contperceptual.py:252-255); x,y [npix][C] */
 int odvae_mul_mask_f32(const float* x, const float* mask, float* y, int64_t npix, int C, void* stream);
