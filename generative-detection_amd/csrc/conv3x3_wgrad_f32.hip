@@ -12,7 +12,10 @@
 // the dy tile [px][64 co] in LDS; both are read with lanes = consecutive channels (conflict-free b32),
 // one dy read feeds nine MFMAs.  Blocks write partial slabs; a second kernel sums them in a fixed order
 // (deterministic) and writes OIHW.  db = column sums of dy ride along in the ci-tile-0 blocks.
-#include "common.h"
+// The Upsample (mode 5) and Downsample (mode 1) kernels also exist in a bf16-split form (conv3x3_wgrad_up_split_kernel,
+// conv3x3_wgrad_down_split_kernel below): same plan, slabs and reduction, six bf16 products of exactly split operands per f32 product;
+// odvae_conv3x3_wgrad_select chooses (default: by shape).
+#include "bf16_common.h"
 
 namespace {
 
@@ -500,6 +503,332 @@ __global__ void conv3x3_wgrad_up_reduce_kernel(const float* __restrict__ slab, c
   }
 }
 
+// ---- Upsample conv by output parity class, bf16-split form -------------------------------------------------------
+// conv3x3_wgrad_up_kernel's plan, blocks, wave roles, slabs and reduction; only a tile's products change: every f32 value of the
+// halo and of the dy patch is split exactly into three bf16 (split8's arithmetic), and per tap the six products of
+// gemm_f32_split.hip, in its order (smallest first), go through v_mfma_f32_32x32x16_bf16 with f32 accumulation.  That instruction
+// wants 8 consecutive k in a lane, k being the pixel along a tile row.  Any one-to-one map of k to pixels will do as long as x and dy
+// agree; the map here is k = 8 h + j <-> low-res tile column 2 j + h (h = lane half), the f32 kernel's own pairing of lane halves and
+// pixels.  Two things follow:
+//   dy: the thread that holds B's fragment for (class, row, co, h) is the one that fetches those eight pixels: lane = co, 128
+//       contiguous bytes per lane half.  dy never goes through LDS, and the thread's values, added in the order they were loaded,
+//       are the f32 kernel's bias chain: dbias keeps its bits.
+//   x:  tap column shift s = px + b reads halo columns 2 j + h + s: the even columns E[0..8] or the odd ones O[0..8] of the 18, from
+//       element 0 or 1.  A thread fetches one parity of one halo row of one channel (9 loads, lane = channel: 256 contiguous bytes
+//       per wave instruction), splits each value once and writes the runs [0..7] and [1..8] (the second is the first's packed words
+//       moved on by 16 bits): LDS holds [buffer][plane][run E0 O0 E1 O1][halo row][channel][8 k] bf16 = 48 KB per buffer; lane
+//       (li, h) reads run h + s, 512 contiguous bytes per lane half, so neither side has bank conflicts to arrange around.
+// Two LDS buffers and the next tile's raw values in registers: one barrier per tile.
+constexpr unsigned USP_RUN_B = 4 * 64 * 16;          // one run: 4 halo rows x 64 channels x 8 k
+constexpr unsigned USP_PLANE_B = 4 * USP_RUN_B;      // 16 384
+constexpr unsigned USP_BUF_B = 3 * USP_PLANE_B;      // 49 152
+
+// x0, x1 -> the packed words of the planes hi, mid, lo (x0 in bits 0..15): split8's arithmetic on one pair
+__device__ __forceinline__ void split_pair(float x0, float x1, unsigned (&w)[3]) {
+  w[0] = cvt_pk_bf16(x0, x1);
+  const float r0 = x0 - bf16_lo(w[0]), r1 = x1 - bf16_hi(w[0]);
+  w[1] = cvt_pk_bf16(r0, r1);
+  const float s0 = r0 - bf16_lo(w[1]), s1 = r1 - bf16_hi(w[1]);
+  w[2] = cvt_pk_bf16(s0, s1);
+}
+
+__global__ __launch_bounds__(512, 2) void conv3x3_wgrad_up_split_kernel(WgradParams p) {
+  extern __shared__ __attribute__((aligned(16))) char ssm[];   // 2 * USP_BUF_B
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int cls = wave >> 1, wn = wave & 1, py = cls >> 1, px = cls & 1;
+  const int li = lane & 31, h = lane >> 5;
+  const int split = blockIdx.x;
+  const int ci_tile = blockIdx.y % p.ci_tiles, co_tile = blockIdx.y / p.ci_tiles;
+  const int ci0 = ci_tile * UP_BC, co0 = co_tile * UP_BC;
+  const bool do_bias = p.bslab != nullptr && ci_tile == 0;
+
+  f32x16 acc[2][4];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mt][t][r] = 0.f;
+  float bsum = 0.f;
+
+  // loader roles.  x: halo row xrow, column parity xu, channel ci0 + lane.  dy: this wave's class, rows 0 and 1, channel co0 + wn * 32
+  // + li, low-res columns 2 j + h.  A lane past the channel count, a row or a column outside the image reads as 0 (offset past
+  // num_records; the scalar offset stays inside the image).
+  const int xrow = wave >> 1, xu = wave & 1;
+  const unsigned OOB = 0x7FFFFFF0u;
+  const unsigned cin4 = (unsigned)p.Cin * 4u, cout4 = (unsigned)p.Cout * 4u;
+  const unsigned xch = ci0 + lane < p.Cin ? (unsigned)(ci0 + lane) * 4u : OOB;
+  const int co_l = co0 + wn * 32 + li;
+  const unsigned dch = co_l < p.Cout ? (unsigned)co_l * 4u + (unsigned)h * 2u * cout4 : OOB;
+
+  float xr[9], dr[2][8];
+  auto fetch = [&](int tile) {
+    int t = tile;
+    const int tx = t % p.tiles_x; t /= p.tiles_x;
+    const int ty = t % p.tiles_y; const int n = t / p.tiles_y;
+    const int ly0 = ty * UP_TH, lx0 = tx * TW;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.x + (int64_t)n * p.Hi * p.Wi * p.Cin), 0, p.Hi * p.Wi * p.Cin * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.dy + (int64_t)n * p.Ho * p.Wo * p.Cout), 0, p.Ho * p.Wo * p.Cout * 4, 0x00020000);
+    const int iy = ly0 - 1 + xrow;
+    const bool xrow_ok = iy >= 0 && iy < p.Hi;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) {
+      const int ix = lx0 - 1 + 2 * e + xu;
+      const bool ok = xrow_ok && ix >= 0 && ix < p.Wi;      // wave-uniform
+      const unsigned soff = ok ? (unsigned)(iy * p.Wi + ix) * cin4 : 0u;
+      xr[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, ok ? xch : OOB, soff, 0));
+    }
+    const int wleft = p.Wi - lx0 - h;                        // columns 2 j + h < wleft are inside the image
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int oy = 2 * (ly0 + r) + py;
+      const bool row_ok = oy < p.Ho;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const bool sok = row_ok && lx0 + 2 * j < p.Wi;       // wave-uniform: the h = 0 column is inside
+        const unsigned soff = sok ? (unsigned)(oy * p.Wo + 2 * (lx0 + 2 * j) + px) * cout4 : 0u;
+        dr[r][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, (sok && 2 * j < wleft) ? dch : OOB, soff, 0));
+      }
+    }
+  };
+
+  const unsigned lds0 = lds_addr_of(ssm);
+  const unsigned xw = lds0 + (unsigned)(xu * 4 + xrow) * 1024u + (unsigned)lane * 16u;                 // run xu; run xu + 2 is 2 * USP_RUN_B on
+  const unsigned adrA = lds0 + (unsigned)((h + px) * 4 + py) * 1024u + (unsigned)li * 16u;            // run h + px + b, halo row py + a + r
+  constexpr int HI = 0, MID = 1, LO = 2;
+  constexpr int ORDER[6][2] = {{LO, HI}, {HI, LO}, {MID, MID}, {MID, HI}, {HI, MID}, {HI, HI}};        // (x plane, dy plane), smallest first
+
+  const int t_beg = split * p.tiles_per_split;
+  const int ntl = min(p.ntiles, t_beg + p.tiles_per_split) - t_beg;
+  if (ntl > 0) fetch(t_beg);
+  for (int it = 0; it < ntl; ++it) {
+    const unsigned buf = (unsigned)(it & 1) * USP_BUF_B;
+    // the bias gradient's terms, unsplit, in the f32 kernel's order: pixel 2 s + h of k-step s = 0..15
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) bsum += dr[r][j];
+    u32x4 bfr[2][3];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) split8(dr[r], bfr[r]);
+    {
+      unsigned w[5][3];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) split_pair(xr[2 * i], xr[2 * i + 1], w[i]);
+      split_pair(xr[8], 0.f, w[4]);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        u32x4 v0, v1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          v0[i] = w[i][q];
+          v1[i] = __builtin_amdgcn_alignbit(w[i + 1][q], w[i][q], 16);
+        }
+        lds_st128(xw + buf + q * USP_PLANE_B, v0);
+        lds_st128(xw + buf + q * USP_PLANE_B + 2 * USP_RUN_B, v1);
+      }
+    }
+    if (it + 1 < ntl) fetch(t_beg + it + 1);
+    __syncthreads();      // this tile's x runs are written; the other buffer's readers passed the previous barrier
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      bf16x8 b[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) b[q] = frag_from_u32x4(bfr[r][q]);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        bf16x8 a[2][3];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+          for (int q = 0; q < 3; ++q)
+            a[mt][q] = frag_from_u32x4(lds_ld128(adrA + buf + q * USP_PLANE_B + (t % 2) * USP_RUN_B + (r + t / 2) * 1024u + mt * 512u));
+#pragma unroll
+        for (int o = 0; o < 6; ++o)
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt) acc[mt][t] = mfma_bf16(a[mt][ORDER[o][0]], b[ORDER[o][1]], acc[mt][t]);
+      }
+    }
+  }
+
+  // slab [split][cls * 4 + tap][CinP][CoutP]
+  const int co = co0 + wn * 32 + li;
+  float* sl = p.slab + (int64_t)split * 16 * p.CinP * p.CoutP;
+  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(sl, 0, 16 * p.CinP * p.CoutP * 4, 0x00020000);
+  const int tap_stride = p.CinP * p.CoutP * 4;
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const unsigned rowoff = (unsigned)((ci0 + mt * 32 + acc_row(r, lane)) * p.CoutP + co) * 4u;
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[mt][t][r]), srsrc, rowoff, (cls * 4 + t) * tap_stride, 0);
+    }
+  if (do_bias) {
+    bsum += __shfl_xor(bsum, 32, 64);
+    if (h == 0) p.bslab[((int64_t)split * 4 + cls) * p.CoutP + co] = bsum;
+  }
+}
+
+// ---- Downsample conv (pad (0, 1, 0, 1), stride 2), bf16-split form -------------------------------------------------
+// conv3x3_wgrad_dma_kernel<1, 2>'s plan, blocks (64 ci x 128 co, 2 x 16 output pixels per tile), wave roles, slabs and reduction with
+// the products of conv3x3_wgrad_up_split_kernel, and its k map: k = 8 h + j <-> tile column 2 j + h.  dy stays in the registers of the
+// thread that fetched it (both ci halves fetch the same dy: the second read hits the cache) and gives the f32 kernel's bias chain.
+// Tap column kw of lane half h reads halo columns 2 (2 j + h) + kw = 4 j + m, m = 2 h + kw = 0..4: the 33 halo columns by residue
+// modulo 4, Q0[0..8], Q1, Q2, Q3[0..7]; m = 4 is Q0 from element 1.  With 144 accumulator registers per lane a whole tile's raw and
+// split values do not fit beside them, so the loop steps by tile ROW (one k-step of nine taps): three halo rows per stage, the middle
+// halo row of a tile fetched and split by both of its stages.  A loader unit is one (halo row, residue) of the 64 channels (lane =
+// channel), 12 units over 8 waves; LDS holds [buffer][plane][run m][halo row][channel][8 k] bf16 = 45 KB per buffer, two buffers,
+// one barrier per stage.
+constexpr unsigned DSP_RUN_B = 3 * 64 * 16;          // one run: 3 halo rows x 64 channels x 8 k
+constexpr unsigned DSP_PLANE_B = 5 * DSP_RUN_B;      // 15 360
+constexpr unsigned DSP_BUF_B = 3 * DSP_PLANE_B;      // 46 080
+
+__global__ __launch_bounds__(512, 2) void conv3x3_wgrad_down_split_kernel(WgradParams p) {
+  extern __shared__ __attribute__((aligned(16))) char ssm[];   // 2 * DSP_BUF_B
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  const int li = lane & 31, h = lane >> 5;
+  const int split = blockIdx.x;
+  const int ci_tile = blockIdx.y % p.ci_tiles, co_tile = blockIdx.y / p.ci_tiles;
+  const int ci0 = ci_tile * BCI2, co0 = co_tile * BCO2;
+  const bool do_bias = p.bslab != nullptr && ci_tile == 0 && wm == 0;
+
+  f32x16 acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  float bsum = 0.f;
+
+  const unsigned OOB = 0x7FFFFFF0u;
+  const unsigned cin4 = (unsigned)p.Cin * 4u, cout4 = (unsigned)p.Cout * 4u;
+  const unsigned xch = ci0 + lane < p.Cin ? (unsigned)(ci0 + lane) * 4u : OOB;
+  const int co_l = co0 + wn * 32 + li;
+  const unsigned dch = co_l < p.Cout ? (unsigned)co_l * 4u + (unsigned)h * cout4 : OOB;
+
+  const int t_beg = split * p.tiles_per_split;
+  const int nst = 2 * (min(p.ntiles, t_beg + p.tiles_per_split) - t_beg);      // stages: tile row st & 1 of tile t_beg + st / 2
+
+  float xr[2][9], dr[8];      // x: units wave, wave + 8 (< 12): halo row unit >> 2 of the stage's three, residue unit & 3
+  auto fetch = [&](int st) {
+    int t = t_beg + (st >> 1);
+    const int tx = t % p.tiles_x; t /= p.tiles_x;
+    const int ty = t % p.tiles_y; const int n = t / p.tiles_y;
+    const int oy = ty * 2 + (st & 1), ox0 = tx * TW;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.x + (int64_t)n * p.Hi * p.Wi * p.Cin), 0, p.Hi * p.Wi * p.Cin * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.dy + (int64_t)n * p.Ho * p.Wo * p.Cout), 0, p.Ho * p.Wo * p.Cout * 4, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int u = wave + 8 * i;
+      if (u < 12) {
+        const int iy = 2 * oy + (u >> 2), res = u & 3;
+        const bool xrow_ok = iy < p.Hi;                        // the pad row below the image, and rows of a ragged tile, read as 0
+#pragma unroll
+        for (int e = 0; e < 9; ++e) {
+          const int ix = 2 * ox0 + 4 * e + res;
+          const bool ok = xrow_ok && ix < p.Wi && (e < 8 || res == 0);      // wave-uniform; the pad column right of the image reads as 0
+          const unsigned soff = ok ? (unsigned)(iy * p.Wi + ix) * cin4 : 0u;
+          xr[i][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, ok ? xch : OOB, soff, 0));
+        }
+      }
+    }
+    const int wleft = p.Wo - ox0 - h;                          // columns 2 j + h < wleft are inside the image
+    const bool row_ok = oy < p.Ho;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool sok = row_ok && ox0 + 2 * j < p.Wo;
+      const unsigned soff = sok ? (unsigned)(oy * p.Wo + ox0 + 2 * j) * cout4 : 0u;
+      dr[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, (sok && 2 * j < wleft) ? dch : OOB, soff, 0));
+    }
+  };
+
+  const unsigned lds0 = lds_addr_of(ssm);
+  const unsigned xw = lds0 + (unsigned)lane * 16u;
+  const unsigned adrA = lds0 + (unsigned)h * 2u * DSP_RUN_B + (unsigned)(wm * 32 + li) * 16u;      // run 2 h + kw, halo row kh
+  constexpr int HI = 0, MID = 1, LO = 2;
+  constexpr int ORDER[6][2] = {{LO, HI}, {HI, LO}, {MID, MID}, {MID, HI}, {HI, MID}, {HI, HI}};    // (x plane, dy plane), smallest first
+
+  if (nst > 0) fetch(0);
+  for (int st = 0; st < nst; ++st) {
+    const unsigned buf = (unsigned)(st & 1) * DSP_BUF_B;
+    if (do_bias) {      // the f32 kernel's chain: pixel 2 s + h of k-step s = 0..15, tile row st & 1 is s = 8 (st & 1) .. + 7
+#pragma unroll
+      for (int j = 0; j < 8; ++j) bsum += dr[j];
+    }
+    u32x4 bfr[3];
+    split8(dr, bfr);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int u = wave + 8 * i;
+      if (u < 12) {
+        const int res = u & 3;
+        const unsigned dst = xw + buf + (unsigned)(res * 3 + (u >> 2)) * 1024u;
+        unsigned w[5][3];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) split_pair(xr[i][2 * k], xr[i][2 * k + 1], w[k]);
+        split_pair(xr[i][8], 0.f, w[4]);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          u32x4 v0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v0[k] = w[k][q];
+          lds_st128(dst + q * DSP_PLANE_B, v0);
+        }
+        if (res == 0) {      // run 4: Q0 from element 1
+#pragma unroll
+          for (int q = 0; q < 3; ++q) {
+            u32x4 v1;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v1[k] = __builtin_amdgcn_alignbit(w[k + 1][q], w[k][q], 16);
+            lds_st128(dst + q * DSP_PLANE_B + 4 * DSP_RUN_B, v1);
+          }
+        }
+      }
+    }
+    if (st + 1 < nst) fetch(st + 1);
+    __syncthreads();      // this stage's x runs are written; the other buffer's readers passed the previous barrier
+    bf16x8 b[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) b[q] = frag_from_u32x4(bfr[q]);
+#pragma unroll
+    for (int t9 = 0; t9 < 9; ++t9) {
+      bf16x8 a[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        a[q] = frag_from_u32x4(lds_ld128(adrA + buf + q * DSP_PLANE_B + (t9 % 3) * DSP_RUN_B + (t9 / 3) * 1024u));
+#pragma unroll
+      for (int o = 0; o < 6; ++o) acc[t9] = mfma_bf16(a[ORDER[o][0]], b[ORDER[o][1]], acc[t9]);
+    }
+  }
+
+  // slab [split][tap][CinP][CoutP], as conv3x3_wgrad_dma_kernel
+  const int co = co0 + wn * 32 + li;
+  float* sl = p.slab + (int64_t)split * 9 * p.CinP * p.CoutP;
+  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(sl, 0, 9 * p.CinP * p.CoutP * 4, 0x00020000);
+  const int tap_stride = p.CinP * p.CoutP * 4;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const unsigned rowoff = (unsigned)((ci0 + wm * 32 + acc_row(r, lane)) * p.CoutP + co) * 4u;
+#pragma unroll
+    for (int t9 = 0; t9 < 9; ++t9)
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[t9][r]), srsrc, rowoff, t9 * tap_stride, 0);
+  }
+  if (do_bias) {
+    bsum += __shfl_xor(bsum, 32, 64);
+    if (h == 0) p.bslab[(int64_t)split * p.CoutP + co] = bsum;
+  }
+}
+
 // ---- thin side: conv_in (3 -> C) and conv_out (C -> 3) ----------------------------------------------------------
 // With <= 3 channels on one side the nine taps of that side fit ONE 32-wide MFMA operand: out[c][j] = sum over pixels
 // of big[pixel][c] * small[pixel shifted by tap(j)][cs(j)], j = tap * Cs + cs < 27 -- a [C x pixels] x [pixels x 32]
@@ -708,9 +1037,39 @@ hipError_t launch_dyn(K kernel, dim3 grid, dim3 block, size_t smem, hipStream_t 
   return hipSuccess;
 }
 
+// The bf16-split form serves the parity-class kernel (mode 5 with both channel counts multiples of 4: any other mode 5 call runs the
+// dense form) and the Downsample conv where it gets the LDS-DMA kernel (mode 1, v2 of make_plan).
+bool direct_split_supported(int mode, int Cin, int Cout) {
+  return (mode == 5 || (mode == 1 && Cout > 64)) && Cin % 4 == 0 && Cout % 4 == 0;
+}
+// The shape rule (form -1): what was measured faster, slowest split launch of ten below the fastest f32 launch of ten, per launch at B = 32
+// on the eight Upsample / Downsample layers of the headline step (profiles/wgrad_direct_split.md section 1): 128, 256 and 512 channels,
+// 64 to 512 tiles per block at 0.58-0.64 (mode 5) and 32 to 512 tiles per block at 0.75-0.82 (mode 1) of the f32 kernel's time.  At 8
+// tiles per block (256 -> 256, 32^2 -> 16^2) launch, slab stores and reduction, which the forms share, leave a gain that one launch in
+// thirty did not show: fewer than 16 tiles per block keep the f32 kernel, and so do channel counts below those measured or with a
+// ragged last channel tile.
+bool direct_split_by_shape(const Plan& pl, int Cin, int Cout) {
+  return pl.tiles_per_split >= 16 && Cin >= 128 && Cout >= 128 && Cin == pl.CinP && Cout == pl.CoutP;
+}
+int g_direct_form = -1;      // set by odvae_conv3x3_wgrad_select
+
 }  // namespace
 
 extern "C" {
+
+// Which form of a tile's products odvae_conv3x3_wgrad_f32 runs: -1 by the shape rule (default), 0 the f32 MFMA kernels everywhere, 1 the
+// bf16-split form wherever it supports the call (the f32 kernels elsewhere).  Returns the previous setting.
+int odvae_conv3x3_wgrad_select(int form) {
+  const int prev = g_direct_form;
+  g_direct_form = form < 0 ? -1 : (form > 1 ? 1 : form);
+  return prev;
+}
+
+// 1 when odvae_conv3x3_wgrad_select(1) makes this call run the bf16-split form; host only
+int odvae_conv3x3_wgrad_split_supported(int mode, int N, int Hi, int Wi, int Cin, int Cout) {
+  if (N <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0) return 0;
+  return direct_split_supported(mode, Cin, Cout) ? 1 : 0;
+}
 
 size_t odvae_conv3x3_wgrad_workspace_bytes(int mode, int N, int Ho, int Wo, int Cin, int Cout) {
   if (thin_applies(mode, Ho, Wo, Cin, Cout)) return thin_workspace_floats(Cin, Cout) * sizeof(float);
@@ -793,8 +1152,11 @@ int odvae_conv3x3_wgrad_f32(int mode, const float* x, const float* dy, int N, in
   p.tiles_per_split = pl.tiles_per_split; p.ci_tiles = pl.ci_tiles;
   dim3 grid(pl.nsplit, pl.ci_tiles * pl.co_tiles);
   hipError_t e = hipSuccess;
+  const bool split = g_direct_form != 0 && direct_split_supported(mode, Cin, Cout) &&
+                     (g_direct_form == 1 || direct_split_by_shape(pl, Cin, Cout));
   if (pl.up) {
-    e = launch_dyn(conv3x3_wgrad_up_kernel, grid, dim3(512), (size_t)2 * UpGeom::BUF_F * sizeof(float), st, p);
+    if (split) e = launch_dyn(conv3x3_wgrad_up_split_kernel, grid, dim3(512), (size_t)2 * USP_BUF_B, st, p);
+    else e = launch_dyn(conv3x3_wgrad_up_kernel, grid, dim3(512), (size_t)2 * UpGeom::BUF_F * sizeof(float), st, p);
     if (e != hipSuccess) {
       odvae_set_error("conv3x3_wgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
       return ODVAE_ERR_HIP;
@@ -808,6 +1170,7 @@ int odvae_conv3x3_wgrad_f32(int mode, const float* x, const float* dy, int N, in
   }
   if (pl.v2) {
     if (mode == 0)      e = launch_dyn(conv3x3_wgrad_dma_kernel<0, 4>, grid, dim3(512), (size_t)2 * DmaGeom<0, 4>::BUF_F * sizeof(float), st, p);
+    else if (mode == 1 && split) e = launch_dyn(conv3x3_wgrad_down_split_kernel, grid, dim3(512), (size_t)2 * DSP_BUF_B, st, p);
     else if (mode == 1) e = launch_dyn(conv3x3_wgrad_dma_kernel<1, 2>, grid, dim3(512), (size_t)2 * DmaGeom<1, 2>::BUF_F * sizeof(float), st, p);
     else                e = launch_dyn(conv3x3_wgrad_dma_kernel<2, 4>, grid, dim3(512), (size_t)2 * DmaGeom<2, 4>::BUF_F * sizeof(float), st, p);
   } else {

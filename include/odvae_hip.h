@@ -153,6 +153,15 @@ int odvae_conv3x3_wgrad_f32(int mode, const float* x, const float* dy, int N, in
  * form.  kind 0: {0, blocks per channel group, waves (= partial slabs), channel groups of 128, 0, 0, 1, 0}; wave w owns image rows w,
  * w + waves, ... of the N * Hi rows. */
 int odvae_conv3x3_wgrad_plan(int mode, int N, int Hi, int Wi, int Cin, int Cout, int out[8]);
+/* How odvae_conv3x3_wgrad_f32 forms a pixel tile's products: -1 by a shape rule (default), 0 the f32 MFMA kernels everywhere, 1 the
+ * bf16-split form (each f32 value of x and dy split exactly into three bf16, six products on v_mfma_f32_32x32x16_bf16, f32
+ * accumulation) wherever ..._split_supported() == 1: the parity-class kernel (kind 3) and the LDS-DMA kernel in mode 1 (kind 2).  Plan,
+ * slabs, reduction and workspace are the same under every setting, dbias is the same bits; dw of the split form is within 2^-22 of
+ * sum |x| |dy| of the f32 kernels' error.  The rule admits what was measured faster (profiles/wgrad_direct_split.md): at least 16 tiles per
+ * block, 128 or more channels on both sides, whole channel tiles.  Returns the previous setting.  ..._split_supported is host only and
+ * launches nothing. */
+int odvae_conv3x3_wgrad_select(int form);
+int odvae_conv3x3_wgrad_split_supported(int mode, int N, int Hi, int Wi, int Cin, int Cout);
 
 /* ---- conv3x3_wgrad_wino_f32.hip: the same weight/bias gradient for mode 0 (stride 1, pad 1) in the Winograd
  * F(2x2,3x3) domain: dU[xi] = sum over 2x2 tiles of (B^T d B)[xi]^T (A dY A^T)[xi], dw = G^T dU G -- 16 instead of 36
