@@ -68,17 +68,29 @@ static inline bool vec8(int64_t n, int C, const void* a, const void* b, const vo
 }
 
 // The exact three-way split of f32 into bf16 (x = hi + mid + lo, round to nearest even, both differences exact in f32) that
-// gemm_f32_split.hip and the split form of conv3x3_wgrad_wino_f32.hip feed to the bf16 MFMA:
+// gemm_f32_split.hip and the split forms of conv3x3_wgrad_wino_f32.hip and conv3x3_wgrad_f32.hip feed to the bf16 MFMA.
+// The planes, and the six of their nine products that reach f32 precision as (A plane, B plane), smallest first:
+namespace split3 {
+constexpr int HI = 0, MID = 1, LO = 2;
+struct Order { int p[6][2]; };      // a struct, so that a kernel can take a copy
+constexpr Order ORDER = {{{LO, HI}, {HI, LO}, {MID, MID}, {MID, HI}, {HI, MID}, {HI, HI}}};
+}  // namespace split3
+// x0, x1 -> the packed words of the planes hi, mid, lo (x0 in bits 0..15)
+__device__ __forceinline__ void split_pair(float x0, float x1, unsigned (&w)[3]) {
+  w[0] = cvt_pk_bf16(x0, x1);
+  const float r0 = x0 - bf16_lo(w[0]), r1 = x1 - bf16_hi(w[0]);
+  w[1] = cvt_pk_bf16(r0, r1);
+  const float s0 = r0 - bf16_lo(w[1]), s1 = r1 - bf16_hi(w[1]);
+  w[2] = cvt_pk_bf16(s0, s1);
+}
 // x[0..7] (consecutive k of one row) -> the 16 bytes of the planes hi (0), mid (1), lo (2)
 __device__ __forceinline__ void split8(const float (&x)[8], u32x4 (&pl)[3]) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const float x0 = x[2 * j], x1 = x[2 * j + 1];
-    const unsigned h = cvt_pk_bf16(x0, x1);
-    const float r0 = x0 - bf16_lo(h), r1 = x1 - bf16_hi(h);
-    const unsigned m = cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - bf16_lo(m), s1 = r1 - bf16_hi(m);
-    pl[0][j] = h; pl[1][j] = m; pl[2][j] = cvt_pk_bf16(s0, s1);
+    unsigned w[3];
+    split_pair(x[2 * j], x[2 * j + 1], w);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) pl[q][j] = w[q];
   }
 }
 // D(32x32) += A(32x16) * B(16x32), bf16 in, f32 accumulate.  lane l (r = l&31, h = l>>5) supplies A[row r][k = 8h+j] and

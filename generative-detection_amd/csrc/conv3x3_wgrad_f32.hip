@@ -6,15 +6,25 @@
 // ([UPSTREAM] ldm/modules/diffusionmodules/model.py ResnetBlock / Downsample / Upsample convs; what
 // loss.backward() computes for them in the reference, src/models/autoencoder.py:295-330).
 //
-// GEMM view per tap: M = ci, N = co, K = pixels (up to N*Ho*Wo = 2M).  A block owns a 64(ci) x 64(co)
-// slice of all 9 taps (each wave 32x32 x 9 taps = 144 accumulator registers) and a contiguous range of
-// 8x16 (MODE 1: 4x16) output-pixel tiles.  Per tile it stages the input halo patch [halo px][64 ci] and
-// the dy tile [px][64 co] in LDS; both are read with lanes = consecutive channels (conflict-free b32),
-// one dy read feeds nine MFMAs.  Blocks write partial slabs; a second kernel sums them in a fixed order
-// (deterministic) and writes OIHW.  db = column sums of dy ride along in the ci-tile-0 blocks.
-// The Upsample (mode 5) and Downsample (mode 1) kernels also exist in a bf16-split form (conv3x3_wgrad_up_split_kernel,
-// conv3x3_wgrad_down_split_kernel below): same plan, slabs and reduction, six bf16 products of exactly split operands per f32 product;
-// odvae_conv3x3_wgrad_select chooses (default: by shape).
+// GEMM view per tap: M = ci, N = co, K = pixels (up to N*Ho*Wo = 2M).  A block owns a ci x co slice of all taps and a
+// contiguous range of pixel tiles (split = blockIdx.x); blocks write partial slabs [split][tap][CinP][CoutP], a second
+// kernel sums them in a fixed order (deterministic) and writes OIHW.  db = column sums of dy ride along in the
+// ci-tile-0 blocks.
+//
+// Map of the file.  kind is what odvae_conv3x3_wgrad_plan reports; make_plan chooses it from the mode and the channel counts alone:
+//   kind | kernel(s)                                   | block, pixel tile                | chosen when
+//   0    | conv3x3_wgrad_thin_kernel, thin_colsum_kernel,| 128 wide channels, whole image   | thin_applies: mode 0, Cin <= 3 or Cout <= 3 (conv_in,
+//        | conv3x3_wgrad_thin_reduce_kernel             | rows, no LDS                     | conv_out), W % 16 == 0, the wide side % 4 == 0 and >= 32
+//   1 v1 | conv3x3_wgrad_kernel<MODE, TH>               | 64 ci x 64 co, 8 x 16 (mode 1:   | everything else: Cin % 4 or Cout % 4 != 0, or Cout <= 64;
+//        |                                              | 4 x 16), 256 threads, 1024 blocks| mode 5 with such channel counts runs MODE 2
+//   2 v2 | conv3x3_wgrad_dma_kernel<MODE, TH>           | 64 ci x 128 co, 4 x 16 (mode 1:  | modes 0, 1, 2 with Cin % 4 == Cout % 4 == 0 and Cout > 64
+//        | conv3x3_wgrad_down_split_kernel (mode 1)     | 2 x 16), 512 threads, 256 blocks | split form: selector 1, or -1 and direct_split_by_shape
+//   3 up | conv3x3_wgrad_up_kernel                      | 64 ci x 64 co x 4 parity classes,| mode 5 with Cin % 4 == Cout % 4 == 0
+//        | conv3x3_wgrad_up_split_kernel                | 2 x 16 low-res, 512 thr, 256 blk | split form: as for kind 2
+// Kinds 1 and 2 end in conv3x3_wgrad_reduce_kernel (9 taps, 1 bias row per split), kind 3 in conv3x3_wgrad_up_reduce_kernel
+// (16 parity taps, 4 bias rows per split): slab_taps / bias_rows.  The split forms keep their f32 kernel's plan, slabs and
+// reduction and replace each f32 product by six bf16 products of exactly split operands (bf16_common.h, split3);
+// odvae_conv3x3_wgrad_select sets the selector (default -1: by shape).  Helpers shared by the block kernels come first.
 #include "bf16_common.h"
 
 namespace {
@@ -43,6 +53,70 @@ __device__ __forceinline__ int halo_index(int r, int c, int kh, int kw) {
   return ((r + kh + 1) >> 1) * Halo<2, TH>::W + ((c + kw + 1) >> 1);
 }
 
+// ---- steps every block kernel takes ------------------------------------------------------------------------------
+// pixel tile `tile` of the plan: image n, tile row ty, tile column tx
+struct Tile { int n, ty, tx; };
+__device__ __forceinline__ Tile tile_decode(const WgradParams& p, int tile) {
+  Tile t;
+  t.tx = tile % p.tiles_x; tile /= p.tiles_x;
+  t.ty = tile % p.tiles_y; t.n = tile / p.tiles_y;
+  return t;
+}
+
+// raw buffer over `bytes` bytes (below 2 GiB) from base: a lane whose offset is >= bytes, OOB for one, loads 0 and stores nothing
+constexpr unsigned OOB = 0x7FFFFFF0u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t f32_rsrc(const float* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
+}
+// image n of x and of dy (the launcher keeps one image below 2 GiB)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t x_rsrc(const WgradParams& p, int n) {
+  return f32_rsrc(p.x + (int64_t)n * p.Hi * p.Wi * p.Cin, p.Hi * p.Wi * p.Cin * 4);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t dy_rsrc(const WgradParams& p, int n) {
+  return f32_rsrc(p.dy + (int64_t)n * p.Ho * p.Wo * p.Cout, p.Ho * p.Wo * p.Cout * 4);
+}
+
+template <int NT>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[NT]) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+}
+
+// Slab stores of the LDS-DMA family: this split's slab [taps][CinP][CoutP] as one buffer, 32-bit offsets into it, the tap
+// stride in the scalar offset (no per-element address arithmetic).  Precondition, checked by the launcher (slab_fits): one
+// split's slab, taps * CinP * CoutP * 4 bytes, stays below 2^31, or num_records and the offsets would wrap.
+// store_taps: NT taps from tap0 on of the 32 x 32 sub-tile at rows ci_base.., column co (lane = co).
+template <int NT>
+__device__ __forceinline__ void store_taps(__amdgpu_buffer_rsrc_t srsrc, const WgradParams& p, const f32x16 (&acc)[NT],
+                                           int tap0, int ci_base, int co, int lane) {
+  const int tap_stride = p.CinP * p.CoutP * 4;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const unsigned rowoff = (unsigned)((ci_base + acc_row(r, lane)) * p.CoutP + co) * 4u;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[t][r]), srsrc, rowoff, (tap0 + t) * tap_stride, 0);
+  }
+}
+// slab [split][tap][CinP][CoutP]
+__device__ __forceinline__ void store_slab9(const WgradParams& p, int split, const f32x16 (&acc)[9], int ci_base, int co, int lane) {
+  store_taps(f32_rsrc(p.slab + (int64_t)split * 9 * p.CinP * p.CoutP, 9 * p.CinP * p.CoutP * 4), p, acc, 0, ci_base, co, lane);
+}
+// slab [split][cls * 4 + tap][CinP][CoutP]: both ci sub-tiles of parity class cls
+__device__ __forceinline__ void store_slab_parity(const WgradParams& p, int split, const f32x16 (&acc)[2][4], int cls, int ci0, int co, int lane) {
+  const __amdgpu_buffer_rsrc_t srsrc = f32_rsrc(p.slab + (int64_t)split * 16 * p.CinP * p.CoutP, 16 * p.CinP * p.CoutP * 4);
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) store_taps(srsrc, p, acc[mt], cls * 4, ci0 + mt * 32, co, lane);
+}
+
+// the lane halves hold the sums over the even and the odd pixels of column co: added, lane half 0 stores row `row` of the bias slab
+__device__ __forceinline__ void store_bias(const WgradParams& p, int row, int co, int h, float bsum) {
+  bsum += __shfl_xor(bsum, 32, 64);
+  if (h == 0) p.bslab[(int64_t)row * p.CoutP + co] = bsum;
+}
+
 template <int MODE, int TH>
 __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(WgradParams p) {
   constexpr int HPIX = Halo<MODE, TH>::H * Halo<MODE, TH>::W;
@@ -63,25 +137,20 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(WgradParams p) {
   const bool do_bias = p.bslab != nullptr && ci_tile == 0 && wm == 0;
 
   f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  zero_acc(acc);
   float bsum = 0.f;
 
   const int t_beg = split * p.tiles_per_split;
   const int t_end = min(p.ntiles, t_beg + p.tiles_per_split);
   for (int tile = t_beg; tile < t_end; ++tile) {
-    int t = tile;
-    const int tx = t % p.tiles_x; t /= p.tiles_x;
-    const int ty = t % p.tiles_y; const int n = t / p.tiles_y;
-    const int oy0 = ty * TH, ox0 = tx * TW;
+    const Tile tl = tile_decode(p, tile);
+    const int oy0 = tl.ty * TH, ox0 = tl.tx * TW;
     int iy0, ix0;
     if (MODE == 0) { iy0 = oy0 - 1; ix0 = ox0 - 1; }
     else if (MODE == 1) { iy0 = 2 * oy0; ix0 = 2 * ox0; }
     else { iy0 = oy0 / 2 - 1; ix0 = ox0 / 2 - 1; }
-    const float* xn = p.x + (int64_t)n * p.Hi * p.Wi * p.Cin;
-    const float* dn = p.dy + (int64_t)n * p.Ho * p.Wo * p.Cout;
+    const float* xn = p.x + (int64_t)tl.n * p.Hi * p.Wi * p.Cin;
+    const float* dn = p.dy + (int64_t)tl.n * p.Ho * p.Wo * p.Cout;
 
     __syncthreads();  // previous tile's reads are done
 #pragma unroll
@@ -154,7 +223,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(WgradParams p) {
       const int ci = ci0 + wm * 32 + acc_row(r, lane);
       sl[((int64_t)t9 * p.CinP + ci) * p.CoutP + co] = acc[t9][r];
     }
-  if (do_bias) {
+  if (do_bias) {      // store_bias, written out: through the helper this kernel takes 8 to 10 VGPRs more (profiles/wgrad_direct_refactor.md)
     bsum += __shfl_xor(bsum, 32, 64);
     if (h == 0) p.bslab[(int64_t)split * p.CoutP + co] = bsum;
   }
@@ -195,27 +264,18 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_dma_kernel(WgradParams p
   const bool do_bias = p.bslab != nullptr && ci_tile == 0 && wm == 0;
 
   f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  zero_acc(acc);
   float bsum = 0.f;
 
   auto issue = [&](int tile, int buf) {
-    int t = tile;
-    const int tx = t % p.tiles_x; t /= p.tiles_x;
-    const int ty = t % p.tiles_y; const int n = t / p.tiles_y;
-    const int oy0 = ty * TH, ox0 = tx * TW;
+    const Tile tl = tile_decode(p, tile);
+    const int oy0 = tl.ty * TH, ox0 = tl.tx * TW;
     int iy0, ix0;
     if (MODE == 0) { iy0 = oy0 - 1; ix0 = ox0 - 1; }
     else if (MODE == 1) { iy0 = 2 * oy0; ix0 = 2 * ox0; }
     else { iy0 = oy0 / 2 - 1; ix0 = ox0 / 2 - 1; }
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x + (int64_t)n * p.Hi * p.Wi * p.Cin), 0, p.Hi * p.Wi * p.Cin * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.dy + (int64_t)n * p.Ho * p.Wo * p.Cout), 0, p.Ho * p.Wo * p.Cout * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = x_rsrc(p, tl.n), rd = dy_rsrc(p, tl.n);
     float* base = smem + buf * G::BUF_F;
-    const unsigned OOB = 0x7FFFFFF0u;   // >= num_records: the load returns 0
     for (int j = wave; j < G::NH + G::ND; j += 8) {
       if (j < G::NH) {
         const int f = j * 64 + lane;
@@ -279,28 +339,20 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_dma_kernel(WgradParams p
     }
   }
 
-  // slab stores: 32-bit offsets into this split's slab; the tap stride goes into the scalar offset, so a store costs
-  // no per-element address arithmetic (144 stores per lane)
   const int co = co0 + wn * 32 + li;
-  float* sl = p.slab + (int64_t)split * 9 * p.CinP * p.CoutP;
-  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(sl, 0, 9 * p.CinP * p.CoutP * 4, 0x00020000);
-  unsigned rowoff[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) rowoff[r] = (unsigned)((ci0 + wm * 32 + acc_row(r, lane)) * p.CoutP + co) * 4u;
-  const int tap_stride = p.CinP * p.CoutP * 4;
-#pragma unroll
-  for (int t9 = 0; t9 < 9; ++t9)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[t9][r]), srsrc, rowoff[r], t9 * tap_stride, 0);
-  if (do_bias) {
-    bsum += __shfl_xor(bsum, 32, 64);
-    if (h == 0) p.bslab[(int64_t)split * p.CoutP + co] = bsum;
-  }
+  store_slab9(p, split, acc, ci0 + wm * 32, co, lane);
+  if (do_bias) store_bias(p, split, co, h, bsum);
+}
+
+// bias tail of both reduce kernels: dbias[co] = the bias slab's rows (brows per split), added in their order
+__device__ __forceinline__ float bias_sum(const float* __restrict__ bslab, int rows, int co, int CoutP) {
+  float s = 0.f;
+  for (int sp = 0; sp < rows; ++sp) s += bslab[(int64_t)sp * CoutP + co];
+  return s;
 }
 
 __global__ void conv3x3_wgrad_reduce_kernel(const float* __restrict__ slab, const float* __restrict__ bslab,
-                                            int nsplit, int Cin, int Cout, int CinP, int CoutP,
+                                            int nsplit, int brows, int Cin, int Cout, int CinP, int CoutP,
                                             float* __restrict__ dw, float* __restrict__ dbias) {
   const int64_t per = (int64_t)9 * CinP * CoutP;
   const int64_t total = per + (dbias ? CoutP : 0);
@@ -322,11 +374,7 @@ __global__ void conv3x3_wgrad_reduce_kernel(const float* __restrict__ slab, cons
       }
     } else {
       const int co = (int)(idx - per);
-      if (co < Cout) {
-        float s = 0.f;
-        for (int sp = 0; sp < nsplit; ++sp) s += bslab[(int64_t)sp * CoutP + co];
-        dbias[co] = s;
-      }
+      if (co < Cout) dbias[co] = bias_sum(bslab, nsplit * brows, co, CoutP);
     }
   }
 }
@@ -362,25 +410,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_up_kernel(WgradParams p)
   const bool do_bias = p.bslab != nullptr && ci_tile == 0;
 
   f32x16 acc[2][4];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mt][t][r] = 0.f;
+  zero_acc(acc[0]); zero_acc(acc[1]);
   float bsum = 0.f;
 
   auto issue = [&](int tile, int buf) {
-    int t = tile;
-    const int tx = t % p.tiles_x; t /= p.tiles_x;
-    const int ty = t % p.tiles_y; const int n = t / p.tiles_y;
-    const int ly0 = ty * UP_TH, lx0 = tx * TW;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x + (int64_t)n * p.Hi * p.Wi * p.Cin), 0, p.Hi * p.Wi * p.Cin * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.dy + (int64_t)n * p.Ho * p.Wo * p.Cout), 0, p.Ho * p.Wo * p.Cout * 4, 0x00020000);
+    const Tile tl = tile_decode(p, tile);
+    const int ly0 = tl.ty * UP_TH, lx0 = tl.tx * TW;
+    const __amdgpu_buffer_rsrc_t rx = x_rsrc(p, tl.n), rd = dy_rsrc(p, tl.n);
     float* base = smem + buf * G::BUF_F;
-    const unsigned OOB = 0x7FFFFFF0u;   // >= num_records: the load returns 0
     for (int j = wave; j < G::NH + G::ND; j += 8) {
       if (j < G::NH) {
         const int f = j * 64 + lane;
@@ -443,30 +480,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_up_kernel(WgradParams p)
     }
   }
 
-  // slab [split][cls * 4 + tap][CinP][CoutP]
   const int co = co0 + wn * 32 + li;
-  float* sl = p.slab + (int64_t)split * 16 * p.CinP * p.CoutP;
-  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(sl, 0, 16 * p.CinP * p.CoutP * 4, 0x00020000);
-  const int tap_stride = p.CinP * p.CoutP * 4;
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const unsigned rowoff = (unsigned)((ci0 + mt * 32 + acc_row(r, lane)) * p.CoutP + co) * 4u;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[mt][t][r]), srsrc, rowoff, (cls * 4 + t) * tap_stride, 0);
-    }
-  if (do_bias) {
-    bsum += __shfl_xor(bsum, 32, 64);
-    if (h == 0) p.bslab[((int64_t)split * 4 + cls) * p.CoutP + co] = bsum;
-  }
+  store_slab_parity(p, split, acc, cls, ci0, co, lane);
+  if (do_bias) store_bias(p, split * 4 + cls, co, h, bsum);
 }
 
 // dW[kh][kw] = sum of the dWeff entries (py, a) x (px, b) with kh in R(py, a), kw in R(px, b):
 // kh = 0: (0,0) (1,0) | kh = 1: (0,1) (1,0) | kh = 2: (0,1) (1,1); splits summed in a fixed order
 __global__ void conv3x3_wgrad_up_reduce_kernel(const float* __restrict__ slab, const float* __restrict__ bslab,
-                                               int nsplit, int Cin, int Cout, int CinP, int CoutP,
+                                               int nsplit, int brows, int Cin, int Cout, int CinP, int CoutP,
                                                float* __restrict__ dw, float* __restrict__ dbias) {
   const int64_t mat = (int64_t)CinP * CoutP;
   const int64_t per = 9 * mat;
@@ -494,11 +516,7 @@ __global__ void conv3x3_wgrad_up_reduce_kernel(const float* __restrict__ slab, c
       }
     } else {
       const int co = (int)(idx - per);
-      if (co < Cout) {
-        float s = 0.f;
-        for (int sp = 0; sp < nsplit * 4; ++sp) s += bslab[(int64_t)sp * CoutP + co];
-        dbias[co] = s;
-      }
+      if (co < Cout) dbias[co] = bias_sum(bslab, nsplit * brows, co, CoutP);
     }
   }
 }
@@ -523,13 +541,18 @@ constexpr unsigned USP_RUN_B = 4 * 64 * 16;          // one run: 4 halo rows x 6
 constexpr unsigned USP_PLANE_B = 4 * USP_RUN_B;      // 16 384
 constexpr unsigned USP_BUF_B = 3 * USP_PLANE_B;      // 49 152
 
-// x0, x1 -> the packed words of the planes hi, mid, lo (x0 in bits 0..15): split8's arithmetic on one pair
-__device__ __forceinline__ void split_pair(float x0, float x1, unsigned (&w)[3]) {
-  w[0] = cvt_pk_bf16(x0, x1);
-  const float r0 = x0 - bf16_lo(w[0]), r1 = x1 - bf16_hi(w[0]);
-  w[1] = cvt_pk_bf16(r0, r1);
-  const float s0 = r0 - bf16_lo(w[1]), s1 = r1 - bf16_hi(w[1]);
-  w[2] = cvt_pk_bf16(s0, s1);
+// dr[j] = dy row oy at tile column c = col0 + 2 j + h of `width` columns, which is dy pixel xs * c + xo; dch holds the lane's channel
+// and its lane half's column.  A row or a column outside the image reads as 0 (offset past num_records; the scalar offset stays inside).
+__device__ __forceinline__ void fetch_dy_row(__amdgpu_buffer_rsrc_t rd, const WgradParams& p, int oy, int col0, int width, int xs, int xo,
+                                             unsigned dch, int h, float (&dr)[8]) {
+  const int wleft = width - col0 - h;                        // columns 2 j + h < wleft are inside the image
+  const bool row_ok = oy < p.Ho;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const bool sok = row_ok && col0 + 2 * j < width;         // wave-uniform: the h = 0 column is inside
+    const unsigned soff = sok ? (unsigned)(oy * p.Wo + xs * (col0 + 2 * j) + xo) * ((unsigned)p.Cout * 4u) : 0u;
+    dr[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, (sok && 2 * j < wleft) ? dch : OOB, soff, 0));
+  }
 }
 
 __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_up_split_kernel(WgradParams p) {
@@ -545,34 +568,23 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_up_split_kernel(WgradPar
   const bool do_bias = p.bslab != nullptr && ci_tile == 0;
 
   f32x16 acc[2][4];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mt][t][r] = 0.f;
+  zero_acc(acc[0]); zero_acc(acc[1]);
   float bsum = 0.f;
 
   // loader roles.  x: halo row xrow, column parity xu, channel ci0 + lane.  dy: this wave's class, rows 0 and 1, channel co0 + wn * 32
   // + li, low-res columns 2 j + h.  A lane past the channel count, a row or a column outside the image reads as 0 (offset past
   // num_records; the scalar offset stays inside the image).
   const int xrow = wave >> 1, xu = wave & 1;
-  const unsigned OOB = 0x7FFFFFF0u;
-  const unsigned cin4 = (unsigned)p.Cin * 4u, cout4 = (unsigned)p.Cout * 4u;
+  const unsigned cin4 = (unsigned)p.Cin * 4u;
   const unsigned xch = ci0 + lane < p.Cin ? (unsigned)(ci0 + lane) * 4u : OOB;
   const int co_l = co0 + wn * 32 + li;
-  const unsigned dch = co_l < p.Cout ? (unsigned)co_l * 4u + (unsigned)h * 2u * cout4 : OOB;
+  const unsigned dch = co_l < p.Cout ? (unsigned)co_l * 4u + (unsigned)h * 2u * ((unsigned)p.Cout * 4u) : OOB;
 
   float xr[9], dr[2][8];
   auto fetch = [&](int tile) {
-    int t = tile;
-    const int tx = t % p.tiles_x; t /= p.tiles_x;
-    const int ty = t % p.tiles_y; const int n = t / p.tiles_y;
-    const int ly0 = ty * UP_TH, lx0 = tx * TW;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x + (int64_t)n * p.Hi * p.Wi * p.Cin), 0, p.Hi * p.Wi * p.Cin * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.dy + (int64_t)n * p.Ho * p.Wo * p.Cout), 0, p.Ho * p.Wo * p.Cout * 4, 0x00020000);
+    const Tile tl = tile_decode(p, tile);
+    const int ly0 = tl.ty * UP_TH, lx0 = tl.tx * TW;
+    const __amdgpu_buffer_rsrc_t rx = x_rsrc(p, tl.n), rd = dy_rsrc(p, tl.n);
     const int iy = ly0 - 1 + xrow;
     const bool xrow_ok = iy >= 0 && iy < p.Hi;
 #pragma unroll
@@ -582,25 +594,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_up_split_kernel(WgradPar
       const unsigned soff = ok ? (unsigned)(iy * p.Wi + ix) * cin4 : 0u;
       xr[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, ok ? xch : OOB, soff, 0));
     }
-    const int wleft = p.Wi - lx0 - h;                        // columns 2 j + h < wleft are inside the image
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int oy = 2 * (ly0 + r) + py;
-      const bool row_ok = oy < p.Ho;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const bool sok = row_ok && lx0 + 2 * j < p.Wi;       // wave-uniform: the h = 0 column is inside
-        const unsigned soff = sok ? (unsigned)(oy * p.Wo + 2 * (lx0 + 2 * j) + px) * cout4 : 0u;
-        dr[r][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, (sok && 2 * j < wleft) ? dch : OOB, soff, 0));
-      }
-    }
+    for (int r = 0; r < 2; ++r) fetch_dy_row(rd, p, 2 * (ly0 + r) + py, lx0, p.Wi, 2, px, dch, h, dr[r]);
   };
 
   const unsigned lds0 = lds_addr_of(ssm);
   const unsigned xw = lds0 + (unsigned)(xu * 4 + xrow) * 1024u + (unsigned)lane * 16u;                 // run xu; run xu + 2 is 2 * USP_RUN_B on
   const unsigned adrA = lds0 + (unsigned)((h + px) * 4 + py) * 1024u + (unsigned)li * 16u;            // run h + px + b, halo row py + a + r
-  constexpr int HI = 0, MID = 1, LO = 2;
-  constexpr int ORDER[6][2] = {{LO, HI}, {HI, LO}, {MID, MID}, {MID, HI}, {HI, MID}, {HI, HI}};        // (x plane, dy plane), smallest first
+  constexpr split3::Order ORDER = split3::ORDER;      // (x plane, dy plane); the kernel's own copy: read in place, six VGPRs more (profiles/wgrad_direct_refactor.md)
 
   const int t_beg = split * p.tiles_per_split;
   const int ntl = min(p.ntiles, t_beg + p.tiles_per_split) - t_beg;
@@ -650,29 +651,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_up_split_kernel(WgradPar
 #pragma unroll
         for (int o = 0; o < 6; ++o)
 #pragma unroll
-          for (int mt = 0; mt < 2; ++mt) acc[mt][t] = mfma_bf16(a[mt][ORDER[o][0]], b[ORDER[o][1]], acc[mt][t]);
+          for (int mt = 0; mt < 2; ++mt) acc[mt][t] = mfma_bf16(a[mt][ORDER.p[o][0]], b[ORDER.p[o][1]], acc[mt][t]);
       }
     }
   }
 
-  // slab [split][cls * 4 + tap][CinP][CoutP]
   const int co = co0 + wn * 32 + li;
-  float* sl = p.slab + (int64_t)split * 16 * p.CinP * p.CoutP;
-  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(sl, 0, 16 * p.CinP * p.CoutP * 4, 0x00020000);
-  const int tap_stride = p.CinP * p.CoutP * 4;
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const unsigned rowoff = (unsigned)((ci0 + mt * 32 + acc_row(r, lane)) * p.CoutP + co) * 4u;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[mt][t][r]), srsrc, rowoff, (cls * 4 + t) * tap_stride, 0);
-    }
-  if (do_bias) {
-    bsum += __shfl_xor(bsum, 32, 64);
-    if (h == 0) p.bslab[((int64_t)split * 4 + cls) * p.CoutP + co] = bsum;
-  }
+  store_slab_parity(p, split, acc, cls, ci0, co, lane);
+  if (do_bias) store_bias(p, split * 4 + cls, co, h, bsum);
 }
 
 // ---- Downsample conv (pad (0, 1, 0, 1), stride 2), bf16-split form -------------------------------------------------
@@ -702,31 +688,22 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_down_split_kernel(WgradP
   const bool do_bias = p.bslab != nullptr && ci_tile == 0 && wm == 0;
 
   f32x16 acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  zero_acc(acc);
   float bsum = 0.f;
 
-  const unsigned OOB = 0x7FFFFFF0u;
-  const unsigned cin4 = (unsigned)p.Cin * 4u, cout4 = (unsigned)p.Cout * 4u;
+  const unsigned cin4 = (unsigned)p.Cin * 4u;
   const unsigned xch = ci0 + lane < p.Cin ? (unsigned)(ci0 + lane) * 4u : OOB;
   const int co_l = co0 + wn * 32 + li;
-  const unsigned dch = co_l < p.Cout ? (unsigned)co_l * 4u + (unsigned)h * cout4 : OOB;
+  const unsigned dch = co_l < p.Cout ? (unsigned)co_l * 4u + (unsigned)h * ((unsigned)p.Cout * 4u) : OOB;
 
   const int t_beg = split * p.tiles_per_split;
   const int nst = 2 * (min(p.ntiles, t_beg + p.tiles_per_split) - t_beg);      // stages: tile row st & 1 of tile t_beg + st / 2
 
   float xr[2][9], dr[8];      // x: units wave, wave + 8 (< 12): halo row unit >> 2 of the stage's three, residue unit & 3
   auto fetch = [&](int st) {
-    int t = t_beg + (st >> 1);
-    const int tx = t % p.tiles_x; t /= p.tiles_x;
-    const int ty = t % p.tiles_y; const int n = t / p.tiles_y;
-    const int oy = ty * 2 + (st & 1), ox0 = tx * TW;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.x + (int64_t)n * p.Hi * p.Wi * p.Cin), 0, p.Hi * p.Wi * p.Cin * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.dy + (int64_t)n * p.Ho * p.Wo * p.Cout), 0, p.Ho * p.Wo * p.Cout * 4, 0x00020000);
+    const Tile tl = tile_decode(p, t_beg + (st >> 1));
+    const int oy = tl.ty * 2 + (st & 1), ox0 = tl.tx * TW;
+    const __amdgpu_buffer_rsrc_t rx = x_rsrc(p, tl.n), rd = dy_rsrc(p, tl.n);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int u = wave + 8 * i;
@@ -742,21 +719,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_down_split_kernel(WgradP
         }
       }
     }
-    const int wleft = p.Wo - ox0 - h;                          // columns 2 j + h < wleft are inside the image
-    const bool row_ok = oy < p.Ho;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const bool sok = row_ok && ox0 + 2 * j < p.Wo;
-      const unsigned soff = sok ? (unsigned)(oy * p.Wo + ox0 + 2 * j) * cout4 : 0u;
-      dr[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, (sok && 2 * j < wleft) ? dch : OOB, soff, 0));
-    }
+    fetch_dy_row(rd, p, oy, ox0, p.Wo, 1, 0, dch, h, dr);
   };
 
   const unsigned lds0 = lds_addr_of(ssm);
   const unsigned xw = lds0 + (unsigned)lane * 16u;
   const unsigned adrA = lds0 + (unsigned)h * 2u * DSP_RUN_B + (unsigned)(wm * 32 + li) * 16u;      // run 2 h + kw, halo row kh
-  constexpr int HI = 0, MID = 1, LO = 2;
-  constexpr int ORDER[6][2] = {{LO, HI}, {HI, LO}, {MID, MID}, {MID, HI}, {HI, MID}, {HI, HI}};    // (x plane, dy plane), smallest first
+  using namespace split3;      // ORDER: (x plane, dy plane)
 
   if (nst > 0) fetch(0);
   for (int st = 0; st < nst; ++st) {
@@ -807,26 +776,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_down_split_kernel(WgradP
       for (int q = 0; q < 3; ++q)
         a[q] = frag_from_u32x4(lds_ld128(adrA + buf + q * DSP_PLANE_B + (t9 % 3) * DSP_RUN_B + (t9 / 3) * 1024u));
 #pragma unroll
-      for (int o = 0; o < 6; ++o) acc[t9] = mfma_bf16(a[ORDER[o][0]], b[ORDER[o][1]], acc[t9]);
+      for (int o = 0; o < 6; ++o) acc[t9] = mfma_bf16(a[ORDER.p[o][0]], b[ORDER.p[o][1]], acc[t9]);
     }
   }
 
-  // slab [split][tap][CinP][CoutP], as conv3x3_wgrad_dma_kernel
   const int co = co0 + wn * 32 + li;
-  float* sl = p.slab + (int64_t)split * 9 * p.CinP * p.CoutP;
-  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(sl, 0, 9 * p.CinP * p.CoutP * 4, 0x00020000);
-  const int tap_stride = p.CinP * p.CoutP * 4;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const unsigned rowoff = (unsigned)((ci0 + wm * 32 + acc_row(r, lane)) * p.CoutP + co) * 4u;
-#pragma unroll
-    for (int t9 = 0; t9 < 9; ++t9)
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[t9][r]), srsrc, rowoff, t9 * tap_stride, 0);
-  }
-  if (do_bias) {
-    bsum += __shfl_xor(bsum, 32, 64);
-    if (h == 0) p.bslab[(int64_t)split * p.CoutP + co] = bsum;
-  }
+  store_slab9(p, split, acc, ci0 + wm * 32, co, lane);
+  if (do_bias) store_bias(p, split, co, h, bsum);
 }
 
 // ---- thin side: conv_in (3 -> C) and conv_out (C -> 3) ----------------------------------------------------------
@@ -969,27 +925,20 @@ __global__ void conv3x3_wgrad_thin_reduce_kernel(const float* __restrict__ slab,
 
 struct Plan { int v2, up, th, tiles_x, tiles_y, ntiles, nsplit, tiles_per_split, CinP, CoutP, ci_tiles, co_tiles; };
 
-// v2 (LDS-DMA) whenever both channel counts allow 16-byte pieces and the 128-wide co tile is not mostly padding
+// up (parity classes) for mode 5, v2 (LDS-DMA) for the other modes, whenever both channel counts allow 16-byte pieces; v2 also only
+// where the 128-wide co tile is not mostly padding.  Mode 5 with other channel counts runs the dense form, mode 2.
 Plan make_plan(int mode, int N, int Ho, int Wo, int Cin, int Cout) {
   Plan pl;
-  pl.up = mode == 5 && Cin % 4 == 0 && Cout % 4 == 0;
+  const bool c4 = Cin % 4 == 0 && Cout % 4 == 0;
+  pl.up = mode == 5 && c4;
+  pl.v2 = pl.up || (c4 && Cout > 64);
+  int bci = BC, bco = BC;
   if (pl.up) {   // tiles of 2 x 16 LOW-RES pixels (Ho, Wo are the output's: twice the input's)
-    pl.v2 = 1; pl.th = UP_TH;
-    pl.tiles_x = ceil_div(Wo / 2, TW); pl.tiles_y = ceil_div(Ho / 2, UP_TH);
-    pl.ntiles = pl.tiles_x * pl.tiles_y * N;
-    pl.CinP = ceil_div(Cin, UP_BC) * UP_BC; pl.CoutP = ceil_div(Cout, UP_BC) * UP_BC;
-    pl.ci_tiles = pl.CinP / UP_BC; pl.co_tiles = pl.CoutP / UP_BC;
-    int nsplit = ceil_div(256, pl.ci_tiles * pl.co_tiles);   // one 8-wave block per CU, one round: fewer slabs to write and sum
-    if (nsplit > pl.ntiles) nsplit = pl.ntiles;
-    if (nsplit < 1) nsplit = 1;
-    pl.tiles_per_split = ceil_div(pl.ntiles, nsplit);
-    pl.nsplit = ceil_div(pl.ntiles, pl.tiles_per_split);
-    return pl;
-  }
-  if (mode == 5) mode = 2;   // channel counts the DMA kernel cannot take: dense form
-  pl.v2 = Cin % 4 == 0 && Cout % 4 == 0 && Cout > 64;
-  const int bci = pl.v2 ? BCI2 : BC, bco = pl.v2 ? BCO2 : BC;
-  pl.th = pl.v2 ? (mode == 1 ? 2 : 4) : (mode == 1 ? 4 : 8);
+    bci = bco = UP_BC; pl.th = UP_TH;
+    Ho /= 2; Wo /= 2;
+  } else if (pl.v2) {
+    bci = BCI2; bco = BCO2; pl.th = mode == 1 ? 2 : 4;
+  } else pl.th = mode == 1 ? 4 : 8;
   pl.tiles_x = ceil_div(Wo, TW);
   pl.tiles_y = ceil_div(Ho, pl.th);
   pl.ntiles = pl.tiles_x * pl.tiles_y * N;
@@ -997,14 +946,19 @@ Plan make_plan(int mode, int N, int Ho, int Wo, int Cin, int Cout) {
   pl.CoutP = ceil_div(Cout, bco) * bco;
   pl.ci_tiles = pl.CinP / bci;
   pl.co_tiles = pl.CoutP / bco;
-  const int ctiles = pl.ci_tiles * pl.co_tiles;
-  int nsplit = ceil_div(pl.v2 ? 256 : 1024, ctiles);   // v2 runs one 8-wave block per CU, one round (512: -3..-10 %)
+  // the 8-wave kernels run one block per CU, one round: fewer slabs to write and sum (512: -3..-10 %)
+  int nsplit = ceil_div(pl.v2 ? 256 : 1024, pl.ci_tiles * pl.co_tiles);
   if (nsplit > pl.ntiles) nsplit = pl.ntiles;
   if (nsplit < 1) nsplit = 1;
   pl.tiles_per_split = ceil_div(pl.ntiles, nsplit);
   pl.nsplit = ceil_div(pl.ntiles, pl.tiles_per_split);
   return pl;
 }
+// slab taps and bias-slab rows of one split: the parity kernels keep 4 classes x 4 taps and one bias row per class
+int slab_taps(const Plan& pl) { return pl.up ? 16 : 9; }
+int bias_rows(const Plan& pl) { return pl.up ? 4 : 1; }
+// what store_taps relies on: one split's slab stays below 2^31 bytes
+bool slab_fits(const Plan& pl) { return (int64_t)slab_taps(pl) * pl.CinP * pl.CoutP * 4 < 0x80000000ll; }
 
 // thin-side kernel: stride-1 conv whose input or output has <= 3 channels (conv_in / conv_out)
 constexpr int THIN_BLOCKS = 1024, THIN_BIAS_BLOCKS = 256;
@@ -1026,15 +980,21 @@ ThinPlan make_thin_plan(int N, int Hi, int Cin, int Cout) {
   return tp;
 }
 
+// the block kernel of a tiled call: function, threads per block, dynamic LDS bytes
+struct BlockKernel { void (*fn)(WgradParams); int threads; size_t smem; };
 template <int MODE, int TH>
-size_t wgrad_smem_bytes() { return (size_t)(Halo<MODE, TH>::H * Halo<MODE, TH>::W + TH * TW) * BC * sizeof(float); }
-
-template <typename K>
-hipError_t launch_dyn(K kernel, dim3 grid, dim3 block, size_t smem, hipStream_t st, const WgradParams& p) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kernel, grid, block, smem, st, p);
-  return hipSuccess;
+BlockKernel v1_kernel() {
+  return {conv3x3_wgrad_kernel<MODE, TH>, 256, (size_t)(Halo<MODE, TH>::H * Halo<MODE, TH>::W + TH * TW) * BC * sizeof(float)};
+}
+template <int MODE, int TH>
+BlockKernel dma_kernel() { return {conv3x3_wgrad_dma_kernel<MODE, TH>, 512, (size_t)2 * DmaGeom<MODE, TH>::BUF_F * sizeof(float)}; }
+// mode: 0, 1 or 2 unless pl.up; split: the bf16-split form was chosen and serves this call
+BlockKernel pick_kernel(const Plan& pl, int mode, bool split) {
+  if (pl.up) return split ? BlockKernel{conv3x3_wgrad_up_split_kernel, 512, (size_t)2 * USP_BUF_B}
+                          : BlockKernel{conv3x3_wgrad_up_kernel, 512, (size_t)2 * UpGeom::BUF_F * sizeof(float)};
+  if (pl.v2 && mode == 1 && split) return {conv3x3_wgrad_down_split_kernel, 512, (size_t)2 * DSP_BUF_B};
+  if (pl.v2) return mode == 0 ? dma_kernel<0, 4>() : mode == 1 ? dma_kernel<1, 2>() : dma_kernel<2, 4>();
+  return mode == 0 ? v1_kernel<0, 8>() : mode == 1 ? v1_kernel<1, 4>() : v1_kernel<2, 8>();
 }
 
 // The bf16-split form serves the parity-class kernel (mode 5 with both channel counts multiples of 4: any other mode 5 call runs the
@@ -1074,8 +1034,7 @@ int odvae_conv3x3_wgrad_split_supported(int mode, int N, int Hi, int Wi, int Cin
 size_t odvae_conv3x3_wgrad_workspace_bytes(int mode, int N, int Ho, int Wo, int Cin, int Cout) {
   if (thin_applies(mode, Ho, Wo, Cin, Cout)) return thin_workspace_floats(Cin, Cout) * sizeof(float);
   const Plan pl = make_plan(mode, N, Ho, Wo, Cin, Cout);
-  if (pl.up) return ((size_t)pl.nsplit * 16 * pl.CinP * pl.CoutP + (size_t)pl.nsplit * 4 * pl.CoutP) * sizeof(float);
-  return ((size_t)pl.nsplit * 9 * pl.CinP * pl.CoutP + (size_t)pl.nsplit * pl.CoutP) * sizeof(float);
+  return ((size_t)pl.nsplit * slab_taps(pl) * pl.CinP * pl.CoutP + (size_t)pl.nsplit * bias_rows(pl) * pl.CoutP) * sizeof(float);
 }
 
 // Which kernel a call gets and how its pixels are split over blocks; host only, launches nothing.
@@ -1094,6 +1053,7 @@ int odvae_conv3x3_wgrad_plan(int mode, int N, int Hi, int Wi, int Cin, int Cout,
   }
   const int Ho = mode == 0 ? Hi : mode == 1 ? Hi / 2 : 2 * Hi, Wo = mode == 0 ? Wi : mode == 1 ? Wi / 2 : 2 * Wi;
   const Plan pl = make_plan(mode, N, Ho, Wo, Cin, Cout);
+  ODVAE_CHECK_ARG(slab_fits(pl), "conv3x3_wgrad_plan: one split's slab must stay below 2 GiB");
   const int v[8] = {pl.up ? 3 : pl.v2 ? 2 : 1, pl.ntiles, pl.nsplit, pl.tiles_per_split, pl.ci_tiles, pl.co_tiles, pl.th,
                     (mode == 5 && !pl.up) ? 2 : mode};
   for (int i = 0; i < 8; ++i) out[i] = v[i];
@@ -1113,13 +1073,15 @@ int odvae_conv3x3_wgrad_f32(int mode, const float* x, const float* dy, int N, in
   ODVAE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0, "conv3x3_wgrad: x/dy must be 16-byte aligned");
   ODVAE_CHECK_ARG((int64_t)Hi * Wi * Cin * 4 < 0x7FFFFFF0ll && (int64_t)Ho * Wo * Cout * 4 < 0x7FFFFFF0ll, "conv3x3_wgrad: one image must stay below 2 GiB");
   const Plan pl = make_plan(mode, N, Ho, Wo, Cin, Cout);
+  const bool thin = thin_applies(mode, Hi, Wi, Cin, Cout);
+  ODVAE_CHECK_ARG(thin || slab_fits(pl), "conv3x3_wgrad: one split's slab must stay below 2 GiB");
   const size_t need = odvae_conv3x3_wgrad_workspace_bytes(mode, N, Ho, Wo, Cin, Cout);
   if (!workspace || workspace_bytes < need) {
     odvae_set_error("conv3x3_wgrad: needs %zu workspace bytes, got %zu", need, workspace_bytes);
     return ODVAE_ERR_WORKSPACE;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (thin_applies(mode, Hi, Wi, Cin, Cout)) {
+  if (thin) {
     ThinParams t;
     const bool in_thin = Cin <= 3;   // conv_in: big = dy, small = x; conv_out: big = x, small = dy
     t.big = in_thin ? dy : x; t.small = in_thin ? x : dy;
@@ -1144,49 +1106,26 @@ int odvae_conv3x3_wgrad_f32(int mode, const float* x, const float* dy, int N, in
   WgradParams p;
   p.x = x; p.dy = dy;
   p.slab = static_cast<float*>(workspace);
-  p.bslab = dbias ? p.slab + (size_t)pl.nsplit * (pl.up ? 16 : 9) * pl.CinP * pl.CoutP : nullptr;
+  p.bslab = dbias ? p.slab + (size_t)pl.nsplit * slab_taps(pl) * pl.CinP * pl.CoutP : nullptr;
   if (mode == 5 && !pl.up) mode = 2;
   p.N = N; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout;
   p.CinP = pl.CinP; p.CoutP = pl.CoutP;
   p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.ntiles = pl.ntiles;
   p.tiles_per_split = pl.tiles_per_split; p.ci_tiles = pl.ci_tiles;
-  dim3 grid(pl.nsplit, pl.ci_tiles * pl.co_tiles);
-  hipError_t e = hipSuccess;
   const bool split = g_direct_form != 0 && direct_split_supported(mode, Cin, Cout) &&
                      (g_direct_form == 1 || direct_split_by_shape(pl, Cin, Cout));
-  if (pl.up) {
-    if (split) e = launch_dyn(conv3x3_wgrad_up_split_kernel, grid, dim3(512), (size_t)2 * USP_BUF_B, st, p);
-    else e = launch_dyn(conv3x3_wgrad_up_kernel, grid, dim3(512), (size_t)2 * UpGeom::BUF_F * sizeof(float), st, p);
-    if (e != hipSuccess) {
-      odvae_set_error("conv3x3_wgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return ODVAE_ERR_HIP;
-    }
-    ODVAE_LAUNCH_CHECK("conv3x3_wgrad up");
-    const int64_t total = (int64_t)9 * pl.CinP * pl.CoutP + pl.CoutP;
-    hipLaunchKernelGGL(conv3x3_wgrad_up_reduce_kernel, dim3((int)std::min<int64_t>(ceil_div64(total, 256), 4096)), dim3(256), 0, st,
-                       p.slab, p.bslab, pl.nsplit, Cin, Cout, pl.CinP, pl.CoutP, dw, dbias);
-    ODVAE_LAUNCH_CHECK("conv3x3_wgrad up reduce");
-    return ODVAE_OK;
-  }
-  if (pl.v2) {
-    if (mode == 0)      e = launch_dyn(conv3x3_wgrad_dma_kernel<0, 4>, grid, dim3(512), (size_t)2 * DmaGeom<0, 4>::BUF_F * sizeof(float), st, p);
-    else if (mode == 1 && split) e = launch_dyn(conv3x3_wgrad_down_split_kernel, grid, dim3(512), (size_t)2 * DSP_BUF_B, st, p);
-    else if (mode == 1) e = launch_dyn(conv3x3_wgrad_dma_kernel<1, 2>, grid, dim3(512), (size_t)2 * DmaGeom<1, 2>::BUF_F * sizeof(float), st, p);
-    else                e = launch_dyn(conv3x3_wgrad_dma_kernel<2, 4>, grid, dim3(512), (size_t)2 * DmaGeom<2, 4>::BUF_F * sizeof(float), st, p);
-  } else {
-    if (mode == 0)      e = launch_dyn(conv3x3_wgrad_kernel<0, 8>, grid, dim3(256), wgrad_smem_bytes<0, 8>(), st, p);
-    else if (mode == 1) e = launch_dyn(conv3x3_wgrad_kernel<1, 4>, grid, dim3(256), wgrad_smem_bytes<1, 4>(), st, p);
-    else                e = launch_dyn(conv3x3_wgrad_kernel<2, 8>, grid, dim3(256), wgrad_smem_bytes<2, 8>(), st, p);
-  }
+  const BlockKernel k = pick_kernel(pl, mode, split);
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.smem);
   if (e != hipSuccess) {
     odvae_set_error("conv3x3_wgrad: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
     return ODVAE_ERR_HIP;
   }
+  hipLaunchKernelGGL(k.fn, dim3(pl.nsplit, pl.ci_tiles * pl.co_tiles), dim3(k.threads), k.smem, st, p);
   ODVAE_LAUNCH_CHECK("conv3x3_wgrad");
   const int64_t total = (int64_t)9 * pl.CinP * pl.CoutP + pl.CoutP;
-  const int blocks = (int)std::min<int64_t>(ceil_div64(total, 256), 4096);
-  hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st,
-                     p.slab, p.bslab, pl.nsplit, Cin, Cout, pl.CinP, pl.CoutP, dw, dbias);
+  hipLaunchKernelGGL(pl.up ? conv3x3_wgrad_up_reduce_kernel : conv3x3_wgrad_reduce_kernel,
+                     dim3((int)std::min<int64_t>(ceil_div64(total, 256), 4096)), dim3(256), 0, st,
+                     p.slab, p.bslab, pl.nsplit, bias_rows(pl), Cin, Cout, pl.CinP, pl.CoutP, dw, dbias);
   ODVAE_LAUNCH_CHECK("conv3x3_wgrad reduce");
   return ODVAE_OK;
 }

@@ -415,8 +415,7 @@ __device__ __forceinline__ void wgs_body(const WgwParams& p, char* smem, const i
   auto half_phase = [&](auto pcc, auto scc, auto fetchc) {
     constexpr int PC = decltype(pcc)::value, SC = decltype(scc)::value;
     constexpr bool FETCH = decltype(fetchc)::value;
-    constexpr int HI = 0, MID = 1, LO = 2;
-    constexpr int ORDER[6][2] = {{LO, HI}, {HI, LO}, {MID, MID}, {MID, HI}, {HI, MID}, {HI, HI}};   // smallest first
+    using namespace split3;      // HI, MID, LO, ORDER
     bf16x8 a[3], b[2][3];
     if constexpr (PC >= 0) {
 #pragma unroll
@@ -461,7 +460,7 @@ __device__ __forceinline__ void wgs_body(const WgwParams& p, char* smem, const i
       if constexpr (FETCH) fetch_piece(i);
       if constexpr (PC >= 0) {
         const int o = i >> 1, nt = i & 1;
-        acc[PC][nt] = mfma_bf16(a[ORDER[o][0]], b[nt][ORDER[o][1]], acc[PC][nt]);
+        acc[PC][nt] = mfma_bf16(a[ORDER.p[o][0]], b[nt][ORDER.p[o][1]], acc[PC][nt]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }

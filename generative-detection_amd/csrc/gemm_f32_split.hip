@@ -26,7 +26,7 @@ using namespace gemm_tile;
 constexpr unsigned PLANE_B = BM * BK * 2;        // 8 192: one bf16 plane of one operand tile
 constexpr unsigned OPER_B = 3 * PLANE_B;         // hi, mid, lo
 constexpr unsigned OOB = 0x7FFFFFF0u;
-constexpr int HI = 0, MID = 1, LO = 2;
+using namespace split3;      // HI, MID, LO, ORDER
 
 // byte of (row, 16-byte slot) inside one plane.  The XOR pattern f(row) = bit 2 of the row | (bit 1 ^ bit 3) << 1 is the one (found by
 // enumeration over the lane groups of MI355X_MICROARCH.md, LDS) that serves both sides: the sixteen rows of every ds_read_b128 lane
@@ -178,13 +178,12 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(GemmParams p) {
           a[t][q] = frag_from_u32x4(lds_ld128(adrA[kk] + t * 2048u + q * PLANE_B));
           b[t][q] = frag_from_u32x4(lds_ld128(adrB[kk] + t * 2048u + q * PLANE_B));
         }
-      constexpr int ORDER[6][2] = {{LO, HI}, {HI, LO}, {MID, MID}, {MID, HI}, {HI, MID}, {HI, HI}};   // smallest first
 #pragma unroll
       for (int o = 0; o < 6; ++o)
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-          for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = mfma_bf16(a[mt][ORDER[o][0]], b[nt][ORDER[o][1]], acc[mt][nt]);
+          for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = mfma_bf16(a[mt][ORDER.p[o][0]], b[nt][ORDER.p[o][1]], acc[mt][nt]);
     }
   };
   fa.template load<true>(0);

@@ -122,6 +122,26 @@ def test_argument_contract(hip_lib, kind):
         run.assert_untouched()
 
 
+def test_slab_of_two_gib_is_refused(hip_lib):
+    """One split's slab is addressed with 32-bit byte offsets: at 2^31 bytes the call is an argument error of its own, one channel tile
+    below it is an ordinary call (here: one without workspace).  Neither call can launch anything."""
+    from odvae_amd import lib
+    cin = 4096
+    x = torch.zeros(1, 1, 1, cin, device=DEV)
+    dw = torch.full((64,), float("nan"), device=DEV)
+    for cout, code in ((8192, ERR_ARG), (8128, ERR_WORKSPACE)):      # parity slab: 16 * CinP * CoutP * 4 = 2^31, and 2^31 - 2^24
+        dy = torch.zeros(1, 2, 2, cout, device=DEV)
+        assert x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0
+        hip_lib.odvae_conv3x3_wgrad_f32(5, None, None, 1, 1, 1, 1, 1, 1, 1, None, None, None, 0, None)   # leaves another message
+        stale = hip_lib.odvae_last_error()
+        assert hip_lib.odvae_conv3x3_wgrad_f32(5, x.data_ptr(), dy.data_ptr(), 1, 1, 1, cin, 2, 2, cout, dw.data_ptr(), None, None, 0,
+                                               lib.stream_ptr()) == code, cout
+        msg = hip_lib.odvae_last_error()
+        assert msg and msg != stale, "Cout %d: no message of its own" % cout
+    torch.cuda.synchronize()
+    assert torch.isnan(dw).all().item(), "a refused call wrote dw"
+
+
 @pytest.mark.parametrize("kind", W.KINDS)
 def test_random_normal_operands_stay_at_f32_precision(hip_lib, kind):
     from test_ops_gpu import ref_conv

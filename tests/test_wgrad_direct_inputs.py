@@ -108,3 +108,8 @@ def test_plan_query_refuses_what_the_launcher_refuses(lib):
         assert L.odvae_last_error()
         assert list(out) == [-7] * 8
     assert L.odvae_conv3x3_wgrad_plan(0, 1, 8, 16, 64, 64, None) == 1
+    # one split's slab of the parity kernel, 16 * CinP * CoutP * 4 bytes: 2^31 at 4096 x 8192 channels, one channel tile less below it
+    assert L.odvae_conv3x3_wgrad_plan(5, 1, 1, 1, 4096, 8192, out) == 1
+    assert "slab" in L.odvae_last_error().decode() and list(out) == [-7] * 8
+    assert L.odvae_conv3x3_wgrad_plan(5, 1, 1, 1, 4096, 8128, out) == 0
+    assert list(out)[0] == 3

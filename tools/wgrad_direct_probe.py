@@ -1,19 +1,24 @@
 """Timing of the direct 3x3 weight-gradient kernels of the Upsample (mode 5, parity classes) and Downsample (mode 1) convs on the layer
 shapes of the headline step: per shape ten launches behind device events, after 30 warm-up launches on a full queue, of the f32 MFMA form
 and of the bf16-split form (odvae_conv3x3_wgrad_select).  A library without the selector (a build of an earlier commit, in whose tree this
-file can be dropped) is timed as "parent".  `pmc`: six launches per form of one shape per mode, for a rocprofv3 --pmc pass (a run of its
-own, no tracing).  python tools/wgrad_direct_probe.py [time|pmc]"""
+file can be dropped) is timed as "parent".  `time all` adds one shape per kernel kind the step does not reach (v2 in modes 0 and 2, v1 in
+modes 0 and 1, mode 5 falling back to v1).  `pmc`: six launches per form of one shape per mode, for a rocprofv3 --pmc pass (a run of its
+own, no tracing).  ODVAE_PROBE_LIB names another build of the library (A/B runs).  python tools/wgrad_direct_probe.py [time [all]|pmc]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from odvae_amd import lib as _lib, ops
 
 dev = "cuda:0"
+if os.environ.get("ODVAE_PROBE_LIB"):      # A/B builds of the library (tools/bin/, not shipped)
+    _lib.LIB_PATH = os.environ["ODVAE_PROBE_LIB"]
 L = _lib.load()
 HAS_SELECT = hasattr(L, "odvae_conv3x3_wgrad_select")
 
 # (mode, B, Cin, Cout, INPUT H = W): the four Upsample convs and the four Downsample convs of bench.py's step (256^2, B = 32)
 STEP_SHAPES = [(5, 32, 512, 512, 16), (5, 32, 256, 256, 32), (5, 32, 256, 256, 64), (5, 32, 128, 128, 128),
                (1, 32, 128, 128, 256), (1, 32, 128, 128, 128), (1, 32, 256, 256, 64), (1, 32, 256, 256, 32)]
+# the kinds the step does not reach: v2 mode 0, v2 mode 2, v1 (Cout <= 64) modes 0 and 1, mode 5 with a channel count that is no multiple of 4
+OTHER_KINDS = [(0, 8, 128, 128, 128), (2, 8, 128, 128, 64), (0, 8, 128, 64, 128), (1, 8, 128, 64, 128), (5, 8, 128, 126, 64)]
 
 
 def run(mode, x, dy, cin, cout):
@@ -37,9 +42,9 @@ def launches_ms(fn, n=10):
     return ts
 
 
-def time_():
-    for (mode, b, cin, cout, hi) in STEP_SHAPES:
-        ho = 2 * hi if mode == 5 else hi // 2
+def time_(shapes):
+    for (mode, b, cin, cout, hi) in shapes:
+        ho = hi if mode == 0 else hi // 2 if mode == 1 else 2 * hi
         x = torch.randn(b, hi, hi, cin, device=dev)
         dy = torch.randn(b, ho, ho, cout, device=dev)
         gf = 2.0 * 9 * cin * cout * b * ho * ho / 1e9
@@ -85,4 +90,4 @@ def pmc():
 
 
 if __name__ == "__main__":
-    pmc() if len(sys.argv) > 1 and sys.argv[1] == "pmc" else time_()
+    pmc() if len(sys.argv) > 1 and sys.argv[1] == "pmc" else time_(STEP_SHAPES + (OTHER_KINDS if "all" in sys.argv[2:] else []))
