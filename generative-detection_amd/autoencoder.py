@@ -16,6 +16,7 @@ from . import ops
 from .config import instantiate_from_config
 from .distributions import DiagonalGaussianDistribution
 from .ema import LitEma
+from .latent_noise import CallCounter, make_draw, with_stream
 from .lightning import LightningModule
 from .modules import Conv1x1, Decoder, Encoder
 from .optim import make_adam
@@ -38,7 +39,9 @@ class AutoencoderKL(LightningModule):
     """[UPSTREAM] ldm.models.autoencoder.AutoencoderKL (the plain KL autoencoder BASELINE.json names)."""
 
     def __init__(self, ddconfig, lossconfig, embed_dim, ckpt_path=None, ignore_keys=[], image_key="image",
-                 colorize_nlabels=None, monitor=None, ema_decay=None, learn_logvar=False):
+                 colorize_nlabels=None, monitor=None, ema_decay=None, learn_logvar=False, device_noise=None):
+        """device_noise: an extension (neither upstream nor the reference has it).  None = the noise is drawn with the host RNG and
+        uploaded, as the reference does; an integer is the seed of the device-side draws (latent_noise.py): no host RNG, no upload."""
         super().__init__()
         self.learn_logvar = learn_logvar
         self.image_key = image_key
@@ -58,11 +61,36 @@ class AutoencoderKL(LightningModule):
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
         # test hook: {"posterior_eps", "samples_eps"} tensors replace the host RNG draws of forward and log_images
         self.injected_noise = None
+        self._init_device_noise(device_noise)
         self._init_ema(ema_decay)
 
     def _noise(self, key):
         noise = getattr(self, "injected_noise", None)
         return None if noise is None else noise.get(key)
+
+    # ---- device-side noise (latent_noise.py: the draw; csrc/latent_noise.hip: the kernels) ------------------------------------------
+    def _init_device_noise(self, device_noise):
+        self.device_noise = None if device_noise is None else int(device_noise)
+        self.noise_rank = 0      # the key's rank: trainer.Trainer sets it where it hands out the process group
+        self._noise_calls = CallCounter()
+        self._last_draw = None
+
+    def _next_draw(self):
+        """The draw descriptor of one forward (None with device_noise off): a pure function of seed, rank, global_step, training and the
+        number of forwards since the last two changed -- nothing of it is in the state_dict, and a resumed run draws what the
+        uninterrupted one drew."""
+        if self.device_noise is None:
+            return None
+        call = self._noise_calls.next(self.global_step, self.training)
+        self._last_draw = make_draw(self.device_noise, self.noise_rank, self.global_step, self.training, call)
+        return self._last_draw
+
+    def _drawn(self, key, shape, draw, stream, kind=0, p=0.0):
+        """injected_noise[key] where a test set it, else the stream's elements from the device fill ([N, C, H, W]: in NHWC order)"""
+        t = self._noise(key)
+        if t is not None:
+            return _lib.upload(t, self.device)
+        return ops.noise_fill(shape, with_stream(draw, stream), self.device, kind=kind, p=p, nhwc=len(shape) == 4)
 
     # ---- exponential moving average of the weights ([UPSTREAM] the stable-diffusion revision of this class; ema.LitEma) -------------
     def _init_ema(self, ema_decay):
@@ -153,8 +181,18 @@ class AutoencoderKL(LightningModule):
 
     def forward(self, input, sample_posterior=True):
         posterior = self.encode(input)
-        z = posterior.sample(self._noise("posterior_eps")) if sample_posterior else posterior.mode()
+        draw = self._next_draw()
+        z = posterior.sample(self._noise("posterior_eps"), draw=draw) if sample_posterior else posterior.mode()
         return self.decode(z), posterior
+
+    def _samples_eps(self, shape):
+        """The N(0, 1) latent that log_images decodes as `samples`: injected, stream 4 of the last forward's draw, or a host draw"""
+        eps = self._noise("samples_eps")
+        if eps is None and self.device_noise is not None:
+            return ops.noise_fill(shape, with_stream(self._last_draw, "samples_eps"), self.device)
+        if eps is None:
+            eps = torch.randn(shape)      # drawn on the host, as DiagonalGaussianDistribution.sample does
+        return _lib.upload(eps.float(), self.device)
 
     def get_input(self, batch, k):
         """[N, H, W, C] (or [N, H, W]) of the batch -> f32 NCHW on the model's device"""
@@ -207,10 +245,7 @@ class AutoencoderKL(LightningModule):
             if x.shape[1] > 3:      # more than three channels (label maps): both sides go through the fixed `colorize` projection
                 assert xrec.shape[1] == x.shape[1], "reconstruction has %d channels, input %d" % (xrec.shape[1], x.shape[1])
                 x, xrec = self.to_rgb(x), self.to_rgb(xrec)
-            eps = self._noise("samples_eps")
-            if eps is None:
-                eps = torch.randn(tuple(posterior.mean.shape))      # drawn on the host, as DiagonalGaussianDistribution.sample does
-            log["samples"] = self.decode(_lib.upload(eps.float(), self.device))
+            log["samples"] = self.decode(self._samples_eps(tuple(posterior.mean.shape)))
             log["reconstructions"] = xrec
             if log_ema or self.use_ema:
                 with self.ema_scope():
@@ -218,10 +253,7 @@ class AutoencoderKL(LightningModule):
                     if x_in.shape[1] > 3:
                         assert xrec_ema.shape[1] == x_in.shape[1]
                         xrec_ema = self.to_rgb(xrec_ema)
-                    eps = self._noise("samples_eps")
-                    if eps is None:
-                        eps = torch.randn(tuple(posterior_ema.mean.shape))      # the shape of the EMA pass's posterior
-                    log["samples_ema"] = self.decode(_lib.upload(eps.float(), self.device))
+                    log["samples_ema"] = self.decode(self._samples_eps(tuple(posterior_ema.mean.shape)))      # the shape of the EMA pass's posterior
                     log["reconstructions_ema"] = xrec_ema
         log["inputs"] = x
         return log
@@ -260,9 +292,11 @@ class PoseAutoencoder(AutoencoderKL):
                  colorize_nlabels=None, monitor=None, activation="relu", feat_dims=[16, 16, 16],
                  pose_decoder_config=None, pose_encoder_config=None, dropout_prob_init=1.0, dropout_prob_final=0.7,
                  dropout_warmup_steps=5000, pose_conditioned_generation_steps=10000, add_noise_to_z_obj=True,
-                 train_on_yaw=True, ema_decay=None, learn_logvar=False):
+                 train_on_yaw=True, ema_decay=None, learn_logvar=False, device_noise=None):
         """ema_decay, learn_logvar: an extension (the reference's PoseAutoencoder has neither): the two keys of the stable-diffusion
-        revision of AutoencoderKL, off by default -- None / False reproduce the reference."""
+        revision of AutoencoderKL, off by default -- None / False reproduce the reference.
+        device_noise: an extension too.  None = posterior_eps, the dropout mask, z_noise and bbox_eps come from the host RNG, as in the
+        reference; an integer seeds the device-side draws and the latent stage runs as one launch each way (_forward_device_noise)."""
         LightningModule.__init__(self)  # the reference skips AutoencoderKL.__init__ as well (:66)
         self.learn_logvar = learn_logvar
         self.encoder_pretrain_steps = lossconfig["params"]["encoder_pretrain_steps"]
@@ -301,6 +335,7 @@ class PoseAutoencoder(AutoencoderKL):
         self.feat_dims = feat_dims
         # test hook: {"posterior_eps", "dropout_mask", "z_noise", "bbox_eps"} tensors replace the host RNG draws
         self.injected_noise = None
+        self._init_device_noise(device_noise)
         self._init_ema(ema_decay)
 
     # ---- pose head (:126-174) ---------------------------------------------------------------------------------
@@ -309,12 +344,12 @@ class PoseAutoencoder(AutoencoderKL):
         bbox_moments = z[..., :2 * BBOX_DIM].to(self.device)
         return DiagonalGaussianDistribution(bbox_moments), c_pred
 
-    def _decode_pose(self, x, sample_posterior=True):
+    def _decode_pose(self, x, sample_posterior=True, draw=None):
         flat = x.reshape(x.size(0), -1)  # logical NCHW order, as x.view(B,-1) in the reference
         z = self.pose_decoder(flat)
         bbox_posterior, c_pred = self._decode_pose_to_distribution(z)
         if sample_posterior:
-            bbox_pred = bbox_posterior.sample(self._noise("bbox_eps"))
+            bbox_pred = bbox_posterior.sample(self._noise("bbox_eps"), draw=None if draw is None else with_stream(draw, "bbox_eps"))
         else:
             bbox_pred = bbox_posterior.mode()
         return torch.cat([bbox_pred, c_pred], dim=-1), bbox_posterior
@@ -355,8 +390,42 @@ class PoseAutoencoder(AutoencoderKL):
                 mask = (torch.rand(z.shape) >= p).float() / (1.0 - p)
         return ops.latent_combine(z, _lib.upload(mask, z.device), None)
 
+    def _latent_device_noise(self, posterior_obj, draw, sample_posterior, enc_pose):
+        """z_obj -> dropout -> + noise -> + enc_pose with the draws of `draw`: one launch (ops.latent_stage).  Where a test injected one of
+        the three tensors, the chain of launches the host path runs, fed the injected tensors and the fill's for the rest."""
+        p = min(float(self.dropout_prob), 1.0)
+        if all(self._noise(k) is None for k in ("posterior_eps", "dropout_mask", "z_noise")):
+            return ops.latent_stage(posterior_obj.parameters, draw, add=enc_pose, sample=sample_posterior, dropout_p=p,
+                                    noise=self.add_noise_to_z_obj)
+        n, c2, h, w = posterior_obj.parameters.shape
+        shape = (n, c2 // 2, h, w)
+        z = posterior_obj.sample(self._drawn("posterior_eps", shape, draw, "posterior_eps")) if sample_posterior else posterior_obj.mode()
+        if p > 0:
+            z = ops.latent_combine(z, self._drawn("dropout_mask", shape, draw, "dropout", kind=1, p=p), None)
+        if self.add_noise_to_z_obj:
+            z = ops.latent_combine(z, None, self._drawn("z_noise", shape, draw, "z_noise"))
+        return z if enc_pose is None else ops.latent_combine(z, None, enc_pose)
+
+    def _forward_device_noise(self, posterior_obj, pose_feat, input_im, sample_posterior):
+        """forward with device_noise on: no torch.randn / torch.rand, no upload.  The pose head runs first, so that enc_pose is there
+        when the one latent launch wants it as `add` (neither depends on the other's draws)."""
+        draw = self._next_draw()
+        self.dropout_prob = self._get_dropout_prob()
+        dec_pose, bbox_posterior = self._decode_pose(pose_feat, sample_posterior, draw=draw)
+        if self.global_step < self.encoder_pretrain_steps:      # z_obj feeds nothing here: not computed
+            n, _, h, w = input_im.shape
+            dec_obj = torch.zeros((n, h, w, input_im.shape[1]), device=self.device).permute(0, 3, 1, 2)
+        else:
+            enc_pose = self._encode_pose(dec_pose)
+            zshape = (posterior_obj.parameters.shape[0], posterior_obj.parameters.shape[1] // 2) + tuple(posterior_obj.parameters.shape[2:])
+            assert zshape == tuple(enc_pose.shape), f"z_obj shape: {zshape}, enc_pose shape: {enc_pose.shape}"
+            dec_obj = self.decode(self._latent_device_noise(posterior_obj, draw, sample_posterior, enc_pose))
+        return dec_obj, dec_pose, posterior_obj, bbox_posterior
+
     def forward(self, input_im, sample_posterior=True):
         posterior_obj, pose_feat = self.encode(input_im)
+        if self.device_noise is not None:
+            return self._forward_device_noise(posterior_obj, pose_feat, input_im, sample_posterior)
         z_obj = posterior_obj.sample(self._noise("posterior_eps")) if sample_posterior else posterior_obj.mode()
         self.dropout_prob = self._get_dropout_prob()
         if self.dropout_prob > 0:
@@ -469,6 +538,10 @@ class PoseAutoencoder(AutoencoderKL):
         return out.to(self.device)
 
     def _perturbed_pose_forward(self, posterior_obj, dec_pose, batch, sample_posterior=True):
+        draw = self._next_draw()      # a call of its own: a second sample of the same posterior
+        if draw is not None and sample_posterior and self._noise("posterior_eps_perturbed") is None:
+            enc_pose = self._encode_pose(self._perturb_poses(batch, dec_pose))
+            return self.decode(ops.latent_stage(posterior_obj.parameters, draw, add=enc_pose))
         z_obj = posterior_obj.sample(self._noise("posterior_eps_perturbed")) if sample_posterior else posterior_obj.mode()
         enc_pose = self._encode_pose(self._perturb_poses(batch, dec_pose))
         return self.decode(ops.latent_combine(z_obj, None, enc_pose))

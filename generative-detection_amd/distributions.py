@@ -49,10 +49,16 @@ class DiagonalGaussianDistribution(object):
             return torch.zeros_like(self.mean)
         return torch.exp(self.logvar)
 
-    def sample(self, eps=None):
+    def sample(self, eps=None, draw=None):
         """mean + std * eps.  eps defaults to the reference's host-side torch.randn draw moved to the device;
-        tests inject it (bit-level RNG parity with a CPU draw is otherwise impossible)."""
+        tests inject it (bit-level RNG parity with a CPU draw is otherwise impossible).
+        draw (a latent_noise.Draw: key, step word, tag), when no eps is given: eps is made on the device from those words -- 4-d HIP
+        moments in the fused latent stage (ops.latent_stage: no eps tensor at all), 2-d moments by the fill, with their torch arithmetic."""
         shape = (self.parameters.shape[0], self.parameters.shape[1] // 2) + tuple(self.parameters.shape[2:])
+        if eps is None and draw is not None:
+            if self._hip and not self.deterministic:
+                return ops.latent_stage(self.parameters, draw)
+            eps = ops.noise_fill(shape, draw, self.parameters.device)
         if eps is None:
             eps = torch.randn(shape)
         eps = _lib.upload(eps, self.parameters.device)

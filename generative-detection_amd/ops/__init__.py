@@ -115,7 +115,7 @@ from .resample import (  # noqa: E402
     upsample2x)
 from .elementwise import (  # noqa: E402
     _Tanh, tanh, rescale_minmax, _GaussianSample, _GaussianKL, gaussian_sample, gaussian_kl, _L1MaskedSum, l1_masked_sum, nhwc_to_nchw,
-    _MulMask, mul_mask, _LatentCombine, latent_combine, _flat_f32, ema_tick, ema_update, ema_swap, _PoseLosses, pose_losses, LINEAR_ACTS, _LinearAct, linear_act)
+    _MulMask, mul_mask, _LatentCombine, latent_combine, LATENT_SAMPLE, LATENT_DROPOUT, LATENT_NOISE, noise_fill, _LatentStage, latent_stage, _flat_f32, ema_tick, ema_update, ema_swap, _PoseLosses, pose_losses, LINEAR_ACTS, _LinearAct, linear_act)
 from .patchgan import (  # noqa: E402
     _conv4x4_out, _Conv4x4, _conv4x4_i_raw, _check_pack_current, _Conv4x4I, conv4x4, _BatchNormLReLU, batchnorm_lrelu, _ActNormLReLU, actnorm_init, actnorm_lrelu, _LeakyReLU,
     leaky_relu, _GanLogitTerms, gan_logit_terms, _conv4x4_b_raw, _Conv4x4B, conv4x4_bf16, _gather_f64, _SyncBatchNormLReLU, _sync_group)

@@ -227,6 +227,70 @@ def latent_combine(z, mask=None, add=None):
 
 
 # ------------------------------------------------------------------------------------------------------
+# device-side latent noise (latent_noise.hip; latent_noise.py is the draw's numpy mirror)
+# ------------------------------------------------------------------------------------------------------
+LATENT_SAMPLE, LATENT_DROPOUT, LATENT_NOISE = 1, 2, 4      # flags of odvae_latent_stage_f32
+
+
+def noise_fill(shape, draw, device, kind=0, p=0.0, first=0, nhwc=False):
+    """A new f32 tensor of `shape` (contiguous: element = flat index) holding elements first .. of the stream in draw.tag: kind 0 =
+    standard normals, 1 = dropout multipliers of probability p.  draw = latent_noise.Draw(key, step, tag); no host RNG, no upload.
+    nhwc: shape is a logical [N, C, H, W] and the tensor comes in channels_last memory -- element = flat NHWC index, the latent's order."""
+    L = _L()
+    if nhwc:
+        n, c, h, w = shape
+        return noise_fill((n, h, w, c), draw, device, kind=kind, p=p, first=first).permute(0, 3, 1, 2)
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    _lib.require_device(out)
+    if out.numel():
+        _lib.check(L.odvae_noise_fill_f32(out.data_ptr(), out.numel(), int(first), draw.key, draw.step, draw.tag, int(kind), float(p),
+                                          _lib.stream_ptr()), "noise_fill")
+    return out
+
+
+class _LatentStage(Function):
+    """z = ((mean + std * eps) * m + noise) + add in one launch; eps, m and noise are streams 0, 1, 2 of `draw`, made in registers.
+    The backward keeps the moments alone and draws eps and m again; the gradient of `add` is dz itself."""
+
+    @staticmethod
+    def forward(ctx, moments, add, draw, flags, p):
+        L = _L()
+        moments = _cl(moments)
+        a = _cl(add) if add is not None else None
+        n, c2, h, w = moments.shape
+        cz = c2 // 2
+        if a is not None and tuple(a.shape) != (n, cz, h, w):
+            raise ValueError("latent_stage: add %s does not have the latent's shape %s" % (tuple(a.shape), (n, cz, h, w)))
+        z = _new_cl(n, cz, h, w, moments)
+        _lib.check(L.odvae_latent_stage_f32(moments.data_ptr(), _lib.ptr(a), z.data_ptr(), n, h * w, cz, draw.key, draw.step, draw.tag,
+                                            flags, p, _lib.stream_ptr()), "latent_stage")
+        ctx.save_for_backward(moments)
+        ctx.draw, ctx.flags, ctx.p, ctx.has_add = draw, flags, p, add is not None
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        L = _L()
+        (moments,) = ctx.saved_tensors
+        dz = _cl(dz)
+        dm = None
+        if ctx.needs_input_grad[0]:
+            n, c2, h, w = moments.shape
+            dm = _new_cl(n, c2, h, w, moments)
+            _lib.check(L.odvae_latent_stage_bwd_f32(moments.data_ptr(), dz.data_ptr(), dm.data_ptr(), n, h * w, c2 // 2, ctx.draw.key,
+                                                    ctx.draw.step, ctx.draw.tag, ctx.flags, ctx.p, _lib.stream_ptr()), "latent_stage_bwd")
+        return dm, (dz if ctx.has_add and ctx.needs_input_grad[1] else None), None, None, None
+
+
+def latent_stage(moments, draw, add=None, sample=True, dropout_p=0.0, noise=False):
+    """The latent stage of one forward: sample (or mode), dropout of probability dropout_p (0 = off, >= 1 zeroes), + N(0,1) noise, + add.
+    draw = latent_noise.Draw of the forward (stream 0's tag: the kernel adds the stream ids)."""
+    p = min(float(dropout_p), 1.0)
+    flags = (LATENT_SAMPLE if sample else 0) | (LATENT_DROPOUT if p > 0.0 else 0) | (LATENT_NOISE if noise else 0)
+    return _LatentStage.apply(moments, add, draw, flags, max(p, 0.0))
+
+
+# ------------------------------------------------------------------------------------------------------
 # exponential moving average of the weights (ema.LitEma): raw launches on flat f32 storage, no autograd
 # ------------------------------------------------------------------------------------------------------
 def _flat_f32(*tensors):

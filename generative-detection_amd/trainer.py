@@ -119,6 +119,8 @@ class Trainer:
             self.reducers = [GradReducer(o, process_group=process_group, bucket_mb=bucket_mb, prescaled=True, comm_dtype=comm_dtype, f32_accumulate=comm_f32_accumulate)
                              for o in opts]
             self.reducers[0].broadcast_parameters(model)
+            if hasattr(model, "noise_rank"):      # device_noise: the rank goes into the Philox key, so the ranks draw different noise
+                model.noise_rank = torch.distributed.get_rank(process_group)
             if ema is not None:
                 # rank 0's average everywhere, once, as whole arenas: from here on every rank computes the same bits from the same
                 # parameters, with no communication

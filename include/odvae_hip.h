@@ -361,6 +361,23 @@ int odvae_mul_mask_f32(const float* x, const float* mask, float* y, int64_t npix
 /* out = z*mask + add, mask/add may be NULL (dropout on z_obj, +noise, +enc_pose: src/models/autoencoder.py:233-253) */
 int odvae_latent_combine_f32(const float* z, const float* mask, const float* add, float* out, int64_t n, void* stream);
 
+/* ---- latent_noise.hip: the latent stage's draws made on the device (model.params.device_noise; csrc/latent_noise.h defines the draw) ----
+ * A draw is a pure function of (seed, step_word, tag, element index): seed = the 64-bit Philox key (the model's seed plus its rank's
+ * offset), step_word = lo32(global_step), tag = stream << 29 | training << 28 | call (each a 32-bit word in a uint64_t).
+ * odvae_noise_fill_f32: out[e] = element first + e of the stream in `tag`, e in [0, n); kind 0 = standard normal, 1 = dropout multiplier
+ * of probability p (0 or f32(1 / (1 - p)); all 0 at p = 1).  first < 2^62 and need not be a multiple of 4.
+ * odvae_latent_stage_f32: z = ((mean + std * eps) * m + noise) + add on NHWC moments [N][HW][2*Cz] (logvar clamped to [-30, 20]), add
+ * (may be NULL) and z [N][HW][Cz]; eps, m, noise are streams 0, 1, 2 of `tag` (whose stream bits must be 0), element = flat index of z.
+ * flags: 1 = sample (else mode: z0 = mean), 2 = dropout on, 4 = noise on.  Bit for bit the chain odvae_gaussian_sample_f32 ->
+ * odvae_latent_combine_f32 (mask) -> (add = noise) -> (add) fed odvae_noise_fill_f32's tensors for the same words.
+ * odvae_latent_stage_bwd_f32: dmoments from moments and dz alone (eps and m are drawn again); the gradient of add is dz itself. */
+int odvae_noise_fill_f32(float* out, int64_t n, uint64_t first, uint64_t seed, uint64_t step_word, uint64_t tag, int kind, double p,
+                         void* stream);
+int odvae_latent_stage_f32(const float* moments, const float* add, float* z, int N, int HW, int Cz, uint64_t seed, uint64_t step_word,
+                           uint64_t tag, int flags, double p, void* stream);
+int odvae_latent_stage_bwd_f32(const float* moments, const float* dz, float* dmoments, int N, int HW, int Cz, uint64_t seed,
+                               uint64_t step_word, uint64_t tag, int flags, double p, void* stream);
+
 /* ---- gan_f32.hip, gan_norm.hip: PatchGAN NLayerDiscriminator ([UPSTREAM] taming discriminator; contperceptual.py:285,355-356) ----
  * gan_f32.hip: the convolution pieces, LeakyReLU, the logit terms; gan_norm.hip: BatchNorm2d / ActNorm + LeakyReLU (f32 here, bf16 below).
  * Conv2d(k=4, pad=1, stride 1|2) = im2col + odvae_gemm_f32 against the weight reordered to [Cout][(kh,kw,ci)];
