@@ -9,7 +9,9 @@ tests/wgrad_wino_math.py pin the loop bit for bit (tests/test_wgrad_wino_split.p
 
 The split loop needs whole chunks of 16 tiles inside a tile row (W / 2 a multiple of 16), so it never meets a ragged last chunk or a
 chunk that spans two images; those shapes are covered where they belong, among the shapes that keep the f32 loop bit for bit.  Splits of
-unequal length, tile rows of several chunks, single tile rows and image borders inside a split are covered on the split loop."""
+unequal length, tile rows of several chunks, single tile rows and image borders inside a split are covered on the split loop.
+tests/test_wgrad_wino_exact_gpu.py pins both loops and the reduction bit for bit at the edges of the plan: several chunks per split, a short
+last split, the XCD block mapping, ragged chunks on the f32 loop."""
 import math
 
 import pytest
