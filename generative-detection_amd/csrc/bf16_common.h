@@ -93,6 +93,20 @@ __device__ __forceinline__ void split8(const float (&x)[8], u32x4 (&pl)[3]) {
     for (int q = 0; q < 3; ++q) pl[q][j] = w[q];
   }
 }
+// The same with fewer planes kept (gemm_f32_split.hip at float32_matmul_precision high / medium).  hi and mid are the numbers split8
+// computes: round to nearest even, mid = bf16(x - hi).  One plane: a conversion and no subtraction, so an Inf stays Inf.
+__device__ __forceinline__ void split8_hi_mid(const float (&x)[8], u32x4 (&pl)[2]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned hi = cvt_pk_bf16(x[2 * j], x[2 * j + 1]);
+    pl[0][j] = hi;
+    pl[1][j] = cvt_pk_bf16(x[2 * j] - bf16_lo(hi), x[2 * j + 1] - bf16_hi(hi));
+  }
+}
+__device__ __forceinline__ void split8_hi(const float (&x)[8], u32x4 (&pl)[1]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) pl[0][j] = cvt_pk_bf16(x[2 * j], x[2 * j + 1]);
+}
 // D(32x32) += A(32x16) * B(16x32), bf16 in, f32 accumulate.  lane l (r = l&31, h = l>>5) supplies A[row r][k = 8h+j] and
 // B[k = 8h+j][col r], j = 0..7; D register i of lane l is D[row (i&3) + 8(i>>2) + 4h][col r]  (tools/tr_probe.hip)
 __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {

@@ -9,6 +9,18 @@
 // MFMAs they replace.  No atomics in the sums and a fixed order: two runs give the same bits.  An Inf operand gives x - hi = NaN, so
 // Inf and NaN inputs both come out as NaN (never as a finite number).
 //
+// float32_matmul_precision (odvae_gemm_select_precision; torch's three levels, on a chip without an xf32 / TF32 matrix instruction):
+// the kernel is a template on the number of planes kept, NP.  hi and mid are always the numbers above; what changes is what is dropped.
+//     level 0 "highest"  NP = 3  the six products above                      48 KB of LDS, 48 fragment registers per 16 k
+//     level 1 "high"     NP = 2  a_mid b_hi, a_hi b_mid, a_hi b_hi           32 KB, 32: "each float32 number as the sum of two bfloat16"
+//     level 2 "medium"   NP = 1  a_hi b_hi                                   16 KB, 16: "the bfloat16 datatype for internal computations"
+// The kept products are a suffix of the order above, still smallest first within every 16 k.  Dropped at high: mid mid, lo hi, hi lo and
+// what highest drops, below 3 * 2^-16 + 2^-21 of sum_k |a_k| |b_k| together; at medium also mid hi and hi mid, below 2^-7 + 2^-13.
+// At medium the loader is one v_cvt_pk_bf16_f32 per pair and no subtraction: an Inf operand stays Inf, so Inf times a finite non-zero
+// value is Inf and Inf times zero NaN; at high x - hi = NaN as at highest.  A non-finite operand never gives a finite output.
+// The ROWNORM row sums come from the unsplit f32 values at every level; the EXPB / SMB row terms join the finished sum.  The dispatch
+// (split_eligible, split_tt_eligible) does not look at the level.  NP = 3 is the code it was before the template.
+//
 // Block = 256 threads = 4 waves (2x2), block tile 128x128, wave tile 64x64, 32 k per step -- gemm_f32.hip's geometry, whose output
 // tails (gemm_f32_tile.h) are used as they are.  The operands are split in the loader, in registers: a thread fetches eight
 // consecutive k of one row (k-contiguous operand: two 16-byte loads; row-contiguous operand: eight 4-byte loads, lane = row, so a
@@ -24,7 +36,14 @@ namespace {
 using namespace gemm_tile;
 
 constexpr unsigned PLANE_B = BM * BK * 2;        // 8 192: one bf16 plane of one operand tile
-constexpr unsigned OPER_B = 3 * PLANE_B;         // hi, mid, lo
+template <int NP> constexpr unsigned OPER_B = NP * PLANE_B;      // the planes kept: hi, mid, lo (3), hi, mid (2) or hi (1)
+// the products kept are the last 6 / 3 / 1 of split3::ORDER: all six; a_mid b_hi, a_hi b_mid, a_hi b_hi; a_hi b_hi
+template <int NP> constexpr int FIRST_PRODUCT = NP == 3 ? 0 : (NP == 2 ? 3 : 5);
+// Blocks per CU asked of the compiler.  Three planes: three (168 registers, 3 x 48 KB of LDS), see the kernel.  Two planes and one: LDS
+// (32 / 16 KB) admits a fourth, and asked for three hipcc already stays at or below 128 registers, without scratch, in four of the five
+// one-plane kernels and the two-plane ROWNORM one -- those run four blocks per CU as they are.  Asked for four, every two-plane
+// kernel but ROWNORM and the one-plane SMB kernel go to scratch (12 to 196 bytes per lane, tools/spill_report.py).  So: three everywhere.
+template <int NP> constexpr int BLOCKS_PER_CU = 3;
 constexpr unsigned OOB = 0x7FFFFFF0u;
 using namespace split3;      // HI, MID, LO, ORDER
 
@@ -37,12 +56,15 @@ __device__ __forceinline__ unsigned tile_byte(int row, int slot) {
   return (unsigned)(row * 64 + ((slot ^ f) << 4));
 }
 
+template <int NP>
 __device__ __forceinline__ void store_unit(unsigned lds_oper, int row, int slot, const float (&x)[8]) {
-  u32x4 pl[3];
-  split8(x, pl);
+  u32x4 pl[NP];
+  if constexpr (NP == 3) split8(x, pl);
+  else if constexpr (NP == 2) split8_hi_mid(x, pl);
+  else split8_hi(x, pl);
   const unsigned a = lds_oper + tile_byte(row, slot);
 #pragma unroll
-  for (int q = 0; q < 3; ++q) lds_st128(a + q * PLANE_B, pl[q]);
+  for (int q = 0; q < NP; ++q) lds_st128(a + q * PLANE_B, pl[q]);
 }
 
 // One operand's loader.  A unit = eight consecutive k of one row; 128 rows x 4 slots = 512 units, two per thread.
@@ -107,25 +129,27 @@ struct SplitLoader {
         }
     }
   }
+  template <int NP>
   __device__ __forceinline__ void store(unsigned lds_oper) const {
     const int tid = threadIdx.x;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      if (KC) store_unit(lds_oper, (tid + 256 * i) >> 2, tid & 3, x[i]);
-      else    store_unit(lds_oper, tid & 127, (tid >> 7) + 2 * i, x[i]);
+      if (KC) store_unit<NP>(lds_oper, (tid + 256 * i) >> 2, tid & 3, x[i]);
+      else    store_unit<NP>(lds_oper, tid & 127, (tid >> 7) + 2 * i, x[i]);
     }
   }
 };
 
-template <bool A_KC, bool B_KC, int EPI>
+template <bool A_KC, bool B_KC, int EPI, int NP>
 // three blocks per CU (168 registers, 3 x 48 KB of LDS): 5 % faster than two on the T-deep attention shapes, 5-6 % on the T x T ones at
 // K = 256 and 11-27 % at K = 128 (few steps deep: two other blocks' MFMAs cover a block's first split and its 64 KB tail);
 // s_setprio around the MFMAs: nothing
-__global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(GemmParams p) {
+__global__ __launch_bounds__(256, BLOCKS_PER_CU<NP>) void gemm_f32_split_kernel(GemmParams p) {
   constexpr bool ROWNORM = EPI == EPI_ROWNORM, EXPB = EPI == EPI_EXPB, SMB = EPI == EPI_SMB;
+  static_assert(NP >= 1 && NP <= 3, "one, two or three bf16 planes");
   static_assert(!ROWNORM || A_KC, "the row sums are taken by the k-contiguous loader");
   static_assert(!(EXPB || SMB) || (A_KC && B_KC), "the T x T tails belong to the NT form");
-  __shared__ __attribute__((aligned(16))) char smem[2 * OPER_B];
+  __shared__ __attribute__((aligned(16))) char smem[2 * OPER_B<NP>];
   const int tile_m = blockIdx.x % p.tiles_m, tile_n = blockIdx.x / p.tiles_m, batch = blockIdx.z;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const float* A = p.A + batch * p.sA;
@@ -144,7 +168,7 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(GemmParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
-  const unsigned ldsA = lds_addr_of(smem), ldsB = ldsA + OPER_B;
+  const unsigned ldsA = lds_addr_of(smem), ldsB = ldsA + OPER_B<NP>;
   // fragment of 32-row tile t, 16-k half kk, plane q: adr[kk] + t * 2048 + q * PLANE_B (rows t*32 + li share li's swizzle: it looks at row bits 1..3)
   unsigned adrA[2], adrB[2];
 #pragma unroll
@@ -164,22 +188,22 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(GemmParams p) {
       for (int i = 0; i < 2; ++i)
         rowl[i] += ((fa.x[i][0] + fa.x[i][1]) + (fa.x[i][2] + fa.x[i][3])) + ((fa.x[i][4] + fa.x[i][5]) + (fa.x[i][6] + fa.x[i][7]));
     }
-    fa.store(ldsA);
-    fb.store(ldsB);
+    fa.template store<NP>(ldsA);
+    fb.template store<NP>(ldsB);
   };
   auto products = [&]() {
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 a[2][3], b[2][3];
+      bf16x8 a[2][NP], b[2][NP];
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
+        for (int q = 0; q < NP; ++q) {
           a[t][q] = frag_from_u32x4(lds_ld128(adrA[kk] + t * 2048u + q * PLANE_B));
           b[t][q] = frag_from_u32x4(lds_ld128(adrB[kk] + t * 2048u + q * PLANE_B));
         }
 #pragma unroll
-      for (int o = 0; o < 6; ++o)
+      for (int o = FIRST_PRODUCT<NP>; o < 6; ++o)
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -247,7 +271,24 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_split_kernel(GemmParams p) {
   }
 }
 
+int g_precision = 0;      // float32_matmul_precision, set by odvae_gemm_select_precision: 0 three planes, 1 two, 2 one
+
+template <int NP>
+void launch_planes(const GemmParams& p, int transA, int epi, dim3 grid, dim3 block, hipStream_t st) {
+  if (epi == EPI_EXPB)          hipLaunchKernelGGL((gemm_f32_split_kernel<true, true, EPI_EXPB, NP>), grid, block, 0, st, p);
+  else if (epi == EPI_SMB)      hipLaunchKernelGGL((gemm_f32_split_kernel<true, true, EPI_SMB, NP>), grid, block, 0, st, p);
+  else if (epi == EPI_ROWNORM)  hipLaunchKernelGGL((gemm_f32_split_kernel<true, false, EPI_ROWNORM, NP>), grid, block, 0, st, p);
+  else if (!transA)             hipLaunchKernelGGL((gemm_f32_split_kernel<true, false, EPI_NONE, NP>), grid, block, 0, st, p);
+  else                          hipLaunchKernelGGL((gemm_f32_split_kernel<false, false, EPI_NONE, NP>), grid, block, 0, st, p);
+}
+
 }  // namespace
+
+extern "C" int odvae_gemm_select_precision(int level) {
+  const int prev = g_precision;
+  g_precision = level < 0 ? 0 : (level > 2 ? 2 : level);
+  return prev;
+}
 
 namespace gemm_tile {
 
@@ -272,11 +313,9 @@ bool split_tt_eligible(int staging_mode, int M, int N, int K, int batch) {
 
 int launch_split(const GemmParams& p, int transA, int epi, int batch, hipStream_t st) {
   const dim3 grid(p.tiles_m * ceil_div(p.N, BN), 1, batch), block(256);
-  if (epi == EPI_EXPB)          hipLaunchKernelGGL((gemm_f32_split_kernel<true, true, EPI_EXPB>), grid, block, 0, st, p);
-  else if (epi == EPI_SMB)      hipLaunchKernelGGL((gemm_f32_split_kernel<true, true, EPI_SMB>), grid, block, 0, st, p);
-  else if (epi == EPI_ROWNORM)  hipLaunchKernelGGL((gemm_f32_split_kernel<true, false, EPI_ROWNORM>), grid, block, 0, st, p);
-  else if (!transA)             hipLaunchKernelGGL((gemm_f32_split_kernel<true, false, EPI_NONE>), grid, block, 0, st, p);
-  else                          hipLaunchKernelGGL((gemm_f32_split_kernel<false, false, EPI_NONE>), grid, block, 0, st, p);
+  if (g_precision == 0)       launch_planes<3>(p, transA, epi, grid, block, st);
+  else if (g_precision == 1)  launch_planes<2>(p, transA, epi, grid, block, st);
+  else                        launch_planes<1>(p, transA, epi, grid, block, st);
   ODVAE_LAUNCH_CHECK("gemm_f32 (bf16 split)");
   return ODVAE_OK;
 }

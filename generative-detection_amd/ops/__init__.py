@@ -68,6 +68,13 @@ DISC_BF16 = os.environ.get("ODVAE_DISC_BF16", "0") == "1"
 # matrix, what a conv saves is its input); default 0 = im2col + GEMM + col2im (_Conv4x4).  A bf16 discriminator never gets here.
 DISC_F32_IMPLICIT = os.environ.get("ODVAE_DISC_F32_IMPLICIT", "0") == "1"
 
+# float32_matmul_precision (the reference's launcher sets 'medium', train.py:521): how many bf16 planes of each f32 operand the
+# bf16-split GEMM multiplies (ops/precision.py).  ODVAE_FLOAT32_MATMUL_PRECISION = highest (default: today's bits) | high | medium |
+# torch (follow torch.get_float32_matmul_precision() at call time).  The pose head's dense layers stay exact f32 at every level.
+FLOAT32_MATMUL_PRECISION = os.environ.get("ODVAE_FLOAT32_MATMUL_PRECISION", "highest").strip().lower() or "highest"
+if FLOAT32_MATMUL_PRECISION not in ("highest", "high", "medium", "torch"):
+    raise ValueError("ODVAE_FLOAT32_MATMUL_PRECISION must be highest, high, medium or torch, got %r" % os.environ["ODVAE_FLOAT32_MATMUL_PRECISION"])
+
 WGRAD_1X1_GROUP = 0   # tests: force the image-group split of the 1x1 weight gradient at small sizes (0 = only past 2 GiB)
 CONV_1X1_GROUP = 0    # tests: the same for the 1x1 forward / data gradient in _conv_b_raw (images per launch; 0 = only past 2 GiB)
 
@@ -81,6 +88,7 @@ WEIGHT_GRADIENT_ONLY = False
 GN_FUSED_BWD_HITS = 0      # GroupNorm backwards that ran without their reduce pass (diagnostics, tests)
 GN_FUSED_BWD_SUSPENDED = 0  # > 0 inside an activation-checkpointed unit (modules.Decoder): a saved tensor of such a unit may be unpacked once per
                             # backward, and the link would read the GroupNorm's from the conv's backward before the GroupNorm's own does
+_MATMUL_LEVEL_PUSHED = 0   # the level last given to odvae_gemm_select_precision (the library loads at 0); precision._sync_precision
 _ATTN_LAST_FLAG = None     # (diagnostics / tests: the device flag of the last folded-softmax attention forward, 1 if its fallback ran)
 
 # ------------------------------------------------------------------------------------------------------
@@ -93,6 +101,9 @@ from .packs import (  # noqa: E402
 from .gn_link import (  # noqa: E402
     GN_GROUPS, _GnBwdLink, _gn_bwd_link_of, _gn_stats_ok, _tag_gn_partials, _gn_partials_of, _f32_gn_link, gn_fused_bwd_suspended,
     _tag_gn_output)
+from .precision import (  # noqa: E402
+    MATMUL_PRECISION_LEVELS, MATMUL_PRECISION_VALUES, _parse_matmul_precision, _matmul_level, _sync_precision,
+    set_float32_matmul_precision, get_float32_matmul_precision)
 from .gemm import (  # noqa: E402
     gemm, _colsum)
 from .conv_bf16 import (  # noqa: E402

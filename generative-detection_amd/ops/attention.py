@@ -9,6 +9,7 @@ from .. import ops as _ops      # the package: switches and run-time state are r
 from .. import lib as _lib
 from ._base import BF16, CL, KERNEL_EVENTS, _L, _cl, _new_cl, _ws
 from .gemm import gemm
+from .precision import _sync_precision
 
 
 def _qkv_views(t, c):
@@ -25,6 +26,7 @@ class _Attention(Function):
     @staticmethod
     def forward(ctx, qkv):
         L = _L()
+        _sync_precision(L)      # the T x T products below call the library directly
         qkv = _cl(qkv)
         n, c3, h, w = qkv.shape
         c = c3 // 3
@@ -70,6 +72,7 @@ class _Attention(Function):
     @staticmethod
     def backward(ctx, do):
         L = _L()
+        _sync_precision(L)
         if ctx.folded:
             qkv, p, o, rinv = ctx.saved_tensors      # p holds E = exp(scale (s - bound)), P = E * rinv[row]
         else:
@@ -154,6 +157,7 @@ class _AttentionRecompute(Function):
     @staticmethod
     def backward(ctx, do):
         L = _L()
+        _sync_precision(L)
         qkv, o = ctx.saved_tensors
         do = _cl(do)
         n, c3, h, w = qkv.shape

@@ -3,6 +3,7 @@ import torch
 
 from .. import lib as _lib
 from ._base import KERNEL_EVENTS, _L, _ws
+from .precision import _sync_precision
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -11,6 +12,7 @@ from ._base import KERNEL_EVENTS, _L, _ws
 def gemm(ta, tb, m, n, k, alpha, a, lda, sa, b, ldb, sb, c, ldc, sc, bias=None, residual=None, batch=1):
     """Raw batched GEMM on device pointers held by tensors a, b, c (see gemm_f32.hip)."""
     L = _L()
+    _sync_precision(L)      # float32_matmul_precision: deep plain products run on the bf16-split kernel
     need = L.odvae_gemm_f32_workspace_bytes(m, n, k, batch)
     wp, wn = _ws(need, c) if need else (None, 0)
     tag = KERNEL_EVENTS.begin(secondary=True)

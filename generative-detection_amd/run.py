@@ -37,6 +37,9 @@ def parse(argv):
     ap.add_argument("-l", "--logdir", default=None, help="if given, the yaml's lightning.callbacks run and ImageLogger writes below it")
     ap.add_argument("--checkpoint", default=None, help="with model.params.ema_decay: write a Lightning-layout checkpoint (weights, model_ema.*, "
                     "optimizer states) here after the run; default <logdir>/checkpoints/last.ckpt when --logdir is given")
+    ap.add_argument("--float32_matmul_precision", default=None, choices=("highest", "high", "medium", "torch"),
+                    help="what the reference's launcher sets with torch.set_float32_matmul_precision (train.py:521: medium); default: "
+                    "leave ODVAE_FLOAT32_MATMUL_PRECISION (highest) alone")
     return ap.parse_known_args(argv)
 
 
@@ -80,7 +83,8 @@ def main(argv=None):
         logger = _Logger()
         for name, cb_cfg in lightning.get("callbacks", Config.create()).items():
             callbacks.append(instantiate_from_config(cb_cfg))
-    trainer = Trainer(model, callbacks=callbacks, logger=logger, **trainer_kwargs(trainer_cfg))
+    trainer = Trainer(model, callbacks=callbacks, logger=logger, float32_matmul_precision=opt.float32_matmul_precision,
+                      **trainer_kwargs(trainer_cfg))
     bs = config.data.params.batch_size
 
     def make(step):

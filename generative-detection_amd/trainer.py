@@ -33,7 +33,7 @@ class Trainer:
     def __init__(self, model, gradient_clip_val=None, optimizer_indices=(0, 1), process_group=None, bucket_mb=None, precision=None,
                  distributed=None, comm_dtype=None, callbacks=(), logger=None, comm_f32_accumulate=False,
                  detect_anomaly=None, accumulate_grad_batches=1, perceptual_precision=None, discriminator_precision=None,
-                 sync_batchnorm=False):
+                 sync_batchnorm=False, float32_matmul_precision=None):
         """optimizer_indices: which of the model's optimizers run each batch; (0,) is the "rec+KL only" benchmark
         configuration (discriminator off, optimizer 1 skipped -- SURVEY.md 8(d)).
         comm_dtype: dtype of the gradient buckets on the wire; None = f32 in every precision -- what the reference's `strategy: ddp`
@@ -56,7 +56,13 @@ class Trainer:
         sync_batchnorm: lightning.trainer.sync_batchnorm of the yaml / `--sync_batchnorm True` (PL 1.9 runs
         torch.nn.SyncBatchNorm.convert_sync_batchnorm over the module; its only BatchNorm layers are the discriminator's three).  True in a
         data-parallel run over more than one rank: those layers take their training statistics and backward sums over this trainer's
-        process group (gan.BatchNormLReLU.dist_group).  Not data-parallel, one rank, or use_actnorm: nothing changes."""
+        process group (gan.BatchNormLReLU.dist_group).  Not data-parallel, one rank, or use_actnorm: nothing changes.
+        float32_matmul_precision: "highest", "high", "medium" or "torch" -- what the reference's launcher sets with
+        torch.set_float32_matmul_precision (train.py:521: 'medium'); ops/precision.py.  Process-global, like torch's, and not
+        restored when the trainer goes away.  None leaves the setting (ODVAE_FLOAT32_MATMUL_PRECISION, default highest) alone."""
+        if float32_matmul_precision is not None:
+            from . import ops
+            ops.set_float32_matmul_precision(float32_matmul_precision)      # (a bad name raises before anything else is touched)
         if not isinstance(sync_batchnorm, bool):
             raise ValueError("sync_batchnorm must be True or False, got %r" % (sync_batchnorm,))
         self.sync_batchnorm = sync_batchnorm

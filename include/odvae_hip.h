@@ -52,6 +52,20 @@ size_t odvae_gemm_f32_workspace_bytes(int M, int N, int K, int batch);
  * results among 0 / 1 / 2, which always mean the f32 MFMA kernel; -1 also lets deep plain products (above) and the attention's two
  * T x T products (odvae_gemm_exp_bound_f32, odvae_gemm_softmax_bwd[_scaled]_f32) run as bf16 splits; returns the previous setting. */
 int odvae_gemm_select_staging(int mode);
+/* torch.set_float32_matmul_precision for the bf16-split kernel (gemm_f32_split.hip): how many bf16 planes of each f32 operand it keeps.
+ *   0 "highest" (value at library load): hi, mid, lo; six products -- the kernel described above, unchanged to the bit;
+ *   1 "high": hi, mid; the products a_mid b_hi, a_hi b_mid, a_hi b_hi -- within 2^-14 of sum_k |a_k| |b_k| of the f32 kernel's result;
+ *   2 "medium": hi; the one product a_hi b_hi (bf16 operands, f32 accumulation) -- within 2^-6.
+ * Clamps to 0..2, returns the previous setting; process-global, host only.  It applies to EVERY launch of the split kernel: the four
+ * odvae_gemm_* entry points that dispatch to it (odvae_gemm_f32, odvae_gemm_rownorm_f32, odvae_gemm_exp_bound_f32,
+ * odvae_gemm_softmax_bwd[_scaled]_f32), and with them a 1x1 convolution's weight gradient where odvae_gemm_f32 sends it there (deep K,
+ * unsplit: 1 024 pixels; deeper ones run split-K on the f32 kernel) -- which in the reference falls under cuDNN's TF32 allowance
+ * (torch.backends.cudnn.allow_tf32, on by default), not under this setting.  The dispatch does not
+ * move with the level: a shape that runs on the f32 MFMA kernel does so at every level, and a forced staging mode
+ * (odvae_gemm_select_staging(0 | 1 | 2)) still means the f32 MFMA kernel.  The row sums of odvae_gemm_rownorm_f32 come from the unsplit
+ * f32 values at every level.  Non-finite operands never give a finite output: at 0 and 1 an Inf operand yields NaN (x - hi = NaN), at 2
+ * Inf times a finite non-zero value is Inf (no subtraction happens) and Inf times zero NaN. */
+int odvae_gemm_select_precision(int level);
 int odvae_gemm_f32(int transA, int transB, int M, int N, int K, float alpha,
                    const float* A, int lda, int64_t strideA,
                    const float* B, int ldb, int64_t strideB,
