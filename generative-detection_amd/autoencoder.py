@@ -406,6 +406,12 @@ class PoseAutoencoder(AutoencoderKL):
             z = ops.latent_combine(z, None, self._drawn("z_noise", shape, draw, "z_noise"))
         return z if enc_pose is None else ops.latent_combine(z, None, enc_pose)
 
+    def _pretrain_channels(self, input_im):
+        """Channels of the all-zero stand-in reconstruction before encoder_pretrain_steps: the input's, as in the reference
+        (zeros_like(input_im), :247).  DEVIATION with image_mask_key: the decoder's out_ch, so that the loss and its 4-channel discriminator
+        see the shape the decoder will deliver -- the reference's 3-channel zeros die in its discriminator call there."""
+        return input_im.shape[1] if self.image_mask_key is None else self.decoder.conv_out.out_channels
+
     def _forward_device_noise(self, posterior_obj, pose_feat, input_im, sample_posterior):
         """forward with device_noise on: no torch.randn / torch.rand, no upload.  The pose head runs first, so that enc_pose is there
         when the one latent launch wants it as `add` (neither depends on the other's draws)."""
@@ -414,7 +420,7 @@ class PoseAutoencoder(AutoencoderKL):
         dec_pose, bbox_posterior = self._decode_pose(pose_feat, sample_posterior, draw=draw)
         if self.global_step < self.encoder_pretrain_steps:      # z_obj feeds nothing here: not computed
             n, _, h, w = input_im.shape
-            dec_obj = torch.zeros((n, h, w, input_im.shape[1]), device=self.device).permute(0, 3, 1, 2)
+            dec_obj = torch.zeros((n, h, w, self._pretrain_channels(input_im)), device=self.device).permute(0, 3, 1, 2)
         else:
             enc_pose = self._encode_pose(dec_pose)
             zshape = (posterior_obj.parameters.shape[0], posterior_obj.parameters.shape[1] // 2) + tuple(posterior_obj.parameters.shape[2:])
@@ -438,7 +444,7 @@ class PoseAutoencoder(AutoencoderKL):
         dec_pose, bbox_posterior = self._decode_pose(pose_feat, sample_posterior)
         if self.global_step < self.encoder_pretrain_steps:
             n, _, h, w = input_im.shape
-            dec_obj = torch.zeros((n, h, w, input_im.shape[1]), device=self.device).permute(0, 3, 1, 2)
+            dec_obj = torch.zeros((n, h, w, self._pretrain_channels(input_im)), device=self.device).permute(0, 3, 1, 2)
         else:
             enc_pose = self._encode_pose(dec_pose)
             assert z_obj.shape == enc_pose.shape, f"z_obj shape: {z_obj.shape}, enc_pose shape: {enc_pose.shape}"

@@ -427,16 +427,20 @@ __global__ void conv4x4_pack_kernel(const float* __restrict__ w, int Cout, int C
 // (10x wasted MFMA work) a wave multiplies a 32-pixel row segment's im2col row block [32 px][27 -> 32] with the whole
 // weight matrix [32][128 co], which it keeps in 64 registers for its lifetime.  No LDS, no barriers; A fragments are
 // gathers from the 25 MB input (cache resident), the output is written once.
+// NC = 4 (the data gradient of a 4-channel conv_out: image_mask_key): K = 9 x 4 = 36 is eighteen MFMA steps with no padding, k = 4 tap + ci,
+// and a tap's four channels are ONE 16-byte load of which the lane keeps two (ci = kk and 2 + kk).  NC = 3 is the code it always was.
+template <int NC>
 __global__ __launch_bounds__(256, 2) void conv3x3_thin_in_kernel(ConvParams p) {
+  constexpr int NS = NC == 3 ? 16 : 18;
   const int lane = threadIdx.x & 63, li = lane & 31, kk = lane >> 5;
   const int wave_in_grid = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
   const int c0 = blockIdx.y * 128;
   const int QT = p.CinP / 4;
-  // k-step s of this lane is k = 2s + kk -> (tap, ci) = (k / 3, k % 3), taps past 8 multiply zeros
-  float bw[4][16];
+  // k-step s of this lane is k = 2s + kk -> (tap, ci) = (k / NC, k % NC), taps past 8 multiply zeros
+  float bw[4][NS];
 #pragma unroll
-  for (int s = 0; s < 16; ++s) {
-    const int k = 2 * s + kk, tap = k / 3, ci = k - 3 * tap;
+  for (int s = 0; s < NS; ++s) {
+    const int k = 2 * s + kk, tap = k / NC, ci = k - NC * tap;
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
       const int co = c0 + ct * 32 + li;
@@ -453,14 +457,25 @@ __global__ __launch_bounds__(256, 2) void conv3x3_thin_in_kernel(ConvParams p) {
   for (int tile = __builtin_amdgcn_readfirstlane(wave_in_grid); tile < ntiles; tile += nwaves) {
     const int seg = tile % segs, row = tile / segs;       // row = n * Ho + y
     const int y = row % p.Ho, x0 = seg * 32;
-    float a[16];
+    float a[NS];
+    if constexpr (NC == 3) {
 #pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int k = 2 * s + kk, tap = k / 3, ci = k - 3 * tap;
-      const int iy = y + tap / 3 - 1, ix = x0 + li + tap % 3 - 1;
-      const bool ok = tap < 9 && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi;
-      const float v = p.x[((int64_t)(row - y + min(max(iy, 0), p.Hi - 1)) * p.Wi + min(max(ix, 0), p.Wi - 1)) * 3 + ci];
-      a[s] = ok ? v : 0.f;
+      for (int s = 0; s < 16; ++s) {
+        const int k = 2 * s + kk, tap = k / 3, ci = k - 3 * tap;
+        const int iy = y + tap / 3 - 1, ix = x0 + li + tap % 3 - 1;
+        const bool ok = tap < 9 && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi;
+        const float v = p.x[((int64_t)(row - y + min(max(iy, 0), p.Hi - 1)) * p.Wi + min(max(ix, 0), p.Wi - 1)) * 3 + ci];
+        a[s] = ok ? v : 0.f;
+      }
+    } else {
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const int iy = y + tap / 3 - 1, ix = x0 + li + tap % 3 - 1;
+        const bool ok = iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi;
+        const float4 v = reinterpret_cast<const float4*>(p.x)[(int64_t)(row - y + min(max(iy, 0), p.Hi - 1)) * p.Wi + min(max(ix, 0), p.Wi - 1)];
+        a[2 * tap] = ok ? (kk ? v.y : v.x) : 0.f;
+        a[2 * tap + 1] = ok ? (kk ? v.w : v.z) : 0.f;
+      }
     }
     f32x16 acc[4];
     // the tile's 32 pixels x Cout channels are one contiguous run of y: a buffer descriptor over exactly that run (base wave-uniform),
@@ -479,7 +494,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_thin_in_kernel(ConvParams p) {
         acc[ct][r] = bv[ct] + (p.residual ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rrs, vo, ((r & 3) + 8 * (r >> 2)) * rstep, 0)) : 0.f);
     }
 #pragma unroll
-    for (int s = 0; s < 16; ++s)
+    for (int s = 0; s < NS; ++s)
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) acc[ct] = mfma32(a[s], bw[ct][s], acc[ct]);
 #pragma unroll
@@ -502,10 +517,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_thin_in_kernel(ConvParams p) {
 // Block = 8 x 32 output pixels; Y27 for the 10 x 34 halo region = eleven 32-pixel MFMA row tiles shared by four waves; the weight
 // matrix W27 [Cin][32] sits in Cin / 2 registers per lane.  Out-of-image halo pixels read as zeros, so their Y27 rows are zero: the
 // conv's zero padding.  No activation, no residual (conv_out has neither).
+// NCO = 4 (a 4-channel conv_out: image_mask_key): 9 x 4 = 36 tap columns are TWO column tiles, [tap * 4 + co] with columns 0 .. 31 in the
+// first and 32 .. 35 (tap 8) in the second; the halo pixel's channels are loaded once and feed both MFMA chains.  Y is 52 KiB of static LDS.
+// NCO = 3 is the kernel it always was (one tile, Cout <= 3).
 constexpr int TO_TH = 8, TO_TW = 32, TO_HW = TO_TW + 2, TO_HPIX = (TO_TH + 2) * TO_HW, TO_MT = (TO_HPIX + 31) / 32;
-template <int CIN>
+template <int CIN, int NCO>
 __global__ __launch_bounds__(256) void conv3x3_thin_out_kernel(ConvParams p) {
-  __shared__ float Y[TO_MT * 32][32 + 1];     // [halo pixel][tap * 3 + co], +1: the nine-term gather walks rows
+  constexpr int YC = NCO == 3 ? 32 : 36;
+  __shared__ float Y[TO_MT * 32][YC + 1];     // [halo pixel][tap * NCO + co], +1: the nine-term gather walks rows
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, kk = lane >> 5;
   int t = blockIdx.x;
   const int tx = t % p.tiles_x; t /= p.tiles_x;
@@ -514,12 +533,14 @@ __global__ __launch_bounds__(256) void conv3x3_thin_out_kernel(ConvParams p) {
   const int QT = p.CinP / 4;
   // B operand: lane (column nn = li, k parity kk) holds W27[2 s + kk][nn] for s = 0 .. CIN/2 - 1
   float bw[CIN / 2];
+  float bw2[NCO == 3 ? 1 : CIN / 2];           // NCO = 4: the second column tile, columns 32 + li (tap 8, co = li) for li < 4
   {
-    const int tap = li / 3, co = li - 3 * tap;
+    const int tap = li / NCO, co = li - NCO * tap;
 #pragma unroll
     for (int s = 0; s < CIN / 2; ++s) {
       const int ci = 2 * s + kk;
-      bw[s] = (li < 27 && co < p.Cout) ? p.wpk[(((int64_t)tap * QT + (ci >> 2)) * p.CoutP + co) * 4 + (ci & 3)] : 0.f;
+      bw[s] = (li < (NCO == 3 ? 27 : 32) && co < p.Cout) ? p.wpk[(((int64_t)tap * QT + (ci >> 2)) * p.CoutP + co) * 4 + (ci & 3)] : 0.f;
+      if constexpr (NCO == 4) bw2[s] = li < 4 ? p.wpk[(((int64_t)8 * QT + (ci >> 2)) * p.CoutP + li) * 4 + (ci & 3)] : 0.f;
     }
   }
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x) + (int64_t)n * p.Hi * p.Wi * p.Cin, 0,
@@ -530,9 +551,9 @@ __global__ __launch_bounds__(256) void conv3x3_thin_out_kernel(ConvParams p) {
     const int iy = oy0 - 1 + hy, ix = ox0 - 1 + hx;
     const bool ok = hp < TO_HPIX && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi;
     const unsigned voff = ok ? (unsigned)((iy * p.Wi + ix) * p.Cin) * 4u : 0x7FFFFFF0u;
-    f32x16 acc;
+    f32x16 acc, acc2;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[r] = acc2[r] = 0.f;
     // ALL of the pixel's channels requested before the first MFMA (CIN / 4 sixteen-byte loads per lane, 128 registers at CIN = 128): with four
     // loads in flight per step the kernel was eight dependent memory round trips per 32 halo pixels -- 533 us for the 1.07 GB it reads (2 TB/s)
     u32x4 v[CIN / 4];
@@ -545,21 +566,33 @@ __global__ __launch_bounds__(256) void conv3x3_thin_out_kernel(ConvParams p) {
       const float a0 = __uint_as_float(kk ? v[j].y : v[j].x), a1 = __uint_as_float(kk ? v[j].w : v[j].z);
       acc = mfma32(a0, bw[2 * j], acc);
       acc = mfma32(a1, bw[2 * j + 1], acc);
+      if constexpr (NCO == 4) {
+        acc2 = mfma32(a0, bw2[2 * j], acc2);
+        acc2 = mfma32(a1, bw2[2 * j + 1], acc2);
+      }
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) Y[mt * 32 + acc_row(r, lane)][li] = acc[r];
+    if constexpr (NCO == 4) {
+      if (li < 4) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Y[mt * 32 + acc_row(r, lane)][32 + li] = acc2[r];
+      }
+    }
   }
   __syncthreads();
   // one output pixel per thread: nine taps x Cout values out of its 3 x 3 neighbourhood of Y27 rows
   const int r = tid / TO_TW, c = tid - r * TO_TW;
   const int oy = oy0 + r, ox = ox0 + c;
   if (oy < p.Ho && ox < p.Wo) {
-    float o[3] = {0.f, 0.f, 0.f};
+    float o[NCO];
+#pragma unroll
+    for (int co = 0; co < NCO; ++co) o[co] = 0.f;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const float* row = Y[(r + tap / 3) * TO_HW + c + tap % 3];
 #pragma unroll
-      for (int co = 0; co < 3; ++co) o[co] += row[3 * tap + co];
+      for (int co = 0; co < NCO; ++co) o[co] += row[NCO * tap + co];
     }
     float* dst = p.y + (((int64_t)n * p.Ho + oy) * p.Wo + ox) * p.Cout;
     for (int co = 0; co < p.Cout; ++co) dst[co] = o[co] + (p.bias ? p.bias[co] : 0.f);
@@ -643,17 +676,19 @@ int odvae_conv3x3_f32(int mode, const float* x, int N, int Hi, int Wi, int Cin,
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool narrow = Cout <= 32;
   dim3 block(256);
-  if (mode == 0 && Cin == 3 && Wo % 32 == 0) {
+  if (mode == 0 && (Cin == 3 || Cin == 4) && Wo % 32 == 0) {
     const int64_t ntiles = (int64_t)N * Ho * (Wo / 32);
     const int blocks = (int)std::min<int64_t>(1024, ceil_div64(ntiles, 4));
-    hipLaunchKernelGGL(conv3x3_thin_in_kernel, dim3(blocks, ceil_div(Cout, 128)), block, 0, st, p);
+    if (Cin == 3) hipLaunchKernelGGL(conv3x3_thin_in_kernel<3>, dim3(blocks, ceil_div(Cout, 128)), block, 0, st, p);
+    else hipLaunchKernelGGL(conv3x3_thin_in_kernel<4>, dim3(blocks, ceil_div(Cout, 128)), block, 0, st, p);
     ODVAE_LAUNCH_CHECK("conv3x3 thin-in");
     return ODVAE_OK;
   }
-  if (mode == 0 && Cout <= 3 && Cin == 128 && !residual && act == 0) {      // decoder.conv_out: the reconstruction
+  if (mode == 0 && Cout <= 4 && Cin == 128 && !residual && act == 0) {      // decoder.conv_out: the reconstruction (RGB, or RGBA)
     p.tiles_x = ceil_div(Wo, TO_TW); p.tiles_y = ceil_div(Ho, TO_TH);
     ODVAE_CHECK_ARG((int64_t)p.tiles_x * p.tiles_y * N < (1ll << 31), "conv3x3: too many tiles");
-    hipLaunchKernelGGL(conv3x3_thin_out_kernel<128>, dim3((unsigned)(p.tiles_x * p.tiles_y * N)), block, 0, st, p);
+    if (Cout <= 3) hipLaunchKernelGGL((conv3x3_thin_out_kernel<128, 3>), dim3((unsigned)(p.tiles_x * p.tiles_y * N)), block, 0, st, p);
+    else hipLaunchKernelGGL((conv3x3_thin_out_kernel<128, 4>), dim3((unsigned)(p.tiles_x * p.tiles_y * N)), block, 0, st, p);
     ODVAE_LAUNCH_CHECK("conv3x3 thin-out");
     return ODVAE_OK;
   }

@@ -13,7 +13,7 @@
 //
 // Map of the file.  kind is what odvae_conv3x3_wgrad_plan reports; make_plan chooses it from the mode and the channel counts alone:
 //   kind | kernel(s)                                   | block, pixel tile                | chosen when
-//   0    | conv3x3_wgrad_thin_kernel, thin_colsum_kernel,| 128 wide channels, whole image   | thin_applies: mode 0, Cin <= 3 or Cout <= 3 (conv_in,
+//   0    | conv3x3_wgrad_thin_kernel, thin_colsum_kernel,| 128 wide channels, whole image   | thin_applies: mode 0, Cin <= 4 or Cout <= 4 (conv_in,
 //        | conv3x3_wgrad_thin_reduce_kernel             | rows, no LDS                     | conv_out), W % 16 == 0, the wide side % 4 == 0 and >= 32
 //   1 v1 | conv3x3_wgrad_kernel<MODE, TH>               | 64 ci x 64 co, 8 x 16 (mode 1:   | everything else: Cin % 4 or Cout % 4 != 0, or Cout <= 64;
 //        |                                              | 4 x 16), 256 threads, 1024 blocks| mode 5 with such channel counts runs MODE 2
@@ -796,49 +796,68 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_down_split_kernel(WgradP
 struct ThinParams {
   const float* big;     // [N][H][W][Cb]
   const float* small;   // [N][H][W][Cs]
-  float* slab;          // [waves][CbP][32]
+  float* slab;          // [waves][CbP][32 * NT]
   int N, H, W, Cb, Cs, CbP, sign, ones_col;   // ones_col: column index that multiplies 1.0 (bias gradient), or -1
 };
 
 // One 16-byte load per lane is a pixel's channels 4i..4i+3: component t feeds channel tile t, whose row i is therefore
 // channel c0 + 4i + t (any channel order will do, the slab store undoes it) -- a wave reads whole 512-byte pixel rows.
+// NT column tiles of 32: one for Cs <= 3 (27 tap columns + the ones column), two for Cs = 4 (36 + 1: image_mask_key's 4-channel conv_out
+// and a 4-channel conv_in); the wide tensor is still read once, each of its fragments feeds NT MFMA chains.
+template <int NT>
 __global__ __launch_bounds__(256) void conv3x3_wgrad_thin_kernel(ThinParams p) {
   const int lane = threadIdx.x & 63, li = lane & 31, kk = lane >> 5;
   const int wave_in_grid = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
   const int c0 = blockIdx.y * 128;
-  // this lane's B column: tap and channel of the thin side
-  const int j = li, tap = j / p.Cs, cs = j % p.Cs;
-  const bool jtap = j < 9 * p.Cs;
-  const int dyj = p.sign * (tap / 3 - 1), dxj = p.sign * (tap % 3 - 1);
-  const bool ones = j == p.ones_col;
+  // this lane's B columns (one per column tile): tap and channel of the thin side
+  int cs[NT], dyj[NT], dxj[NT];
+  bool jtap[NT], ones[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int j = 32 * t + li, tap = j / p.Cs;
+    cs[t] = j % p.Cs;
+    jtap[t] = j < 9 * p.Cs;
+    dyj[t] = p.sign * (tap / 3 - 1); dxj[t] = p.sign * (tap % 3 - 1);
+    ones[t] = j == p.ones_col;
+  }
   // channel quads past Cb (Cb not a multiple of 128): clamped address + select, never a guarded load
   const bool cok = c0 + 4 * li < p.Cb;
   const int coff = min(c0 + 4 * li, p.Cb - 4);
-  f32x16 acc[4];
+  f32x16 acc[NT][4];
 #pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
+  for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[t][ct][r] = 0.f;
 
   const int rows = p.N * p.H;
   constexpr int CH = 8;   // k-steps per chunk (16 pixels)
   float4 a_cur[CH], a_nxt[CH];
-  float b_cur[CH], b_nxt[CH];
+  float b_cur[NT][CH], b_nxt[NT][CH];
   for (int row = wave_in_grid; row < rows; row += nwaves) {
     const int y = row % p.H;
-    const int ys = y + dyj;
-    const bool rowok = jtap && ys >= 0 && ys < p.H;
-    const float* srow = p.small + ((int64_t)(row - y + min(max(ys, 0), p.H - 1)) * p.W) * p.Cs + cs;
+    bool rowok[NT];
+    const float* srow[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int ys = y + dyj[t];
+      rowok[t] = jtap[t] && ys >= 0 && ys < p.H;
+      srow[t] = p.small + ((int64_t)(row - y + min(max(ys, 0), p.H - 1)) * p.W) * p.Cs + cs[t];
+    }
     const float* brow = p.big + (int64_t)row * p.W * p.Cb + coff;
-    auto load_chunk = [&](int x0, float4 (&a)[CH], float (&b)[CH]) {
+    auto load_chunk = [&](int x0, float4 (&a)[CH], float (&b)[NT][CH]) {
 #pragma unroll
       for (int s = 0; s < CH; ++s) {
         const int x = x0 + 2 * s + kk;
         const float4 v4 = *reinterpret_cast<const float4*>(brow + (int64_t)x * p.Cb);
         a[s] = cok ? v4 : make_float4(0.f, 0.f, 0.f, 0.f);
-        const int xs = x + dxj;
-        const float v = srow[(int64_t)min(max(xs, 0), p.W - 1) * p.Cs];
-        b[s] = ones ? 1.f : ((rowok && xs >= 0 && xs < p.W) ? v : 0.f);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const int xs = x + dxj[t];
+          const float v = srow[t][(int64_t)min(max(xs, 0), p.W - 1) * p.Cs];
+          b[t][s] = ones[t] ? 1.f : ((rowok[t] && xs >= 0 && xs < p.W) ? v : 0.f);
+        }
       }
     };
     load_chunk(0, a_cur, b_cur);
@@ -847,40 +866,49 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_thin_kernel(ThinParams p) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int s = 0; s < CH; ++s) {
-        acc[0] = mfma32(a_cur[s].x, b_cur[s], acc[0]);
-        acc[1] = mfma32(a_cur[s].y, b_cur[s], acc[1]);
-        acc[2] = mfma32(a_cur[s].z, b_cur[s], acc[2]);
-        acc[3] = mfma32(a_cur[s].w, b_cur[s], acc[3]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          acc[t][0] = mfma32(a_cur[s].x, b_cur[t][s], acc[t][0]);
+          acc[t][1] = mfma32(a_cur[s].y, b_cur[t][s], acc[t][1]);
+          acc[t][2] = mfma32(a_cur[s].z, b_cur[t][s], acc[t][2]);
+          acc[t][3] = mfma32(a_cur[s].w, b_cur[t][s], acc[t][3]);
+        }
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int s = 0; s < CH; ++s) { b_cur[s] = b_nxt[s]; a_cur[s] = a_nxt[s]; }
+      for (int s = 0; s < CH; ++s) {
+        a_cur[s] = a_nxt[s];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) b_cur[t][s] = b_nxt[t][s];
+      }
     }
   }
-  float* sl = p.slab + (int64_t)wave_in_grid * p.CbP * 32;
+  float* sl = p.slab + (int64_t)wave_in_grid * p.CbP * (32 * NT);
 #pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
+  for (int t = 0; t < NT; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int c = c0 + 4 * acc_row(r, lane) + ct;
-      if (c < p.Cb) sl[c * 32 + li] = acc[ct][r];
-    }
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int c = c0 + 4 * acc_row(r, lane) + ct;
+        if (c < p.Cb) sl[c * (32 * NT) + 32 * t + li] = acc[t][ct][r];
+      }
 }
 
 // partial column sums of the thin tensor (bias gradient of conv_out): part[block][Cs]
 __global__ __launch_bounds__(256) void thin_colsum_kernel(const float* __restrict__ t, int64_t npix, int Cs, float* __restrict__ part) {
-  __shared__ float red[4][3];
-  float s[3] = {0.f, 0.f, 0.f};
+  __shared__ float red[4][4];
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
   for (int64_t px = (int64_t)blockIdx.x * 256 + threadIdx.x; px < npix; px += (int64_t)gridDim.x * 256)
     for (int c = 0; c < Cs; ++c) s[c] += t[px * Cs + c];
-  for (int c = 0; c < 3; ++c) s[c] = wave_sum(s[c]);
-  if ((threadIdx.x & 63) == 0) for (int c = 0; c < 3; ++c) red[threadIdx.x >> 6][c] = s[c];
+  for (int c = 0; c < 4; ++c) s[c] = wave_sum(s[c]);
+  if ((threadIdx.x & 63) == 0) for (int c = 0; c < 4; ++c) red[threadIdx.x >> 6][c] = s[c];
   __syncthreads();
   if (threadIdx.x < Cs) part[blockIdx.x * Cs + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
 // sum the per-wave slabs in a fixed order and scatter into OIHW; sign +1: c = co, thin = ci; sign -1: c = ci, thin = co
-__global__ void conv3x3_wgrad_thin_reduce_kernel(const float* __restrict__ slab, int nwaves, int Cb, int Cs, int CbP, int sign,
+__global__ void conv3x3_wgrad_thin_reduce_kernel(const float* __restrict__ slab, int nwaves, int Cb, int Cs, int CbP, int JW, int sign,
                                                  const float* __restrict__ bpart, int nbpart, int Cin, int Cout,
                                                  float* __restrict__ dw, float* __restrict__ dbias) {
   // block = 16 outputs x 16 parts: part q sums slabs q, q+16, ... (eight loads in flight), then the 16 parts are added in
@@ -888,11 +916,11 @@ __global__ void conv3x3_wgrad_thin_reduce_kernel(const float* __restrict__ slab,
   __shared__ float red[16][17];
   const int part = threadIdx.x >> 4;
   const int idx = blockIdx.x * 16 + (threadIdx.x & 15);
-  if (idx < Cb * 32) {
-    const int c = idx / 32, j = idx % 32;
+  if (idx < Cb * JW) {      // JW: the slab's columns per channel, 32 per column tile of the thin kernel
+    const int c = idx / JW, j = idx % JW;
     float ps = 0.f;
-    const float* src = slab + (int64_t)c * 32 + j;
-    const int64_t wstride = (int64_t)CbP * 32;
+    const float* src = slab + (int64_t)c * JW + j;
+    const int64_t wstride = (int64_t)CbP * JW;
     int w = part;
     for (; w + 7 * 16 < nwaves; w += 8 * 16) {
       float v[8];
@@ -905,8 +933,8 @@ __global__ void conv3x3_wgrad_thin_reduce_kernel(const float* __restrict__ slab,
     red[part][threadIdx.x & 15] = ps;
   }
   __syncthreads();
-  if (part == 0 && idx < Cb * 32) {
-    const int c = idx / 32, j = idx % 32;
+  if (part == 0 && idx < Cb * JW) {
+    const int c = idx / JW, j = idx % JW;
     float s = 0.f;
 #pragma unroll
     for (int q = 0; q < 16; ++q) s += red[q][threadIdx.x & 15];
@@ -915,8 +943,8 @@ __global__ void conv3x3_wgrad_thin_reduce_kernel(const float* __restrict__ slab,
       const int co = sign > 0 ? c : cs, ci = sign > 0 ? cs : c;
       dw[((int64_t)co * Cin + ci) * 9 + tap] = s;
     } else if (sign > 0 && dbias && j == 9 * Cs) dbias[c] = s;
-  } else if (part == 0 && sign < 0 && dbias && idx >= Cb * 32 && idx - Cb * 32 < Cout) {
-    const int co = idx - Cb * 32;
+  } else if (part == 0 && sign < 0 && dbias && idx >= Cb * JW && idx - Cb * JW < Cout) {
+    const int co = idx - Cb * JW;
     float s = 0.f;
     for (int b = 0; b < nbpart; ++b) s += bpart[b * Cs + co];
     dbias[co] = s;
@@ -960,22 +988,24 @@ int bias_rows(const Plan& pl) { return pl.up ? 4 : 1; }
 // what store_taps relies on: one split's slab stays below 2^31 bytes
 bool slab_fits(const Plan& pl) { return (int64_t)slab_taps(pl) * pl.CinP * pl.CoutP * 4 < 0x80000000ll; }
 
-// thin-side kernel: stride-1 conv whose input or output has <= 3 channels (conv_in / conv_out)
-constexpr int THIN_BLOCKS = 1024, THIN_BIAS_BLOCKS = 256;
+// thin-side kernel: stride-1 conv whose input or output has <= 4 channels (conv_in / conv_out; 4: an RGBA reconstruction)
+constexpr int THIN_BLOCKS = 1024, THIN_BIAS_BLOCKS = 256, THIN_MAX = 4;
+// column tiles of 32 the thin side's 9 * Cs tap columns (+ the ones column) take
+int thin_col_tiles(int Cin, int Cout) { return std::min(Cin, Cout) <= 3 ? 1 : 2; }
 bool thin_applies(int mode, int Hi, int Wi, int Cin, int Cout) {
-  const int cb = Cin <= 3 ? Cout : Cin;
-  return mode == 0 && (Cin <= 3) != (Cout <= 3) && Wi % 16 == 0 && cb % 4 == 0 && cb >= 32 &&
+  const int cb = Cin <= THIN_MAX ? Cout : Cin;
+  return mode == 0 && (Cin <= THIN_MAX) != (Cout <= THIN_MAX) && Wi % 16 == 0 && cb % 4 == 0 && cb >= 32 &&
          (int64_t)Hi * Wi * cb * 4 < 0x7FFFFFF0ll;
 }
 size_t thin_workspace_floats(int Cin, int Cout) {
-  const int cb = Cin <= 3 ? Cout : Cin;
-  return (size_t)THIN_BLOCKS * 4 * cb * 32 + (size_t)THIN_BIAS_BLOCKS * 3;
+  const int cb = Cin <= THIN_MAX ? Cout : Cin;
+  return (size_t)THIN_BLOCKS * 4 * cb * 32 * thin_col_tiles(Cin, Cout) + (size_t)THIN_BIAS_BLOCKS * std::max(3, std::min(Cin, Cout));
 }
 // grid of the thin kernel: channel groups of 128 on y, four waves (= four image rows in flight) per block on x
 struct ThinPlan { int groups, blocks; };
 ThinPlan make_thin_plan(int N, int Hi, int Cin, int Cout) {
   ThinPlan tp;
-  tp.groups = ceil_div(Cin <= 3 ? Cout : Cin, 128);
+  tp.groups = ceil_div(Cin <= THIN_MAX ? Cout : Cin, 128);
   tp.blocks = std::max(1, std::min(THIN_BLOCKS / tp.groups, ceil_div(N * Hi, 4)));
   return tp;
 }
@@ -1083,23 +1113,25 @@ int odvae_conv3x3_wgrad_f32(int mode, const float* x, const float* dy, int N, in
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (thin) {
     ThinParams t;
-    const bool in_thin = Cin <= 3;   // conv_in: big = dy, small = x; conv_out: big = x, small = dy
+    const bool in_thin = Cin <= THIN_MAX;   // conv_in: big = dy, small = x; conv_out: big = x, small = dy
     t.big = in_thin ? dy : x; t.small = in_thin ? x : dy;
     t.slab = static_cast<float*>(workspace);
     t.N = N; t.H = Hi; t.W = Wi; t.Cb = in_thin ? Cout : Cin; t.Cs = in_thin ? Cin : Cout; t.CbP = t.Cb;
     t.sign = in_thin ? 1 : -1; t.ones_col = (in_thin && dbias) ? 9 * t.Cs : -1;
     const ThinPlan tp = make_thin_plan(N, Hi, Cin, Cout);
     const int groups = tp.groups, blocks = tp.blocks;
-    hipLaunchKernelGGL(conv3x3_wgrad_thin_kernel, dim3(blocks, groups), dim3(256), 0, st, t);
+    const int nt = thin_col_tiles(Cin, Cout), jw = 32 * nt;
+    if (nt == 1) hipLaunchKernelGGL(conv3x3_wgrad_thin_kernel<1>, dim3(blocks, groups), dim3(256), 0, st, t);
+    else hipLaunchKernelGGL(conv3x3_wgrad_thin_kernel<2>, dim3(blocks, groups), dim3(256), 0, st, t);
     ODVAE_LAUNCH_CHECK("conv3x3_wgrad thin");
-    float* bpart = t.slab + (size_t)THIN_BLOCKS * 4 * t.Cb * 32;
+    float* bpart = t.slab + (size_t)THIN_BLOCKS * 4 * t.Cb * jw;
     if (!in_thin && dbias) {
       hipLaunchKernelGGL(thin_colsum_kernel, dim3(THIN_BIAS_BLOCKS), dim3(256), 0, st, dy, (int64_t)N * Hi * Wi, Cout, bpart);
       ODVAE_LAUNCH_CHECK("conv3x3_wgrad thin bias");
     }
-    const int items = t.Cb * 32 + (in_thin ? 0 : Cout);
+    const int items = t.Cb * jw + (in_thin ? 0 : Cout);
     hipLaunchKernelGGL(conv3x3_wgrad_thin_reduce_kernel, dim3(ceil_div(items, 16)), dim3(256), 0, st,
-                       t.slab, blocks * 4, t.Cb, t.Cs, t.CbP, t.sign, bpart, THIN_BIAS_BLOCKS, Cin, Cout, dw, dbias);
+                       t.slab, blocks * 4, t.Cb, t.Cs, t.CbP, jw, t.sign, bpart, THIN_BIAS_BLOCKS, Cin, Cout, dw, dbias);
     ODVAE_LAUNCH_CHECK("conv3x3_wgrad thin reduce");
     return ODVAE_OK;
   }

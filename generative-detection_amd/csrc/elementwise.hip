@@ -366,6 +366,101 @@ __global__ __launch_bounds__(256) void l1_bwd_kernel(const float* __restrict__ x
   }
 }
 
+// ---- RGBA reconstruction terms (image_mask_key: contperceptual.py:230-257,166-174 on a 4-channel reconstruction) ----------------
+// One pass over rec [N][HW][4] (one 16-byte load per pixel), rgb [N][HW][3] (three 4-byte loads: any 4-byte aligned base), alpha [N][HW]
+// and box [N][HW] (nullable = 1).  Per pixel, every operation separately rounded (plain operators under
+// `fp contract(off)`: hipcc fuses xm - rec * w into one multiply-add otherwise, and __fmul_rn does not stop it):
+//   xm_c = rgb_c * w, rm_c = rec_c * w (c < 3), am = alpha * w, ra = rec_3 * w
+//   l1 += |xm_0 - rm_0| + |xm_1 - rm_1| + |xm_2 - rm_2|  (added in this order),  d = am - ra,  mask += |d| (l1) or d * d (l2)
+// and the four masked copies, each skipped when its pointer is null.  Stage 1 leaves part[0][n][blk] (l1) and part[1][n][blk] (mask);
+// rgba_final_kernel adds a sample's partials in f64 in a fixed order: no atomics.
+__global__ __launch_bounds__(256) void rgba_terms_kernel(const float4* __restrict__ rec, const float* __restrict__ rgb, const float* __restrict__ alpha,
+                                                         const float* __restrict__ box, float* __restrict__ part, float* __restrict__ rec_rgb_m,
+                                                         float* __restrict__ gt_rgb_m, float4* __restrict__ rec_rgba_m, float4* __restrict__ gt_rgba_m,
+                                                         int HW, int l2) {
+#pragma clang fp contract(off)
+  __shared__ float sh[4];
+  const int n = blockIdx.y, N = gridDim.y;
+  const int64_t base = (int64_t)n * HW;
+  float s1 = 0.f, s2 = 0.f;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < HW; p += (int64_t)gridDim.x * 256) {
+    const int64_t px = base + p;
+    const float4 r = rec[px];
+    const float w = box ? box[px] : 1.f;
+    const float x0 = rgb[px * 3] * w, x1 = rgb[px * 3 + 1] * w, x2 = rgb[px * 3 + 2] * w;
+    const float am = alpha[px] * w;
+    const float4 rm = make_float4(r.x * w, r.y * w, r.z * w, r.w * w);
+    float t = fabsf(x0 - rm.x);
+    t = t + fabsf(x1 - rm.y);
+    t = t + fabsf(x2 - rm.z);
+    s1 = s1 + t;
+    const float d = am - rm.w;
+    s2 = s2 + (l2 ? d * d : fabsf(d));
+    if (rec_rgb_m) { rec_rgb_m[px * 3] = rm.x; rec_rgb_m[px * 3 + 1] = rm.y; rec_rgb_m[px * 3 + 2] = rm.z; }
+    if (gt_rgb_m) { gt_rgb_m[px * 3] = x0; gt_rgb_m[px * 3 + 1] = x1; gt_rgb_m[px * 3 + 2] = x2; }
+    if (rec_rgba_m) rec_rgba_m[px] = rm;
+    if (gt_rgba_m) gt_rgba_m[px] = make_float4(x0, x1, x2, am);
+  }
+  if (!part) return;      // (block-uniform) the caller wants the masked copies alone: the discriminator phase
+  s1 = block_sum(s1, sh);
+  s2 = block_sum(s2, sh);
+  if (threadIdx.x == 0) {
+    part[(int64_t)n * gridDim.x + blockIdx.x] = s1;
+    part[((int64_t)N + n) * gridDim.x + blockIdx.x] = s2;
+  }
+}
+// grid (N, 2): out0[n] / out1[n] = the sum of the sample's nblk partials
+__global__ void rgba_final_kernel(const float* __restrict__ part, int nblk, float* __restrict__ out0, float* __restrict__ out1) {
+  const int n = blockIdx.x, which = blockIdx.y, N = gridDim.x;
+  const float* p = part + ((int64_t)which * N + n) * nblk;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 64) s += (double)p[i];
+  s = wave_sum_f64(s);
+  if (threadIdx.x == 0) (which ? out1 : out0)[n] = (float)s;
+}
+// d_rec [N][HW][4], overwritten.  c < 3: ((g_l1[n] * sign(rm_c - xm_c)) * w + g_rgb_c * w) + g_rgba_c * w (l1_bwd_kernel's sign rule);
+// c = 3: (g_mask[n] * (sign(ra - am) or 2 * (ra - am))) * w + g_rgba_3 * w.  A null gradient is a zero and adds nothing.
+__global__ __launch_bounds__(256) void rgba_terms_bwd_kernel(const float4* __restrict__ rec, const float* __restrict__ rgb, const float* __restrict__ alpha,
+                                                             const float* __restrict__ box, const float* __restrict__ g_l1, const float* __restrict__ g_mask,
+                                                             const float* __restrict__ g_rgb, const float4* __restrict__ g_rgba, float4* __restrict__ d_rec,
+                                                             int HW, int l2) {
+#pragma clang fp contract(off)
+  const int n = blockIdx.y;      // grid (blocks, N), as the forward: no division per pixel
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < HW; q += (int64_t)gridDim.x * 256) {
+    const int64_t px = (int64_t)n * HW + q;
+    const float w = box ? box[px] : 1.f;
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+    if (g_l1) {
+      const float4 r = rec[px];
+      const float g = g_l1[n];
+      const float rv[3] = {r.x, r.y, r.z};
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float a = rv[c] * w, b = rgb[px * 3 + c] * w;
+        const float d = a - b;
+        const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+        o[c] = (g * sg) * w;
+      }
+    }
+    if (g_mask) {
+      const float a = rec[px].w * w, b = alpha[px] * w;
+      const float d = a - b;
+      const float e = l2 ? 2.f * d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
+      o[3] = (g_mask[n] * e) * w;
+    }
+    if (g_rgb) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) { const float t = g_rgb[px * 3 + c] * w; o[c] = o[c] + t; }
+    }
+    if (g_rgba) {
+      const float4 g = g_rgba[px];
+      const float t0 = g.x * w, t1 = g.y * w, t2 = g.z * w, t3 = g.w * w;
+      o[0] = o[0] + t0; o[1] = o[1] + t1; o[2] = o[2] + t2; o[3] = o[3] + t3;
+    }
+    d_rec[px] = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
 // ---- column sums (bias gradient of the 1x1 convolutions): out[c] = sum_rows x[row][c] ------------------
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ x, int64_t rows, int C,
                                                              int rows_per_block, float* __restrict__ part) {
@@ -927,6 +1022,52 @@ int odvae_l1_masked_bwd_f32(const float* x, const float* xr, const float* mask, 
   ODVAE_CHECK_ARG(x && xr && g && dxr && N > 0 && HW > 0 && C > 0, "l1_masked_bwd: bad arguments");
   hipLaunchKernelGGL(l1_bwd_kernel, dim3(grid_1d((int64_t)N * HW * C)), dim3(256), 0, static_cast<hipStream_t>(stream), x, xr, mask, g, dxr, N, HW, C);
   ODVAE_LAUNCH_CHECK("l1_masked_bwd");
+  return ODVAE_OK;
+}
+
+// the sample's pixels are cut over at most this many blocks (the kernel's grid cap); the workspace holds 2 * N * that many floats
+static const int kRgbaBlocks = 256;
+
+size_t odvae_rgba_terms_workspace_bytes(int N) { return (size_t)2 * (size_t)std::max(N, 0) * kRgbaBlocks * sizeof(float); }
+
+int odvae_rgba_terms_f32(const float* rec, const float* rgb_gt, const float* mask_gt, const float* box, int l2, float* l1_sum, float* mask_sum,
+                         float* rec_rgb_m, float* gt_rgb_m, float* rec_rgba_m, float* gt_rgba_m, int N, int HW,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(rec && rgb_gt && mask_gt && N > 0 && N <= 65535 && HW > 0, "rgba_terms: bad arguments");
+  ODVAE_CHECK_ARG((l1_sum == nullptr) == (mask_sum == nullptr), "rgba_terms: l1_sum and mask_sum must both be set or both null");
+  const bool sums = l1_sum != nullptr;
+  ODVAE_CHECK_ARG(sums || rec_rgb_m || gt_rgb_m || rec_rgba_m || gt_rgba_m, "rgba_terms: nothing to compute");
+  ODVAE_CHECK_ARG((((uintptr_t)rec | (uintptr_t)rec_rgba_m | (uintptr_t)gt_rgba_m) & 15) == 0,
+                  "rgba_terms: rec, rec_rgba_m and gt_rgba_m must be 16-byte aligned");
+  ODVAE_CHECK_ARG((((uintptr_t)rgb_gt | (uintptr_t)mask_gt | (uintptr_t)box | (uintptr_t)rec_rgb_m | (uintptr_t)gt_rgb_m) & 3) == 0,
+                  "rgba_terms: a float array is not 4-byte aligned");
+  if (sums && (!workspace || workspace_bytes < odvae_rgba_terms_workspace_bytes(N))) {
+    odvae_set_error("rgba_terms: needs %zu workspace bytes", odvae_rgba_terms_workspace_bytes(N));
+    return ODVAE_ERR_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* part = sums ? static_cast<float*>(workspace) : nullptr;
+  const int nblk = (int)std::min<int64_t>(ceil_div64(HW, 256), kRgbaBlocks);
+  hipLaunchKernelGGL(rgba_terms_kernel, dim3(nblk, N), dim3(256), 0, st, reinterpret_cast<const float4*>(rec), rgb_gt, mask_gt, box, part,
+                     rec_rgb_m, gt_rgb_m, reinterpret_cast<float4*>(rec_rgba_m), reinterpret_cast<float4*>(gt_rgba_m), HW, l2 ? 1 : 0);
+  ODVAE_LAUNCH_CHECK("rgba_terms");
+  if (!sums) return ODVAE_OK;
+  hipLaunchKernelGGL(rgba_final_kernel, dim3(N, 2), dim3(64), 0, st, part, nblk, l1_sum, mask_sum);
+  ODVAE_LAUNCH_CHECK("rgba_terms(final)");
+  return ODVAE_OK;
+}
+
+int odvae_rgba_terms_bwd_f32(const float* rec, const float* rgb_gt, const float* mask_gt, const float* box, int l2, const float* g_l1,
+                             const float* g_mask, const float* g_rec_rgb_m, const float* g_rec_rgba_m, float* d_rec, int N, int HW, void* stream) {
+  ODVAE_CHECK_ARG(rec && rgb_gt && mask_gt && d_rec && N > 0 && N <= 65535 && HW > 0, "rgba_terms_bwd: bad arguments");
+  ODVAE_CHECK_ARG((((uintptr_t)rec | (uintptr_t)g_rec_rgba_m | (uintptr_t)d_rec) & 15) == 0,
+                  "rgba_terms_bwd: rec, g_rec_rgba_m and d_rec must be 16-byte aligned");
+  ODVAE_CHECK_ARG((((uintptr_t)rgb_gt | (uintptr_t)mask_gt | (uintptr_t)box | (uintptr_t)g_l1 | (uintptr_t)g_mask | (uintptr_t)g_rec_rgb_m) & 3) == 0,
+                  "rgba_terms_bwd: a float array is not 4-byte aligned");
+  hipLaunchKernelGGL(rgba_terms_bwd_kernel, dim3(grid_1d(HW, std::max(1, 8192 / N)), N), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const float4*>(rec), rgb_gt, mask_gt, box, g_l1, g_mask, g_rec_rgb_m,
+                     reinterpret_cast<const float4*>(g_rec_rgba_m), reinterpret_cast<float4*>(d_rec), HW, l2 ? 1 : 0);
+  ODVAE_LAUNCH_CHECK("rgba_terms_bwd");
   return ODVAE_OK;
 }
 

@@ -396,6 +396,43 @@ class PoseLoss(LPIPSWithDiscriminator):
             s = s + self.perceptual_weight * p_loss.reshape(n) * chw
         return s, chw
 
+    @staticmethod
+    def _checked_mask(mask_gt, rgb_gt, dec_obj):
+        """The alpha target of image_mask_key as f32 [B,1,H,W] on the images' device (float, bool or uint8 in; values as they are)."""
+        if not torch.is_tensor(mask_gt) or mask_gt.dim() != 4 or tuple(mask_gt.shape) != (rgb_gt.shape[0], 1) + tuple(rgb_gt.shape[2:]):
+            raise ValueError("mask_gt must be [B,1,H,W] = %s for rgb_gt %s, got %s" % ((rgb_gt.shape[0], 1) + tuple(rgb_gt.shape[2:]),
+                             tuple(rgb_gt.shape), tuple(mask_gt.shape) if torch.is_tensor(mask_gt) else type(mask_gt)))
+        if dec_obj.dim() != 4 or dec_obj.shape[1] != 4 or dec_obj.shape[0] != rgb_gt.shape[0] or dec_obj.shape[2:] != rgb_gt.shape[2:]:
+            # (the reference dies here with a shape error in its discriminator call: cat(rgb_gt, mask_gt) has four channels)
+            raise ValueError("image_mask_key needs a 4-channel reconstruction (ddconfig.out_ch: 4, disc_in_channels: 4), got dec_obj %s"
+                             % (tuple(dec_obj.shape),))
+        return mask_gt.to(rgb_gt.device).float()
+
+    def _rgba_rec_sums(self, rgb_gt, mask_gt, reconstructions, mask_2d_bbox, use_pixel_loss, need_d_input):
+        """(rec_sums, chw, mask_sums, rec_rgba_m): _rec_sums on the RGB part of a 4-channel reconstruction, the per-sample sums of the
+        element-wise mask loss |mask_gt*m - rec[:, 3:]*m| (or its square) and reconstructions * m for the discriminator (None unless asked)."""
+        n, _, h, w = rgb_gt.shape
+        chw = float(3 * h * w)
+        perceptual = self.perceptual_weight > 0
+        l1_sums, mask_sums, rec_rgb_m, gt_rgb_m, rec_rgba_m, _ = ops.rgba_terms(
+            reconstructions, rgb_gt, mask_gt, mask_2d_bbox, l2=not isinstance(self.mask_loss, nn.L1Loss), rec_rgb_m=perceptual,
+            gt_rgb_m=perceptual, rec_rgba_m=need_d_input)
+        s = l1_sums if use_pixel_loss else torch.zeros(n, device=rgb_gt.device)
+        if perceptual:
+            self._check_perceptual_weights()
+            p_loss = self.perceptual_loss(gt_rgb_m, rec_rgb_m)
+            s = s + self.perceptual_weight * p_loss.reshape(n) * chw
+        return s, chw, mask_sums, rec_rgba_m
+
+    def _mask_loss_mean(self, mask_sums, count):
+        """(mask_loss, weighted_mask_loss) of get_mask_loss as scalars: the mean over B*H*W of the element-wise mask loss -- what the
+        reference logs -- and mask_weight times it.  QUIRK (:169): NOT multiplied by mask_bg (the reference computes that product and drops it)."""
+        if self.use_mask_loss:
+            mask_loss = torch.sum(mask_sums) / float(count)
+            return mask_loss, self.mask_weight * mask_loss
+        zero = torch.zeros((), device=mask_sums.device)
+        return zero, zero
+
     def _get_nll_loss(self, rec_sums, chw, mask_bg, weights=None):
         eps = 1e-8
         nll_sums = rec_sums / (torch.exp(self.logvar) + eps) + self.logvar * chw
@@ -417,15 +454,17 @@ class PoseLoss(LPIPSWithDiscriminator):
         mask_bg = torch.zeros_like(class_gt, device=rgb_gt.device)
         mask_bg[class_gt != BACKGROUND_CLASS_IDX] = 1
         if mask_gt is not None:
-            raise NotImplementedError("image_mask_key is None in the OD-VAE configs; alpha-mask inputs are not on the HIP path")
-        self.use_mask_loss = False  # (:232,248) no mask channel on either side
+            mask_gt = self._checked_mask(mask_gt, rgb_gt, dec_obj)      # image_mask_key: gt_obj = cat(rgb_gt, mask_gt) (:235)
+        else:
+            self.use_mask_loss = False  # QUIRK (:232,248): no mask channel on either side -- and sticky: a later call WITH a mask finds it off
+        rgba = mask_gt is not None
         reconstructions = dec_obj
         recon_rgb = reconstructions[:, :3, :, :] if reconstructions.shape[1] != 3 else reconstructions
         if optimizer_idx == 1:
             # The discriminator phase returns d_loss and three logit statistics only (contperceptual.py:352-375).  The reference
             # evaluates the pose, reconstruction (incl. LPIPS: 16 VGG convs on two image sets) and KL terms first and then does not use
             # them; they have no consumer here either, so they are not evaluated: same outputs, 11 ms of a 113 ms step.
-            return self._discriminator_phase(rgb_gt, reconstructions, mask_2d_bbox, mask_bg, global_step, cond, split)
+            return self._discriminator_phase(rgb_gt, reconstructions, mask_2d_bbox, mask_bg, global_step, cond, split, mask_gt=mask_gt)
 
         pose_rec = dec_pose[:, :POSE_6D_DIM]
         lhw_rec = dec_pose[:, POSE_6D_DIM:POSE_6D_DIM + LHW_DIM]
@@ -445,9 +484,16 @@ class PoseLoss(LPIPSWithDiscriminator):
             # QUIRK (:269): (gt, pred) are passed into the (pred, gt) slots; symmetric for l1/l2
             pose_loss, weighted_pose_loss, t1_loss, t2_loss, t3_loss, v3_loss = self.compute_pose_loss(pose_gt, pose_rec, mask_bg)
             fill_factor_loss, weighted_fill_factor_loss = self.compute_fill_factor_loss(fill_factor_gt, fill_factor_rec.squeeze(), mask_bg)
-        mask_loss, weighted_mask_loss = self.get_mask_loss(None, None, mask_bg)
-
-        rec_sums, chw = self._rec_sums(rgb_gt, recon_rgb, mask_2d_bbox, use_pixel_loss)
+        if rgba:
+            # one pass over the 4-channel reconstruction: the L1 sums over RGB, the mask-loss sums over alpha, the masked RGB pair of the
+            # LPIPS-style net and D's masked RGBA input (ops.rgba_terms) in place of l1_masked_sum + three mul_mask + the channel slice
+            need_d_input = optimizer_idx == 0 and (self.disc_factor > 0.0 or self.log_exact_g_loss
+                                                   or (self.discriminator.training and self.discriminator.actnorm_uninitialized()))
+            rec_sums, chw, mask_sums, rec_rgba_m = self._rgba_rec_sums(rgb_gt, mask_gt, reconstructions, mask_2d_bbox, use_pixel_loss, need_d_input)
+            mask_loss, weighted_mask_loss = self._mask_loss_mean(mask_sums, mask_gt.numel())
+        else:
+            mask_loss, weighted_mask_loss = self.get_mask_loss(None, None, mask_bg)
+            rec_sums, chw = self._rec_sums(rgb_gt, recon_rgb, mask_2d_bbox, use_pixel_loss)
         nll_loss, weighted_nll_loss = self._get_nll_loss(rec_sums, chw, mask_bg, weights)
         rec_mean = rec_sums.detach().sum() / (rec_sums.numel() * chw)
         kl_loss_obj = self._get_kl_loss(posterior_obj, mask_bg)
@@ -458,7 +504,7 @@ class PoseLoss(LPIPSWithDiscriminator):
         if optimizer_idx == 0:
             assert cond is None and not self.disc_conditional
             if self.disc_factor > 0.0:
-                logits_fake = self.discriminator(ops.mul_mask(reconstructions, mask_2d_bbox))
+                logits_fake = self.discriminator(rec_rgba_m if rgba else ops.mul_mask(reconstructions, mask_2d_bbox))
                 g_loss = -torch.mean(logits_fake * bg4)
             elif self.log_exact_g_loss or (self.discriminator.training and self.discriminator.actnorm_uninitialized()):
                 # discriminator off: the reference still evaluates D(x_rec) (its BatchNorm running statistics move too) and
@@ -467,7 +513,8 @@ class PoseLoss(LPIPSWithDiscriminator):
                 # use_actnorm: the reference's ActNorm layers initialise from THIS tensor on the first training batch, so the
                 # forward also runs while any of them is uninitialised; afterwards the shortcut below applies again.
                 with torch.no_grad():
-                    g_loss = -torch.mean(self.discriminator(ops.mul_mask(reconstructions.detach(), mask_2d_bbox)) * bg4)
+                    d_in = rec_rgba_m.detach() if rgba else ops.mul_mask(reconstructions.detach(), mask_2d_bbox)
+                    g_loss = -torch.mean(self.discriminator(d_in) * bg4)
                 if not self.log_exact_g_loss:     # the forward ran for the initialisation alone: the logged value stays the shortcut's 0
                     g_loss = torch.zeros((), device=rgb_gt.device)
             else:
@@ -495,6 +542,10 @@ class PoseLoss(LPIPSWithDiscriminator):
                 # one pass: the reconstruction-dependent terms enter by VALUE (same expression, same order of additions) ...
                 wn = weighted_nll_loss.detach() if one_pass is not None else weighted_nll_loss
                 gl = g_loss.detach() if one_pass is not None else g_loss
+                # DEVIATION (image_mask_key with use_mask_loss): the reference leaves weighted_mask_loss unreduced here
+                # (:168-170), so its `loss` is a [B,1,H,W] tensor no trainer can back-propagate; weighted_mask_loss is mask_weight * the MEAN
+                # of the element-wise mask loss instead -- the value the reference logs as total_loss, with its gradient.  The term keeps its
+                # own graph under the one-pass adaptive weight (not detached, not in the surrogate).
                 loss = (weighted_pose_loss + weighted_mask_loss.to(rgb_gt.device) + wn + weighted_class_loss
                         + weighted_bbox_loss + weighted_fill_factor_loss + self.kl_weight_obj * kl_loss_obj
                         + self.kl_weight_bbox * kl_loss_obj_bbox + d_weight.to(rgb_gt.device) * disc_factor * gl)
@@ -541,13 +592,19 @@ class PoseLoss(LPIPSWithDiscriminator):
 
         return None      # (any other optimizer_idx: the reference falls off the end of forward as well)
 
-    def _discriminator_phase(self, rgb_gt, reconstructions, mask_2d_bbox, mask_bg, global_step, cond, split):
+    def _discriminator_phase(self, rgb_gt, reconstructions, mask_2d_bbox, mask_bg, global_step, cond, split, mask_gt=None):
         """optimizer_idx == 1 (contperceptual.py:352-375): hinge / vanilla loss of the discriminator on the masked target and the masked,
-        detached reconstruction; background samples (mask_bg == 0) drop out of the logits."""
+        detached reconstruction; background samples (mask_bg == 0) drop out of the logits.  mask_gt (image_mask_key): the target is
+        cat(rgb_gt, mask_gt) and both masked 4-channel inputs come from one pass (ops.rgba_terms)."""
         assert cond is None
         bg4 = mask_bg.reshape(-1, 1, 1, 1)
-        logits_real = self.discriminator(ops.mul_mask(rgb_gt, mask_2d_bbox).detach())
-        logits_fake = self.discriminator(ops.mul_mask(reconstructions, mask_2d_bbox).detach())
+        if mask_gt is not None:
+            terms = ops.rgba_terms(reconstructions.detach(), rgb_gt, mask_gt, mask_2d_bbox, rec_rgba_m=True, gt_rgba_m=True, sums=False)
+            logits_real = self.discriminator(terms[5])
+            logits_fake = self.discriminator(terms[4])
+        else:
+            logits_real = self.discriminator(ops.mul_mask(rgb_gt, mask_2d_bbox).detach())
+            logits_fake = self.discriminator(ops.mul_mask(reconstructions, mask_2d_bbox).detach())
         disc_factor = adopt_weight(self.disc_factor, global_step, threshold=self.discriminator_iter_start)
         logits_real = logits_real * bg4
         logits_fake = logits_fake * bg4

@@ -153,6 +153,64 @@ def l1_masked_sum(x, xr, mask=None):
     return _L1MaskedSum.apply(x, xr, mask)
 
 
+def _aligned16(t):
+    """`t` itself, or a copy of the same strides where its base is not 16-byte aligned (a view into a larger buffer)."""
+    return t if t.data_ptr() % 16 == 0 else torch.empty_like(t).copy_(t)
+
+
+class _RgbaTerms(Function):
+    """image_mask_key: every reconstruction-side term of PoseLoss on a 4-channel reconstruction from one pass (contperceptual.py:230-257):
+    the per-sample L1 sums over RGB, the per-sample mask-loss sums over alpha, and the box-masked copies the LPIPS-style net (RGB) and the
+    discriminator (RGBA) read.  Differentiable w.r.t. `rec` alone; the backward is one pass as well."""
+
+    @staticmethod
+    def forward(ctx, rec, rgb_gt, mask_gt, box, l2, want, sums):
+        L = _L()
+        rec = _aligned16(_cl(rec))
+        rgb = _cl(rgb_gt.detach())
+        n, c, h, w = rec.shape
+        if c != 4 or tuple(rgb.shape) != (n, 3, h, w) or mask_gt.numel() != n * h * w or (box is not None and box.numel() != n * h * w):
+            raise ValueError("rgba_terms: rec %s, rgb_gt %s, mask_gt %s, box %s" % (tuple(rec.shape), tuple(rgb.shape), tuple(mask_gt.shape),
+                                                                                    None if box is None else tuple(box.shape)))
+        a = mask_gt.detach().to(rec.device).float().reshape(n, h * w).contiguous()
+        m = box.detach().to(rec.device).float().reshape(n, h * w).contiguous() if box is not None else None
+        _lib.require_device(a, *(() if m is None else (m,)))
+        l1_sums = torch.empty(n, dtype=torch.float32, device=rec.device) if sums else None
+        mask_sums = torch.empty(n, dtype=torch.float32, device=rec.device) if sums else None
+        outs = [(_new_cl(n, cc, h, w, rec) if flag else None) for flag, cc in zip(want, (3, 3, 4, 4))]
+        wp, wn = _ws(L.odvae_rgba_terms_workspace_bytes(n), rec) if sums else (None, 0)
+        _lib.check(L.odvae_rgba_terms_f32(rec.data_ptr(), rgb.data_ptr(), a.data_ptr(), _lib.ptr(m), int(l2), _lib.ptr(l1_sums),
+                                          _lib.ptr(mask_sums), _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]), _lib.ptr(outs[3]),
+                                          n, h * w, wp, wn, _lib.stream_ptr()), "rgba_terms")
+        ctx.save_for_backward(rec, rgb, a, m)
+        ctx.l2 = int(l2)
+        ctx.set_materialize_grads(False)      # an output nobody differentiated arrives as None, and its term is skipped
+        ctx.mark_non_differentiable(*[t for t in (outs[1], outs[3]) if t is not None])      # the target's copies (one call: a second replaces it)
+        return (l1_sums, mask_sums) + tuple(outs)
+
+    @staticmethod
+    def backward(ctx, g_l1, g_mask, g_rgb, _g_gt_rgb, g_rgba, _g_gt_rgba):
+        L = _L()
+        rec, rgb, a, m = ctx.saved_tensors
+        n, c, h, w = rec.shape
+        g_l1 = None if g_l1 is None else g_l1.contiguous()
+        g_mask = None if g_mask is None else g_mask.contiguous()
+        g_rgb = None if g_rgb is None else _cl(g_rgb)
+        g_rgba = None if g_rgba is None else _aligned16(_cl(g_rgba))
+        d_rec = _new_cl(n, 4, h, w, rec)
+        _lib.check(L.odvae_rgba_terms_bwd_f32(rec.data_ptr(), rgb.data_ptr(), a.data_ptr(), _lib.ptr(m), ctx.l2, _lib.ptr(g_l1), _lib.ptr(g_mask),
+                                              _lib.ptr(g_rgb), _lib.ptr(g_rgba), d_rec.data_ptr(), n, h * w, _lib.stream_ptr()), "rgba_terms_bwd")
+        return d_rec, None, None, None, None, None, None
+
+
+def rgba_terms(rec, rgb_gt, mask_gt, box=None, l2=False, rec_rgb_m=False, gt_rgb_m=False, rec_rgba_m=False, gt_rgba_m=False, sums=True):
+    """(l1_sums [N], mask_sums [N], rec_rgb_m, gt_rgb_m, rec_rgba_m, gt_rgba_m) of a 4-channel reconstruction: sum |rgb_gt*box - rec[:, :3]*box|
+    and sum of |mask_gt*box - rec[:, 3:]*box| (or its square, l2) per sample, and those of the four box-masked tensors that were asked for
+    (None otherwise): rec[:, :3]*box, rgb_gt*box, rec*box, cat(rgb_gt, mask_gt)*box, all NHWC in memory.  sums=False: the two sums are
+    None and not computed (no reduction, no second launch)."""
+    return _RgbaTerms.apply(rec, rgb_gt, mask_gt, box, l2, (bool(rec_rgb_m), bool(gt_rgb_m), bool(rec_rgba_m), bool(gt_rgba_m)), bool(sums))
+
+
 def nhwc_to_nchw(x):
     """Contiguous NCHW copy of an NHWC-in-memory tensor (hand-off to NCHW consumers)."""
     L = _L()

@@ -35,8 +35,8 @@ def parse(argv):
     ap.add_argument("--height", type=int, default=256, help="synthetic crop size (the yaml's patch_height)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("-l", "--logdir", default=None, help="if given, the yaml's lightning.callbacks run and ImageLogger writes below it")
-    ap.add_argument("--checkpoint", default=None, help="with model.params.ema_decay: write a Lightning-layout checkpoint (weights, model_ema.*, "
-                    "optimizer states) here after the run; default <logdir>/checkpoints/last.ckpt when --logdir is given")
+    ap.add_argument("--checkpoint", default=None, help="with model.params.ema_decay or model.params.image_mask_key: write a Lightning-layout checkpoint "
+                    "(weights, model_ema.* if any, optimizer states) here after the run; default <logdir>/checkpoints/last.ckpt when --logdir is given")
     ap.add_argument("--float32_matmul_precision", default=None, choices=("highest", "high", "medium", "torch"),
                     help="what the reference's launcher sets with torch.set_float32_matmul_precision (train.py:521: medium); default: "
                     "leave ODVAE_FLOAT32_MATMUL_PRECISION (highest) alone")
@@ -90,7 +90,7 @@ def main(argv=None):
     def make(step):
         if hasattr(model, "image_key"):      # AutoencoderKL / Autoencoder: images alone
             return synthetic.make_image_batch(bs, opt.height, seed=opt.seed + step, image_key=model.image_key)
-        return synthetic.make_batch(bs, opt.height, seed=opt.seed + step)
+        return synthetic.make_batch(bs, opt.height, seed=opt.seed + step, mask_key=getattr(model, "image_mask_key", None))
     for step in range(opt.steps):
         batch = make(step)
         losses = trainer.training_batch(batch, step, last_in_epoch=step == opt.steps - 1)   # (closes an accumulation window)
@@ -103,6 +103,12 @@ def main(argv=None):
         ckpt = opt.checkpoint or (os.path.join(opt.logdir, "checkpoints", "last.ckpt") if opt.logdir else None)
         if ckpt:
             print("checkpoint  %s (%d model_ema.* keys)" % (trainer.save_checkpoint(ckpt), len(model.model_ema.state_dict())), flush=True)
+    elif getattr(model, "image_mask_key", None) is not None:     # model.params.image_mask_key: one validation batch with the alpha mask
+        metrics = trainer.validate([make(opt.steps)])
+        print("validation  val/rec_loss %.4f  val/mask_loss %.4f" % (metrics["val/rec_loss"].item(), metrics["val/mask_loss"].item()), flush=True)
+        ckpt = opt.checkpoint or (os.path.join(opt.logdir, "checkpoints", "last.ckpt") if opt.logdir else None)
+        if ckpt:
+            print("checkpoint  %s" % trainer.save_checkpoint(ckpt), flush=True)
     return model
 
 

@@ -16,11 +16,18 @@ def dataset_stats_standin():
     return {lab: {k: torch.tensor([0.0, 0.0]) for k in ("t3", "l", "h", "w")} for lab in LABELS}
 
 
-def make_batch(batch_size, height, width=None, seed=23, class_id=0):
-    """The batch dict PoseAutoencoder.training_step reads; `patch` ~ U[0,1) NCHW like ToTensor output."""
+def make_batch(batch_size, height, width=None, seed=23, class_id=0, mask_key=None):
+    """The batch dict PoseAutoencoder.training_step reads; `patch` ~ U[0,1) NCHW like ToTensor output.
+    mask_key (the model's image_mask_key): a seeded {0,1} alpha mask [B,1,H,W] under that key, drawn from a generator of its own so that
+    the other entries are the ones a batch without it holds."""
     width = width or height
     g = torch.Generator().manual_seed(seed)
+    extra = {}
+    if mask_key is not None:
+        gm = torch.Generator().manual_seed(seed + 104729)
+        extra[mask_key] = (torch.rand(batch_size, 1, height, width, generator=gm) < 0.5).float()
     return {
+        **extra,
         "patch": torch.rand(batch_size, 3, height, width, generator=g),
         "pose_6d": torch.randn(batch_size, 4, generator=g),
         "yaw": (torch.rand(batch_size, generator=g) * 2 - 1) * math.pi,

@@ -345,6 +345,21 @@ int odvae_l1_masked_sum_f32(const float* x, const float* xr, const float* mask, 
                             void* workspace, size_t workspace_bytes, void* stream);
 int odvae_l1_masked_bwd_f32(const float* x, const float* xr, const float* mask, const float* g, float* dxr,
                             int N, int HW, int C, void* stream);
+/* image_mask_key: PoseLoss's terms on a 4-channel reconstruction (contperceptual.py:230-257,166-174) in one pass.  rec [N][HW][4] (16-byte
+ * aligned: one load per pixel), rgb_gt [N][HW][3], mask_gt [N][HW], box [N][HW] or NULL (= 1): any 4-byte aligned base.
+ * l1_sum[n] = sum over pixels and RGB of |rgb_gt*box - rec*box| (the term of odvae_l1_masked_sum_f32); mask_sum[n] = sum over pixels of
+ * |mask_gt*box - rec_3*box| (l2 = 0) or its square (l2 = 1); every product, difference and addition separately rounded.  Each of
+ * rec_rgb_m / gt_rgb_m [N][HW][3] and rec_rgba_m / gt_rgba_m [N][HW][4] (16-byte aligned; gt_rgba_m = cat(rgb_gt, mask_gt) * box) is
+ * written unless NULL.  The sums go through the workspace (odvae_rgba_terms_workspace_bytes(N) bytes) in a fixed order, no atomics;
+ * l1_sum and mask_sum both NULL: the copies alone, no sums, no workspace (the discriminator phase).  N <= 65535.
+ * odvae_rgba_terms_bwd_f32: d_rec [N][HW][4] (overwritten) from g_l1[N], g_mask[N], g_rec_rgb_m [N][HW][3], g_rec_rgba_m [N][HW][4], each
+ * NULL = zero; the L1 term's sign rule is odvae_l1_masked_bwd_f32's (0 at a tie). */
+size_t odvae_rgba_terms_workspace_bytes(int N);
+int odvae_rgba_terms_f32(const float* rec, const float* rgb_gt, const float* mask_gt, const float* box, int l2, float* l1_sum, float* mask_sum,
+                         float* rec_rgb_m, float* gt_rgb_m, float* rec_rgba_m, float* gt_rgba_m, int N, int HW,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int odvae_rgba_terms_bwd_f32(const float* rec, const float* rgb_gt, const float* mask_gt, const float* box, int l2, const float* g_l1,
+                             const float* g_mask, const float* g_rec_rgb_m, const float* g_rec_rgba_m, float* d_rec, int N, int HW, void* stream);
 /* bias gradient of a 1x1 convolution: out[c] = sum_rows x[row][c] */
 size_t odvae_colsum_workspace_bytes(int64_t rows, int C);
 int odvae_colsum_f32(const float* x, int64_t rows, int C, float* out, void* workspace, size_t workspace_bytes, void* stream);
