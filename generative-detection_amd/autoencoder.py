@@ -39,12 +39,16 @@ class AutoencoderKL(LightningModule):
     """[UPSTREAM] ldm.models.autoencoder.AutoencoderKL (the plain KL autoencoder BASELINE.json names)."""
 
     def __init__(self, ddconfig, lossconfig, embed_dim, ckpt_path=None, ignore_keys=[], image_key="image",
-                 colorize_nlabels=None, monitor=None, ema_decay=None, learn_logvar=False, device_noise=None):
-        """device_noise: an extension (neither upstream nor the reference has it).  None = the noise is drawn with the host RNG and
+                 colorize_nlabels=None, monitor=None, ema_decay=None, learn_logvar=False, device_noise=None, cond_key=None):
+        """cond_key: an extension (upstream's steps never pass the loss's `cond`).  When set, batch[key] (NCHW) goes to the loss as cond=
+        (the conditional discriminator's side channel: lossconfig disc_conditional, disc_in_channels) in the training and validation
+        steps.  (PoseAutoencoder has loss_weights_key beside it: a weight map is PoseLoss's, the plain loss takes none.)
+        device_noise: an extension (neither upstream nor the reference has it).  None = the noise is drawn with the host RNG and
         uploaded, as the reference does; an integer is the seed of the device-side draws (latent_noise.py): no host RNG, no upload."""
         super().__init__()
         self.learn_logvar = learn_logvar
         self.image_key = image_key
+        self.cond_key = cond_key
         self.encoder = Encoder(**ddconfig)
         self.decoder = Decoder(**ddconfig)
         self.loss = instantiate_from_config(lossconfig)
@@ -194,6 +198,16 @@ class AutoencoderKL(LightningModule):
             eps = torch.randn(shape)      # drawn on the host, as DiagonalGaussianDistribution.sample does
         return _lib.upload(eps.float(), self.device)
 
+    def _loss_extras(self, batch):
+        """cond= and weights= of the loss call: batch[cond_key] and (PoseAutoencoder alone has that key) batch[loss_weights_key], both NCHW,
+        where the keys are set, else nothing"""
+        extras = {}
+        if getattr(self, "cond_key", None) is not None:
+            extras["cond"] = batch[self.cond_key]
+        if getattr(self, "loss_weights_key", None) is not None:
+            extras["weights"] = batch[self.loss_weights_key]
+        return extras
+
     def get_input(self, batch, k):
         """[N, H, W, C] (or [N, H, W]) of the batch -> f32 NCHW on the model's device"""
         x = batch[k]
@@ -206,12 +220,12 @@ class AutoencoderKL(LightningModule):
         reconstructions, posterior = self(inputs)
         if optimizer_idx == 0:
             aeloss, log_dict_ae = self.loss(inputs, reconstructions, posterior, optimizer_idx, self.global_step,
-                                            last_layer=self.get_last_layer(), split="train")
+                                            last_layer=self.get_last_layer(), split="train", **self._loss_extras(batch))
             self.log("aeloss", aeloss, prog_bar=True, logger=True, on_step=True, on_epoch=True)
             self.log_dict(log_dict_ae, prog_bar=False, logger=True, on_step=True, on_epoch=False)
             return aeloss
         discloss, log_dict_disc = self.loss(inputs, reconstructions, posterior, optimizer_idx, self.global_step,
-                                            last_layer=self.get_last_layer(), split="train")
+                                            last_layer=self.get_last_layer(), split="train", **self._loss_extras(batch))
         self.log("discloss", discloss, prog_bar=True, logger=True, on_step=True, on_epoch=True)
         self.log_dict(log_dict_disc, prog_bar=False, logger=True, on_step=True, on_epoch=False)
         return discloss
@@ -227,9 +241,9 @@ class AutoencoderKL(LightningModule):
         inputs = self.get_input(batch, self.image_key)
         reconstructions, posterior = self(inputs)
         _, log_dict_ae = self.loss(inputs, reconstructions, posterior, 0, self.global_step,
-                                   last_layer=self.get_last_layer(), split="val" + postfix)
+                                   last_layer=self.get_last_layer(), split="val" + postfix, **self._loss_extras(batch))
         _, log_dict_disc = self.loss(inputs, reconstructions, posterior, 1, self.global_step,
-                                     last_layer=self.get_last_layer(), split="val" + postfix)
+                                     last_layer=self.get_last_layer(), split="val" + postfix, **self._loss_extras(batch))
         self.log(f"val{postfix}/rec_loss", log_dict_ae[f"val{postfix}/rec_loss"])
         self.log_dict(log_dict_ae)
         self.log_dict(log_dict_disc)
@@ -292,8 +306,11 @@ class PoseAutoencoder(AutoencoderKL):
                  colorize_nlabels=None, monitor=None, activation="relu", feat_dims=[16, 16, 16],
                  pose_decoder_config=None, pose_encoder_config=None, dropout_prob_init=1.0, dropout_prob_final=0.7,
                  dropout_warmup_steps=5000, pose_conditioned_generation_steps=10000, add_noise_to_z_obj=True,
-                 train_on_yaw=True, ema_decay=None, learn_logvar=False, device_noise=None):
-        """ema_decay, learn_logvar: an extension (the reference's PoseAutoencoder has neither): the two keys of the stable-diffusion
+                 train_on_yaw=True, ema_decay=None, learn_logvar=False, device_noise=None, cond_key=None, loss_weights_key=None):
+        """cond_key, loss_weights_key: extensions (the reference's steps never pass the loss's `cond` / `weights`).  When set, batch[key]
+        (NCHW) goes to PoseLoss as cond= (the conditional discriminator's side channel: lossconfig disc_conditional, disc_in_channels) or
+        weights= (a weight on the NLL: scalar, per sample, per pixel or per element) in the training and validation steps.
+        ema_decay, learn_logvar: an extension (the reference's PoseAutoencoder has neither): the two keys of the stable-diffusion
         revision of AutoencoderKL, off by default -- None / False reproduce the reference.
         device_noise: an extension too.  None = posterior_eps, the dropout mask, z_noise and bbox_eps come from the host RNG, as in the
         reference; an integer seeds the device-side draws and the latent stage runs as one launch each way (_forward_device_noise)."""
@@ -308,6 +325,7 @@ class PoseAutoencoder(AutoencoderKL):
         self.add_noise_to_z_obj = add_noise_to_z_obj
         self.feature_dims = feat_dims
         self.image_rgb_key, self.image_mask_key = image_rgb_key, image_mask_key
+        self.cond_key, self.loss_weights_key = cond_key, loss_weights_key
         self.pose_key, self.pose_perturbed_key = pose_key, pose_perturbed_key
         self.class_key, self.bbox_key, self.fill_factor_key = class_key, bbox_key, fill_factor_key
         self.encoder = FeatEncoder(**ddconfig)
@@ -501,7 +519,7 @@ class PoseAutoencoder(AutoencoderKL):
         self.log("dropout_prob", self.dropout_prob, prog_bar=True, logger=True, on_step=True, on_epoch=True)
         loss, log_dict = self.loss(rgb_gt, mask_gt, pose_gt, dec_obj, dec_pose, class_gt, class_gt_label, bbox_gt,
                                    fill_factor_gt, posterior_obj, bbox_posterior, optimizer_idx, self.global_step,
-                                   mask_2d_bbox, last_layer=self.get_last_layer(), split="train")
+                                   mask_2d_bbox, last_layer=self.get_last_layer(), split="train", **self._loss_extras(batch))
         name = "aeloss" if optimizer_idx == 0 else "discloss"
         self.log(name, loss, prog_bar=True, logger=True, on_step=True, on_epoch=True)
         self.log_dict(log_dict, prog_bar=False, logger=True, on_step=True, on_epoch=False)
@@ -514,7 +532,7 @@ class PoseAutoencoder(AutoencoderKL):
         for optimizer_idx in (0, 1):
             _, log = self.loss(rgb_gt, mask_gt, pose_gt, dec_obj, dec_pose, class_gt, class_gt_label, bbox_gt,
                                fill_factor_gt, posterior_obj, bbox_posterior, optimizer_idx, self.global_step,
-                               mask_2d_bbox, last_layer=self.get_last_layer(), split="val" + postfix)
+                               mask_2d_bbox, last_layer=self.get_last_layer(), split="val" + postfix, **self._loss_extras(batch))
             logs.append(log)
         log_dict_ae, log_dict_disc = logs
         self.log(f"val{postfix}/rec_loss", log_dict_ae[f"val{postfix}/rec_loss"], sync_dist=True)

@@ -461,6 +461,169 @@ __global__ __launch_bounds__(256) void rgba_terms_bwd_kernel(const float4* __res
   }
 }
 
+// ---- weighted L1 sums (the `weights` argument of the losses: contperceptual.py:147-158 with a weight map) ------------------------------
+// One pass over x [N][HW][C], the first C channels of xr [N][HW][Cr], box [N][HW] (nullable = 1) and wgt ([N][HW], or [N][HW][C] when
+// per_channel).  Per element, every operation separately rounded, as in rgba_terms_kernel:
+//   xm = x * b, rm = xr * b, t = |xm - rm|,  l1 += t,  wl1 += wgt * t,  w += wgt   (a per-pixel weight is added once per channel)
+// x == null (then xr is not read either): the weight sums alone.  Stage 1 leaves part[k][n][blk], k = 0 (l1), 1 (wl1), 2 (w); sums3_final_kernel
+// adds a sample's partials in f64 in a fixed order: no atomics.  CC: the channel count when it is known at compile time (0 = C_rt);
+// V4 (CC > 0, Cr == 4, xr 16-byte aligned): the reconstruction's pixel is one 16-byte load.
+template <int CC, bool V4>
+__global__ __launch_bounds__(256) void l1_weighted_kernel(const float* __restrict__ x, const float* __restrict__ xr, const float* __restrict__ box,
+                                                          const float* __restrict__ wgt, float* __restrict__ part, int HW, int C_rt, int Cr,
+                                                          int per_channel) {
+#pragma clang fp contract(off)
+  __shared__ float sh[4];
+  const int C = CC ? CC : C_rt;
+  const int n = blockIdx.y, N = gridDim.y;
+  const int64_t base = (int64_t)n * HW;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < HW; p += (int64_t)gridDim.x * 256) {
+    const int64_t px = base + p;
+    const float wp = per_channel ? 0.f : wgt[px];
+    if (!x) {      // (block-uniform) the pixel term is off: W[n] alone
+      for (int c = 0; c < C; ++c) s2 = s2 + (per_channel ? wgt[px * C + c] : wp);
+      continue;
+    }
+    const float b = box ? box[px] : 1.f;
+    if constexpr (V4) {
+      const float4 r = reinterpret_cast<const float4*>(xr)[px];
+      const float rv[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+      for (int c = 0; c < CC; ++c) {
+        const float w = per_channel ? wgt[px * CC + c] : wp;
+        const float xm = x[px * CC + c] * b, rm = rv[c] * b;
+        const float t = fabsf(xm - rm);
+        const float wt = w * t;
+        s0 = s0 + t; s1 = s1 + wt; s2 = s2 + w;
+      }
+    } else {
+      for (int c = 0; c < C; ++c) {
+        const float w = per_channel ? wgt[px * C + c] : wp;
+        const float xm = x[px * C + c] * b, rm = xr[px * Cr + c] * b;
+        const float t = fabsf(xm - rm);
+        const float wt = w * t;
+        s0 = s0 + t; s1 = s1 + wt; s2 = s2 + w;
+      }
+    }
+  }
+  s0 = block_sum(s0, sh);
+  s1 = block_sum(s1, sh);
+  s2 = block_sum(s2, sh);
+  if (threadIdx.x == 0) {
+    part[(int64_t)n * gridDim.x + blockIdx.x] = s0;
+    part[((int64_t)N + n) * gridDim.x + blockIdx.x] = s1;
+    part[((int64_t)2 * N + n) * gridDim.x + blockIdx.x] = s2;
+  }
+}
+// grid (N, 3): out_k[n] = the sum of the sample's nblk partials of term k; a null out_k is skipped
+__global__ void sums3_final_kernel(const float* __restrict__ part, int nblk, float* __restrict__ out0, float* __restrict__ out1,
+                                   float* __restrict__ out2) {
+  const int n = blockIdx.x, which = blockIdx.y, N = gridDim.x;
+  float* out = which == 0 ? out0 : (which == 1 ? out1 : out2);
+  if (!out) return;
+  const float* p = part + ((int64_t)which * N + n) * nblk;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 64) s += (double)p[i];
+  s = wave_sum_f64(s);
+  if (threadIdx.x == 0) out[n] = (float)s;
+}
+// dxr [N][HW][Cr], overwritten.  c < C: ((g_l1[n] + g_wl1[n] * wgt) * sign(rm - xm)) * b (l1_bwd_kernel's sign rule: 0 at a tie), a null
+// gradient a zero; c >= C: 0.  V4: dxr and xr are 16-byte aligned and Cr == 4.
+template <int CC, bool V4>
+__global__ __launch_bounds__(256) void l1_weighted_bwd_kernel(const float* __restrict__ x, const float* __restrict__ xr, const float* __restrict__ box,
+                                                              const float* __restrict__ wgt, const float* __restrict__ g_l1,
+                                                              const float* __restrict__ g_wl1, float* __restrict__ dxr, int HW, int C_rt, int Cr,
+                                                              int per_channel) {
+#pragma clang fp contract(off)
+  const int C = CC ? CC : C_rt;
+  const int n = blockIdx.y;
+  const float gl = g_l1 ? g_l1[n] : 0.f, gw = g_wl1 ? g_wl1[n] : 0.f;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < HW; q += (int64_t)gridDim.x * 256) {
+    const int64_t px = (int64_t)n * HW + q;
+    const float b = box ? box[px] : 1.f;
+    const float wp = per_channel ? 0.f : wgt[px];
+    if constexpr (V4) {
+      const float4 r = reinterpret_cast<const float4*>(xr)[px];
+      const float rv[4] = {r.x, r.y, r.z, r.w};
+      float o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < CC; ++c) {
+        const float w = per_channel ? wgt[px * CC + c] : wp;
+        const float d = rv[c] * b - x[px * CC + c] * b;
+        const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+        const float gwt = gw * w;
+        const float g = gl + gwt;
+        o[c] = (g * sg) * b;
+      }
+      reinterpret_cast<float4*>(dxr)[px] = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+      for (int c = 0; c < C; ++c) {
+        const float w = per_channel ? wgt[px * C + c] : wp;
+        const float d = xr[px * Cr + c] * b - x[px * C + c] * b;
+        const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+        const float gwt = gw * w;
+        const float g = gl + gwt;
+        dxr[px * Cr + c] = (g * sg) * b;
+      }
+      for (int c = C; c < Cr; ++c) dxr[px * Cr + c] = 0.f;
+    }
+  }
+}
+
+// ---- discriminator input under disc_conditional: y = cat(x * box, cond) along the channels (contperceptual.py:283-289,354-361) ----------
+// x [N][HW][Cx], box [N][HW] (nullable = 1), cond [N][HW][Cc], y [N][HW][Cy], Cy = Cx + Cc.  One thread per OUTPUT element: consecutive
+// lanes store consecutive floats, and read x / cond nearly so.  grid (blocks, N); a sample's HW * Cy elements are counted in 32 bits (the
+// launcher checks), so the pixel of an element is one 32-bit division -- by a constant where CY names the row width (0 = Cy_rt).
+template <int CY>
+__global__ __launch_bounds__(256) void cat_mask_kernel(const float* __restrict__ x, const float* __restrict__ box, const float* __restrict__ cond,
+                                                       float* __restrict__ y, int HW, int Cx, int Cy_rt) {
+  const uint32_t Cy = CY ? (uint32_t)CY : (uint32_t)Cy_rt, cx = (uint32_t)Cx, cc = Cy - cx;
+  const int n = blockIdx.y;
+  const float* xa = x + (int64_t)n * HW * cx;
+  const float* ca = cond + (int64_t)n * HW * cc;
+  const float* bx = box ? box + (int64_t)n * HW : nullptr;
+  float* ya = y + (int64_t)n * HW * Cy;
+  const uint32_t per = (uint32_t)HW * Cy;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < per; i += gridDim.x * 256u) {
+    const uint32_t p = i / Cy, c = i - p * Cy;
+    float v;
+    if (c < cx) { v = xa[(int64_t)p * cx + c]; if (bx) v = v * bx[p]; }
+    else v = ca[(int64_t)p * cc + (c - cx)];
+    ya[i] = v;
+  }
+}
+// Cy == 4 and y 16-byte aligned: one thread per pixel, one 16-byte store
+__global__ __launch_bounds__(256) void cat_mask_px4_kernel(const float* __restrict__ x, const float* __restrict__ box, const float* __restrict__ cond,
+                                                           float4* __restrict__ y, int HW, int Cx) {
+  const int n = blockIdx.y, Cc = 4 - Cx;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < HW; q += (int64_t)gridDim.x * 256) {
+    const int64_t px = (int64_t)n * HW + q;
+    const float b = box ? box[px] : 1.f;
+    float v[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] = c < Cx ? x[px * Cx + c] * b : cond[px * Cc + (c - Cx)];
+    y[px] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+// dx [N][HW][Cx] = dy[..., :Cx] * box: one thread per element of dx (CX: the row width of dx when known at compile time, 0 = Cx_rt)
+template <int CX>
+__global__ __launch_bounds__(256) void cat_mask_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ box, float* __restrict__ dx,
+                                                           int HW, int Cx_rt, int Cy) {
+  const uint32_t cx = CX ? (uint32_t)CX : (uint32_t)Cx_rt;
+  const int n = blockIdx.y;
+  const float* ga = dy + (int64_t)n * HW * Cy;
+  const float* bx = box ? box + (int64_t)n * HW : nullptr;
+  float* da = dx + (int64_t)n * HW * cx;
+  const uint32_t per = (uint32_t)HW * cx;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < per; i += gridDim.x * 256u) {
+    const uint32_t p = i / cx, c = i - p * cx;
+    float v = ga[(int64_t)p * Cy + c];
+    if (bx) v = v * bx[p];
+    da[i] = v;
+  }
+}
+
 // ---- column sums (bias gradient of the 1x1 convolutions): out[c] = sum_rows x[row][c] ------------------
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ x, int64_t rows, int C,
                                                              int rows_per_block, float* __restrict__ part) {
@@ -1068,6 +1231,104 @@ int odvae_rgba_terms_bwd_f32(const float* rec, const float* rgb_gt, const float*
                      reinterpret_cast<const float4*>(rec), rgb_gt, mask_gt, box, g_l1, g_mask, g_rec_rgb_m,
                      reinterpret_cast<const float4*>(g_rec_rgba_m), reinterpret_cast<float4*>(d_rec), HW, l2 ? 1 : 0);
   ODVAE_LAUNCH_CHECK("rgba_terms_bwd");
+  return ODVAE_OK;
+}
+
+// the stage-1 grid cap of the weighted sums; the workspace holds 3 * N * that many floats
+static const int kL1wBlocks = 256;
+
+size_t odvae_l1_weighted_workspace_bytes(int N) { return (size_t)3 * (size_t)std::max(N, 0) * kL1wBlocks * sizeof(float); }
+
+// which instantiation of the weighted-L1 kernels a call takes: the 16-byte forms need Cr == 4 and 16-byte aligned 4-channel arrays
+#define ODVAE_L1W_DISPATCH(KERNEL, v4, ...)                                                                   \
+  do {                                                                                                        \
+    if ((v4) && C == 3) hipLaunchKernelGGL((KERNEL<3, true>), __VA_ARGS__);                                   \
+    else if ((v4) && C == 4) hipLaunchKernelGGL((KERNEL<4, true>), __VA_ARGS__);                              \
+    else if (C == 3) hipLaunchKernelGGL((KERNEL<3, false>), __VA_ARGS__);                                     \
+    else hipLaunchKernelGGL((KERNEL<0, false>), __VA_ARGS__);                                                 \
+  } while (0)
+
+int odvae_l1_weighted_sums_f32(const float* x, const float* xr, const float* box, const float* wgt, int wgt_per_channel, float* l1_sum,
+                               float* wl1_sum, float* w_sum, int N, int HW, int C, int Cr, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  ODVAE_CHECK_ARG(N > 0 && HW > 0 && C > 0 && Cr >= C, "l1_weighted_sums: needs N > 0, HW > 0, 0 < C <= Cr (got N %d, HW %d, C %d, Cr %d)", N, HW, C, Cr);
+  ODVAE_CHECK_ARG(N <= 65535, "l1_weighted_sums: N %d is beyond the grid's 65535 samples", N);
+  ODVAE_CHECK_ARG(wgt != nullptr, "l1_weighted_sums: wgt is null");
+  ODVAE_CHECK_ARG(l1_sum || wl1_sum || w_sum, "l1_weighted_sums: nothing to compute (every output is null)");
+  ODVAE_CHECK_ARG((x == nullptr) == (xr == nullptr), "l1_weighted_sums: x and xr must both be set or both null");
+  ODVAE_CHECK_ARG(x || (!l1_sum && !wl1_sum), "l1_weighted_sums: without x and xr only w_sum can be asked for");
+  ODVAE_CHECK_ARG((((uintptr_t)x | (uintptr_t)xr | (uintptr_t)box | (uintptr_t)wgt) & 3) == 0, "l1_weighted_sums: a float array is not 4-byte aligned");
+  if (!workspace || workspace_bytes < odvae_l1_weighted_workspace_bytes(N)) {
+    odvae_set_error("l1_weighted_sums: needs %zu workspace bytes", odvae_l1_weighted_workspace_bytes(N));
+    return ODVAE_ERR_WORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  const int nblk = (int)std::min<int64_t>(ceil_div64(HW, 256), kL1wBlocks);
+  const bool v4 = x && Cr == 4 && ((uintptr_t)xr & 15) == 0;
+  ODVAE_L1W_DISPATCH(l1_weighted_kernel, v4, dim3(nblk, N), dim3(256), 0, st, x, xr, box, wgt, part, HW, C, Cr, wgt_per_channel ? 1 : 0);
+  ODVAE_LAUNCH_CHECK("l1_weighted_sums");
+  hipLaunchKernelGGL(sums3_final_kernel, dim3(N, 3), dim3(64), 0, st, part, nblk, l1_sum, wl1_sum, w_sum);
+  ODVAE_LAUNCH_CHECK("l1_weighted_sums(final)");
+  return ODVAE_OK;
+}
+
+int odvae_l1_weighted_bwd_f32(const float* x, const float* xr, const float* box, const float* wgt, int wgt_per_channel, const float* g_l1,
+                              const float* g_wl1, float* dxr, int N, int HW, int C, int Cr, void* stream) {
+  ODVAE_CHECK_ARG(N > 0 && HW > 0 && C > 0 && Cr >= C, "l1_weighted_bwd: needs N > 0, HW > 0, 0 < C <= Cr (got N %d, HW %d, C %d, Cr %d)", N, HW, C, Cr);
+  ODVAE_CHECK_ARG(N <= 65535, "l1_weighted_bwd: N %d is beyond the grid's 65535 samples", N);
+  ODVAE_CHECK_ARG(x && xr && wgt && dxr, "l1_weighted_bwd: x, xr, wgt and dxr are required");
+  ODVAE_CHECK_ARG((((uintptr_t)x | (uintptr_t)xr | (uintptr_t)box | (uintptr_t)wgt | (uintptr_t)g_l1 | (uintptr_t)g_wl1 | (uintptr_t)dxr) & 3) == 0,
+                  "l1_weighted_bwd: a float array is not 4-byte aligned");
+  const bool v4 = Cr == 4 && (((uintptr_t)xr | (uintptr_t)dxr) & 15) == 0;
+  ODVAE_L1W_DISPATCH(l1_weighted_bwd_kernel, v4, dim3(grid_1d(HW, std::max(1, 8192 / N)), N), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     x, xr, box, wgt, g_l1, g_wl1, dxr, HW, C, Cr, wgt_per_channel ? 1 : 0);
+  ODVAE_LAUNCH_CHECK("l1_weighted_bwd");
+  return ODVAE_OK;
+}
+#undef ODVAE_L1W_DISPATCH
+
+static int cat_mask_check(const char* what, int N, int HW, int Cx, int Cc) {
+  ODVAE_CHECK_ARG(N > 0 && HW > 0 && Cx > 0 && Cc > 0, "%s: needs N, HW, Cx, Cc > 0 (got %d, %d, %d, %d)", what, N, HW, Cx, Cc);
+  ODVAE_CHECK_ARG(N <= 65535, "%s: N %d is beyond the grid's 65535 samples", what, N);
+  ODVAE_CHECK_ARG((int64_t)HW * ((int64_t)Cx + Cc) < ((int64_t)1 << 31), "%s: a sample of %d x %lld floats is beyond the 32-bit element index",
+                  what, HW, (long long)Cx + Cc);
+  return ODVAE_OK;
+}
+
+int odvae_cat_mask_f32(const float* x, const float* box, const float* cond, float* y, int N, int HW, int Cx, int Cc, void* stream) {
+  if (int rc = cat_mask_check("cat_mask", N, HW, Cx, Cc)) return rc;
+  ODVAE_CHECK_ARG(x && cond && y, "cat_mask: x, cond and y are required");
+  ODVAE_CHECK_ARG((((uintptr_t)x | (uintptr_t)box | (uintptr_t)cond | (uintptr_t)y) & 3) == 0, "cat_mask: a float array is not 4-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int Cy = Cx + Cc, cap = std::max(1, 8192 / N);
+  if (Cy == 4 && ((uintptr_t)y & 15) == 0) {
+    hipLaunchKernelGGL(cat_mask_px4_kernel, dim3(grid_1d(HW, cap), N), dim3(256), 0, st, x, box, cond, reinterpret_cast<float4*>(y), HW, Cx);
+  } else {
+    const dim3 grid(grid_1d((int64_t)HW * Cy, cap), N);
+    switch (Cy) {
+      case 4: hipLaunchKernelGGL(cat_mask_kernel<4>, grid, dim3(256), 0, st, x, box, cond, y, HW, Cx, Cy); break;
+      case 5: hipLaunchKernelGGL(cat_mask_kernel<5>, grid, dim3(256), 0, st, x, box, cond, y, HW, Cx, Cy); break;
+      case 6: hipLaunchKernelGGL(cat_mask_kernel<6>, grid, dim3(256), 0, st, x, box, cond, y, HW, Cx, Cy); break;
+      default: hipLaunchKernelGGL(cat_mask_kernel<0>, grid, dim3(256), 0, st, x, box, cond, y, HW, Cx, Cy);
+    }
+  }
+  ODVAE_LAUNCH_CHECK("cat_mask");
+  return ODVAE_OK;
+}
+
+int odvae_cat_mask_bwd_f32(const float* dy, const float* box, float* dx, int N, int HW, int Cx, int Cc, void* stream) {
+  if (int rc = cat_mask_check("cat_mask_bwd", N, HW, Cx, Cc)) return rc;
+  ODVAE_CHECK_ARG(dy && dx, "cat_mask_bwd: dy and dx are required");
+  ODVAE_CHECK_ARG((((uintptr_t)dy | (uintptr_t)box | (uintptr_t)dx) & 3) == 0, "cat_mask_bwd: a float array is not 4-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(grid_1d((int64_t)HW * Cx, std::max(1, 8192 / N)), N);
+  switch (Cx) {
+    case 3: hipLaunchKernelGGL(cat_mask_bwd_kernel<3>, grid, dim3(256), 0, st, dy, box, dx, HW, Cx, Cx + Cc); break;
+    case 4: hipLaunchKernelGGL(cat_mask_bwd_kernel<4>, grid, dim3(256), 0, st, dy, box, dx, HW, Cx, Cx + Cc); break;
+    default: hipLaunchKernelGGL(cat_mask_bwd_kernel<0>, grid, dim3(256), 0, st, dy, box, dx, HW, Cx, Cx + Cc);
+  }
+  ODVAE_LAUNCH_CHECK("cat_mask_bwd");
   return ODVAE_OK;
 }
 

@@ -139,6 +139,28 @@ class LPIPSWithDiscriminator(nn.Module):
         return d_weight * self.discriminator_weight
 
     # ---- the plain loss ([UPSTREAM] ldm contperceptual.py LPIPSWithDiscriminator.forward) ---------------------------------------------
+    def _weights_layout(self, weights, shape):
+        """(layout, tensor) of ops.loss_weights_layout, (None, None) without weights; `map` layouts ("pixel", "element") take the weighted
+        sums of ops.l1_weighted_sums, the other two scale the per-sample sums."""
+        if weights is None:
+            return None, None
+        return ops.loss_weights_layout(weights, *shape)
+
+    def _checked_cond(self, cond, d_input):
+        """`cond` of the conditional discriminator as f32 [B,Cc,H,W] on the device of the tensor it is concatenated to (float, bool or
+        uint8 in; values as they are, never box-masked, never differentiated); None stays None."""
+        if cond is None:
+            return None
+        want = (d_input.shape[0], d_input.shape[2], d_input.shape[3])
+        if not torch.is_tensor(cond) or cond.dim() != 4 or (cond.shape[0], cond.shape[2], cond.shape[3]) != want or cond.shape[1] < 1:
+            raise ValueError("cond must be [B,Cc,H,W] = [%d,Cc,%d,%d] for a discriminator input %s, got %s"
+                             % (want + (tuple(d_input.shape), tuple(cond.shape) if torch.is_tensor(cond) else type(cond))))
+        input_nc = self.discriminator.main[0].in_channels
+        if d_input.shape[1] + cond.shape[1] != input_nc:
+            raise ValueError("cond has %d channels and the discriminator input %d, but the discriminator was built with disc_in_channels: %d "
+                             "(set lossconfig.params.disc_in_channels: %d)" % (cond.shape[1], d_input.shape[1], input_nc, d_input.shape[1] + cond.shape[1]))
+        return cond.detach().to(d_input.device).float()
+
     def _plain_nll(self, rec_sums, chw, weights=None):
         """(nll_loss, weighted_nll_loss) = sum over everything / N of rec_loss / exp(logvar) + logvar, from the per-sample sums of rec_loss.
         No +1e-8 beside exp(logvar) here (PoseLoss has one)."""
@@ -161,7 +183,11 @@ class LPIPSWithDiscriminator(nn.Module):
             return self._plain_discriminator_phase(inputs, reconstructions, global_step, cond, split)
         if optimizer_idx != 0:
             return None      # (upstream falls off the end of forward as well)
-        assert cond is None and not self.disc_conditional
+        if cond is None:
+            assert not self.disc_conditional
+        else:
+            assert self.disc_conditional
+        cond = self._checked_cond(cond, reconstructions)
         dev = inputs.device
         n, c, h, w = inputs.shape
         chw = float(c * h * w)
@@ -175,12 +201,12 @@ class LPIPSWithDiscriminator(nn.Module):
         kl_loss = torch.sum(posteriors.kl()) / n
 
         if self.disc_factor > 0.0:
-            g_loss = -ops.gan_logit_terms(None, self.discriminator(reconstructions))[1]
+            g_loss = -ops.gan_logit_terms(None, self.discriminator(ops.cat_mask(reconstructions, None, cond)))[1]
         elif self.log_exact_g_loss or (self.discriminator.training and self.discriminator.actnorm_uninitialized()):
             # discriminator off: upstream still evaluates D(x_rec) (BatchNorm running statistics move, ActNorm layers initialise from this
             # tensor on the first training batch) and multiplies the term by an exact 0; the forward runs here without a graph
             with torch.no_grad():
-                g_loss = -ops.gan_logit_terms(None, self.discriminator(reconstructions.detach()))[1]
+                g_loss = -ops.gan_logit_terms(None, self.discriminator(ops.cat_mask(reconstructions.detach(), None, cond)))[1]
             if not self.log_exact_g_loss:     # the forward ran for the initialisation alone: the logged value stays the shortcut's 0
                 g_loss = torch.zeros((), device=dev)
         else:
@@ -231,9 +257,12 @@ class LPIPSWithDiscriminator(nn.Module):
     def _plain_discriminator_phase(self, inputs, reconstructions, global_step, cond, split):
         """optimizer_idx == 1: hinge / vanilla loss of the discriminator on the target and the detached reconstruction; the two loss terms
         and the two logged logit means come from one kernel (ops.gan_logit_terms)."""
-        assert cond is None and not self.disc_conditional
-        logits_real = self.discriminator(inputs.detach())
-        logits_fake = self.discriminator(reconstructions.detach())
+        # A None cond means no concatenation, as upstream.  DEVIATION: upstream has no assert in this phase; here a cond without
+        # disc_conditional is refused as in the generator phase (which every training step passes first, and where upstream asserts it).
+        assert cond is None or self.disc_conditional
+        cond = self._checked_cond(cond, inputs)
+        logits_real = self.discriminator(ops.cat_mask(inputs.detach(), None, cond))
+        logits_fake = self.discriminator(ops.cat_mask(reconstructions.detach(), None, cond))
         disc_factor = adopt_weight(self.disc_factor, global_step, threshold=self.discriminator_iter_start)
         terms = ops.gan_logit_terms(logits_real, logits_fake)
         pair = (terms[2], terms[3]) if self.disc_loss is hinge_d_loss else (terms[4], terms[5])
@@ -381,20 +410,37 @@ class PoseLoss(LPIPSWithDiscriminator):
         return self._masked_mean(kl * keep.unsqueeze(1), mask_bg)
 
     # ---- reconstruction / KL terms on the image (contperceptual.py:134-164) ----------------------------------
-    def _rec_sums(self, inputs_rgb, recon_rgb, mask_2d_bbox, use_pixel_loss):
-        """Per-sample sum over (c,h,w) of rec_loss = |x*m - xr*m| (+ perceptual_weight * p_loss), and p_loss."""
+    def _weighted_l1(self, inputs_rgb, reconstructions, mask_2d_bbox, use_pixel_loss, wmap, want_l1):
+        """(l1_sums | None, wl1_sums, w_sums) of a weight map per sample; reconstructions may carry more channels than inputs_rgb (read in
+        place).  With the pixel term off only w_sums comes from the kernel: it still multiplies the perceptual and the logvar term."""
+        if use_pixel_loss:
+            return ops.l1_weighted_sums(inputs_rgb, reconstructions, mask_2d_bbox, wmap, want_l1=want_l1)
+        w_sums = ops.l1_weighted_sums(None, None, None, wmap, shape=tuple(inputs_rgb.shape), device=inputs_rgb.device)[2]
+        zeros = torch.zeros(inputs_rgb.shape[0], device=inputs_rgb.device)
+        return (zeros if want_l1 else None), zeros, w_sums
+
+    def _rec_sums(self, inputs_rgb, recon_rgb, mask_2d_bbox, use_pixel_loss, wmap=None, reconstructions=None):
+        """(rec_sums, chw, weighted): the per-sample sum over (c,h,w) of rec_loss = |x*m - xr*m| (+ perceptual_weight * p_loss); weighted =
+        None, or under a weight map `wmap` (sum of weights * rec_loss, sum of weights) per sample."""
         n, c, h, w = inputs_rgb.shape
         chw = float(c * h * w)
-        if use_pixel_loss:
+        weighted = None
+        if wmap is not None:
+            s, ws, w_sums = self._weighted_l1(inputs_rgb, recon_rgb if reconstructions is None else reconstructions, mask_2d_bbox,
+                                              use_pixel_loss, wmap, True)
+        elif use_pixel_loss:
             s = ops.l1_masked_sum(inputs_rgb, recon_rgb, mask_2d_bbox)
         else:
             s = torch.zeros(n, device=inputs_rgb.device)
-        p_loss = None
         if self.perceptual_weight > 0:
             self._check_perceptual_weights()
             p_loss = self.perceptual_loss(ops.mul_mask(inputs_rgb, mask_2d_bbox), ops.mul_mask(recon_rgb, mask_2d_bbox))
             s = s + self.perceptual_weight * p_loss.reshape(n) * chw
-        return s, chw
+            if wmap is not None:
+                ws = ws + self.perceptual_weight * p_loss.reshape(n) * w_sums
+        if wmap is not None:
+            weighted = (ws, w_sums)
+        return s, chw, weighted
 
     @staticmethod
     def _checked_mask(mask_gt, rgb_gt, dec_obj):
@@ -408,9 +454,11 @@ class PoseLoss(LPIPSWithDiscriminator):
                              % (tuple(dec_obj.shape),))
         return mask_gt.to(rgb_gt.device).float()
 
-    def _rgba_rec_sums(self, rgb_gt, mask_gt, reconstructions, mask_2d_bbox, use_pixel_loss, need_d_input):
-        """(rec_sums, chw, mask_sums, rec_rgba_m): _rec_sums on the RGB part of a 4-channel reconstruction, the per-sample sums of the
-        element-wise mask loss |mask_gt*m - rec[:, 3:]*m| (or its square) and reconstructions * m for the discriminator (None unless asked)."""
+    def _rgba_rec_sums(self, rgb_gt, mask_gt, reconstructions, mask_2d_bbox, use_pixel_loss, need_d_input, wmap=None):
+        """(rec_sums, chw, mask_sums, rec_rgba_m, weighted): _rec_sums on the RGB part of a 4-channel reconstruction, the per-sample sums of the
+        element-wise mask loss |mask_gt*m - rec[:, 3:]*m| (or its square) and reconstructions * m for the discriminator (None unless asked).
+        Under a weight map the unweighted sums and the masked copies still come from ops.rgba_terms; the weighted sums from
+        ops.l1_weighted_sums on the 4-channel reconstruction in place."""
         n, _, h, w = rgb_gt.shape
         chw = float(3 * h * w)
         perceptual = self.perceptual_weight > 0
@@ -418,11 +466,18 @@ class PoseLoss(LPIPSWithDiscriminator):
             reconstructions, rgb_gt, mask_gt, mask_2d_bbox, l2=not isinstance(self.mask_loss, nn.L1Loss), rec_rgb_m=perceptual,
             gt_rgb_m=perceptual, rec_rgba_m=need_d_input)
         s = l1_sums if use_pixel_loss else torch.zeros(n, device=rgb_gt.device)
+        weighted = None
+        if wmap is not None:
+            _, ws, w_sums = self._weighted_l1(rgb_gt, reconstructions, mask_2d_bbox, use_pixel_loss, wmap, False)
         if perceptual:
             self._check_perceptual_weights()
             p_loss = self.perceptual_loss(gt_rgb_m, rec_rgb_m)
             s = s + self.perceptual_weight * p_loss.reshape(n) * chw
-        return s, chw, mask_sums, rec_rgba_m
+            if wmap is not None:
+                ws = ws + self.perceptual_weight * p_loss.reshape(n) * w_sums
+        if wmap is not None:
+            weighted = (ws, w_sums)
+        return s, chw, mask_sums, rec_rgba_m, weighted
 
     def _mask_loss_mean(self, mask_sums, count):
         """(mask_loss, weighted_mask_loss) of get_mask_loss as scalars: the mean over B*H*W of the element-wise mask loss -- what the
@@ -433,10 +488,17 @@ class PoseLoss(LPIPSWithDiscriminator):
         zero = torch.zeros((), device=mask_sums.device)
         return zero, zero
 
-    def _get_nll_loss(self, rec_sums, chw, mask_bg, weights=None):
+    def _get_nll_loss(self, rec_sums, chw, mask_bg, weights=None, weighted=None):
+        """weights: a scalar or a [B] tensor (they scale the per-sample sums; a [B,1,1,1] weight arrives here as [B]: multiplied as it
+        came it would broadcast against the [B] sums to [B,1,1,B]).  weighted = (sum of weights * rec_loss, sum of weights) per sample for a
+        weight map: per sample sum w * nll = wrec / (exp(logvar) + eps) + logvar * wsum (contperceptual.py:147-158)."""
         eps = 1e-8
         nll_sums = rec_sums / (torch.exp(self.logvar) + eps) + self.logvar * chw
         nll_loss = self._masked_mean(nll_sums * mask_bg, mask_bg)
+        if weighted is not None:
+            wrec_sums, w_sums = weighted
+            wnll_sums = wrec_sums / (torch.exp(self.logvar) + eps) + self.logvar * w_sums
+            return nll_loss, self._masked_mean(wnll_sums * mask_bg, mask_bg)
         weighted = nll_loss if weights is None else self._masked_mean(weights * nll_sums * mask_bg, mask_bg)
         return nll_loss, weighted
 
@@ -460,6 +522,7 @@ class PoseLoss(LPIPSWithDiscriminator):
         rgba = mask_gt is not None
         reconstructions = dec_obj
         recon_rgb = reconstructions[:, :3, :, :] if reconstructions.shape[1] != 3 else reconstructions
+        cond = self._checked_cond(cond, reconstructions)
         if optimizer_idx == 1:
             # The discriminator phase returns d_loss and three logit statistics only (contperceptual.py:352-375).  The reference
             # evaluates the pose, reconstruction (incl. LPIPS: 16 VGG convs on two image sets) and KL terms first and then does not use
@@ -484,17 +547,22 @@ class PoseLoss(LPIPSWithDiscriminator):
             # QUIRK (:269): (gt, pred) are passed into the (pred, gt) slots; symmetric for l1/l2
             pose_loss, weighted_pose_loss, t1_loss, t2_loss, t3_loss, v3_loss = self.compute_pose_loss(pose_gt, pose_rec, mask_bg)
             fill_factor_loss, weighted_fill_factor_loss = self.compute_fill_factor_loss(fill_factor_gt, fill_factor_rec.squeeze(), mask_bg)
+        layout, wt = self._weights_layout(weights, tuple(rgb_gt.shape))
+        wmap = wt if layout in ("pixel", "element") else None
+        if layout == "sample":
+            weights = wt.to(rgb_gt.device)      # [B], however it was shaped
         if rgba:
             # one pass over the 4-channel reconstruction: the L1 sums over RGB, the mask-loss sums over alpha, the masked RGB pair of the
             # LPIPS-style net and D's masked RGBA input (ops.rgba_terms) in place of l1_masked_sum + three mul_mask + the channel slice
             need_d_input = optimizer_idx == 0 and (self.disc_factor > 0.0 or self.log_exact_g_loss
                                                    or (self.discriminator.training and self.discriminator.actnorm_uninitialized()))
-            rec_sums, chw, mask_sums, rec_rgba_m = self._rgba_rec_sums(rgb_gt, mask_gt, reconstructions, mask_2d_bbox, use_pixel_loss, need_d_input)
+            rec_sums, chw, mask_sums, rec_rgba_m, weighted = self._rgba_rec_sums(rgb_gt, mask_gt, reconstructions, mask_2d_bbox, use_pixel_loss,
+                                                                                 need_d_input, wmap)
             mask_loss, weighted_mask_loss = self._mask_loss_mean(mask_sums, mask_gt.numel())
         else:
             mask_loss, weighted_mask_loss = self.get_mask_loss(None, None, mask_bg)
-            rec_sums, chw = self._rec_sums(rgb_gt, recon_rgb, mask_2d_bbox, use_pixel_loss)
-        nll_loss, weighted_nll_loss = self._get_nll_loss(rec_sums, chw, mask_bg, weights)
+            rec_sums, chw, weighted = self._rec_sums(rgb_gt, recon_rgb, mask_2d_bbox, use_pixel_loss, wmap, reconstructions)
+        nll_loss, weighted_nll_loss = self._get_nll_loss(rec_sums, chw, mask_bg, weights, weighted)
         rec_mean = rec_sums.detach().sum() / (rec_sums.numel() * chw)
         kl_loss_obj = self._get_kl_loss(posterior_obj, mask_bg)
         if not fused:
@@ -502,9 +570,12 @@ class PoseLoss(LPIPSWithDiscriminator):
         bg4 = mask_bg.reshape(-1, 1, 1, 1)
 
         if optimizer_idx == 0:
-            assert cond is None and not self.disc_conditional
+            if cond is None:
+                assert not self.disc_conditional
+            else:
+                assert self.disc_conditional
             if self.disc_factor > 0.0:
-                logits_fake = self.discriminator(rec_rgba_m if rgba else ops.mul_mask(reconstructions, mask_2d_bbox))
+                logits_fake = self.discriminator(ops.cat_mask(rec_rgba_m, None, cond) if rgba else ops.cat_mask(reconstructions, mask_2d_bbox, cond))
                 g_loss = -torch.mean(logits_fake * bg4)
             elif self.log_exact_g_loss or (self.discriminator.training and self.discriminator.actnorm_uninitialized()):
                 # discriminator off: the reference still evaluates D(x_rec) (its BatchNorm running statistics move too) and
@@ -513,7 +584,7 @@ class PoseLoss(LPIPSWithDiscriminator):
                 # use_actnorm: the reference's ActNorm layers initialise from THIS tensor on the first training batch, so the
                 # forward also runs while any of them is uninitialised; afterwards the shortcut below applies again.
                 with torch.no_grad():
-                    d_in = rec_rgba_m.detach() if rgba else ops.mul_mask(reconstructions.detach(), mask_2d_bbox)
+                    d_in = ops.cat_mask(rec_rgba_m.detach(), None, cond) if rgba else ops.cat_mask(reconstructions.detach(), mask_2d_bbox, cond)
                     g_loss = -torch.mean(self.discriminator(d_in) * bg4)
                 if not self.log_exact_g_loss:     # the forward ran for the initialisation alone: the logged value stays the shortcut's 0
                     g_loss = torch.zeros((), device=rgb_gt.device)
@@ -596,15 +667,14 @@ class PoseLoss(LPIPSWithDiscriminator):
         """optimizer_idx == 1 (contperceptual.py:352-375): hinge / vanilla loss of the discriminator on the masked target and the masked,
         detached reconstruction; background samples (mask_bg == 0) drop out of the logits.  mask_gt (image_mask_key): the target is
         cat(rgb_gt, mask_gt) and both masked 4-channel inputs come from one pass (ops.rgba_terms)."""
-        assert cond is None
-        bg4 = mask_bg.reshape(-1, 1, 1, 1)
+        bg4 = mask_bg.reshape(-1, 1, 1, 1)      # (cond: checked by forward; None means no concatenation, and there is no assert in this phase)
         if mask_gt is not None:
             terms = ops.rgba_terms(reconstructions.detach(), rgb_gt, mask_gt, mask_2d_bbox, rec_rgba_m=True, gt_rgba_m=True, sums=False)
-            logits_real = self.discriminator(terms[5])
-            logits_fake = self.discriminator(terms[4])
+            logits_real = self.discriminator(ops.cat_mask(terms[5], None, cond))
+            logits_fake = self.discriminator(ops.cat_mask(terms[4], None, cond))
         else:
-            logits_real = self.discriminator(ops.mul_mask(rgb_gt, mask_2d_bbox).detach())
-            logits_fake = self.discriminator(ops.mul_mask(reconstructions, mask_2d_bbox).detach())
+            logits_real = self.discriminator(ops.cat_mask(rgb_gt, mask_2d_bbox, cond).detach())
+            logits_fake = self.discriminator(ops.cat_mask(reconstructions, mask_2d_bbox, cond).detach())
         disc_factor = adopt_weight(self.disc_factor, global_step, threshold=self.discriminator_iter_start)
         logits_real = logits_real * bg4
         logits_fake = logits_fake * bg4

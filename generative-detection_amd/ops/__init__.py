@@ -125,7 +125,7 @@ from .resample import (  # noqa: E402
     _RsKind, _RS_F32, _RS_BF16, _rs_in, _rs_forward, _rs_backward, _AvgPool2x2, _AvgPool2x2B, _Upsample2x, _Upsample2xB, avg_pool2x2,
     upsample2x)
 from .elementwise import (  # noqa: E402
-    _Tanh, tanh, rescale_minmax, _GaussianSample, _GaussianKL, gaussian_sample, gaussian_kl, _L1MaskedSum, l1_masked_sum, _aligned16, _RgbaTerms, rgba_terms, nhwc_to_nchw,
+    _Tanh, tanh, rescale_minmax, _GaussianSample, _GaussianKL, gaussian_sample, gaussian_kl, _L1MaskedSum, l1_masked_sum, _aligned16, _RgbaTerms, rgba_terms, WEIGHT_LAYOUTS, loss_weights_layout, _L1WeightedSums, l1_weighted_sums, _CatMask, cat_mask, nhwc_to_nchw,
     _MulMask, mul_mask, _LatentCombine, latent_combine, LATENT_SAMPLE, LATENT_DROPOUT, LATENT_NOISE, noise_fill, _LatentStage, latent_stage, _flat_f32, ema_tick, ema_update, ema_swap, _PoseLosses, pose_losses, LINEAR_ACTS, _LinearAct, linear_act)
 from .patchgan import (  # noqa: E402
     _conv4x4_out, _Conv4x4, _conv4x4_i_raw, _check_pack_current, _Conv4x4I, conv4x4, _BatchNormLReLU, batchnorm_lrelu, _ActNormLReLU, actnorm_init, actnorm_lrelu, _LeakyReLU,

@@ -211,6 +211,150 @@ def rgba_terms(rec, rgb_gt, mask_gt, box=None, l2=False, rec_rgb_m=False, gt_rgb
     return _RgbaTerms.apply(rec, rgb_gt, mask_gt, box, l2, (bool(rec_rgb_m), bool(gt_rgb_m), bool(rec_rgba_m), bool(gt_rgba_m)), bool(sums))
 
 
+WEIGHT_LAYOUTS = ("scalar", "sample", "pixel", "element")
+
+
+def loss_weights_layout(weights, n, c, h, w):
+    """(layout, tensor) of a loss's `weights` argument against rec_loss [n, c, h, w] -- the one place that classifies it.  layout:
+    "scalar" (a number or a one-element tensor; tensor: 0-d), "sample" (a 1-D [n] tensor -- this project's reading of one weight per
+    sample -- or anything that broadcasts as [n,1,1,1]; tensor: [n]), "pixel" ([n or 1, 1, h, w]; tensor: a [n,1,h,w] view) or "element"
+    (anything else that broadcasts to exactly [n,c,h,w]; tensor: a [n,c,h,w] view).  Needs no device.  A shape that does not broadcast to
+    [n,c,h,w], or weights that require grad, raise ValueError."""
+    target = (int(n), int(c), int(h), int(w))
+    t = weights if torch.is_tensor(weights) else torch.as_tensor(weights, dtype=torch.float32)
+    if t.requires_grad:
+        raise ValueError("weights requires grad: the losses treat weights as a constant (detach it, or scale the loss instead)")
+    if t.numel() == 1:
+        return "scalar", t.reshape(())
+    shape = tuple(t.shape)
+    if shape == (target[0],):
+        return "sample", t
+    refuse = ValueError("weights of shape %s do not broadcast to the reconstruction loss's %s" % (shape, target))
+    if len(shape) > 4:
+        raise refuse
+    padded = (1,) * (4 - len(shape)) + shape
+    if any(p not in (1, q) for p, q in zip(padded, target)):
+        raise refuse
+    if padded == (target[0], 1, 1, 1):
+        return "sample", t.reshape(target[0])
+    t4 = t.reshape(padded)
+    if padded[1] == 1 and padded[2:] == target[2:]:
+        return "pixel", t4.expand(target[0], 1, target[2], target[3])
+    return "element", t4.expand(target)
+
+
+class _L1WeightedSums(Function):
+    """Per-sample sums of |x*box - xr*box|, of weights * that and of the weights themselves from one pass (odvae_l1_weighted_sums_f32).
+    wgt arrives flat: [N][HW] or, per_channel, [N][HW][C].  Differentiable w.r.t. xr alone; the backward is one launch."""
+
+    @staticmethod
+    def forward(ctx, x, xr, box, wgt, per_channel, want_l1, shape):
+        L = _L()
+        n, c, h, w = shape
+        _lib.require_device(wgt)
+        dev = wgt.device
+        w_sums = torch.empty(n, dtype=torch.float32, device=dev)
+        wp, wn = _ws(L.odvae_l1_weighted_workspace_bytes(n), wgt)
+        if x is None:      # the pixel term is off: the weight sums alone
+            _lib.check(L.odvae_l1_weighted_sums_f32(None, None, None, wgt.data_ptr(), int(per_channel), None, None, w_sums.data_ptr(),
+                                                    n, h * w, c, c, wp, wn, _lib.stream_ptr()), "l1_weighted_sums")
+            ctx.mark_non_differentiable(w_sums)
+            return None, None, w_sums
+        x = _cl(x.detach())
+        xr = _cl(xr)
+        cr = xr.shape[1]
+        if tuple(x.shape) != (n, c, h, w) or cr < c or (xr.shape[0], xr.shape[2], xr.shape[3]) != (n, h, w) or (box is not None and box.numel() != n * h * w):
+            raise ValueError("l1_weighted_sums: x %s, xr %s, box %s" % (tuple(x.shape), tuple(xr.shape), None if box is None else tuple(box.shape)))
+        m = box.detach().to(dev).float().reshape(n, h * w).contiguous() if box is not None else None
+        _lib.require_device(m)
+        l1_sums = torch.empty(n, dtype=torch.float32, device=dev) if want_l1 else None
+        wl1_sums = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.check(L.odvae_l1_weighted_sums_f32(x.data_ptr(), xr.data_ptr(), _lib.ptr(m), wgt.data_ptr(), int(per_channel), _lib.ptr(l1_sums),
+                                                wl1_sums.data_ptr(), w_sums.data_ptr(), n, h * w, c, cr, wp, wn, _lib.stream_ptr()),
+                   "l1_weighted_sums")
+        ctx.save_for_backward(x, xr, m, wgt)
+        ctx.per_channel = int(per_channel)
+        ctx.set_materialize_grads(False)      # a sum nobody differentiated arrives as None, and its term is skipped
+        ctx.mark_non_differentiable(w_sums)
+        return l1_sums, wl1_sums, w_sums
+
+    @staticmethod
+    def backward(ctx, g_l1, g_wl1, _g_w):
+        L = _L()
+        if g_l1 is None and g_wl1 is None:
+            return (None,) * 7
+        x, xr, m, wgt = ctx.saved_tensors
+        n, c, h, w = x.shape
+        cr = xr.shape[1]
+        g_l1 = None if g_l1 is None else g_l1.contiguous()
+        g_wl1 = None if g_wl1 is None else g_wl1.contiguous()
+        dxr = _new_cl(n, cr, h, w, xr)
+        _lib.check(L.odvae_l1_weighted_bwd_f32(x.data_ptr(), xr.data_ptr(), _lib.ptr(m), wgt.data_ptr(), ctx.per_channel, _lib.ptr(g_l1),
+                                               _lib.ptr(g_wl1), dxr.data_ptr(), n, h * w, c, cr, _lib.stream_ptr()), "l1_weighted_bwd")
+        return None, dxr, None, None, None, None, None
+
+
+def l1_weighted_sums(x, xr, box, weights, want_l1=True, shape=None, device=None):
+    """(l1_sums | None, wl1_sums, w_sums), each [N]: per sample, sum |x*box - xr*box|, sum weights * |x*box - xr*box| and sum weights
+    (broadcast against [N,C,H,W], NOT box-masked).  weights: a per-pixel or per-element map in the sense of loss_weights_layout.  xr may
+    have more channels than x: only its first C are read, in place.  x = xr = None with shape=(n, c, h, w) and the device to compute on
+    (default: the weights'): (None, None, w_sums)."""
+    n, c, h, w = tuple(x.shape) if x is not None else tuple(shape)
+    layout, wt = loss_weights_layout(weights, n, c, h, w)
+    if layout not in ("pixel", "element"):
+        raise ValueError("l1_weighted_sums: %s weights need no weight map (scale the per-sample sums instead)" % layout)
+    dev = x.device if x is not None else (wt.device if device is None else torch.device(device))
+    wt = wt.detach().to(dev).float()
+    wgt = wt.reshape(n, h * w).contiguous() if layout == "pixel" else wt.permute(0, 2, 3, 1).contiguous()
+    if x is None:
+        xr = box = None
+    return _L1WeightedSums.apply(x, xr, box, wgt, layout == "element", bool(want_l1), (n, c, h, w))
+
+
+class _CatMask(Function):
+    """cat(x * box, cond) along the channels in one pass (odvae_cat_mask_f32); gradient to x only."""
+
+    @staticmethod
+    def forward(ctx, x, box, cond):
+        L = _L()
+        x = _cl(x)
+        n, cx, h, w = x.shape
+        cc = cond.shape[1]
+        cond = _cl(cond)
+        m = box.detach().to(x.device).float().reshape(n, h * w).contiguous() if box is not None else None
+        _lib.require_device(m)
+        y = _new_cl(n, cx + cc, h, w, x)
+        _lib.check(L.odvae_cat_mask_f32(x.data_ptr(), _lib.ptr(m), cond.data_ptr(), y.data_ptr(), n, h * w, cx, cc, _lib.stream_ptr()), "cat_mask")
+        ctx.save_for_backward(m)
+        ctx.dims = (n, cx, cc, h, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        (m,) = ctx.saved_tensors
+        n, cx, cc, h, w = ctx.dims
+        dy = _cl(dy)
+        dx = _new_cl(n, cx, h, w, dy)
+        _lib.check(L.odvae_cat_mask_bwd_f32(dy.data_ptr(), _lib.ptr(m), dx.data_ptr(), n, h * w, cx, cc, _lib.stream_ptr()), "cat_mask_bwd")
+        return dx, None, None
+
+
+def cat_mask(x, box, cond):
+    """torch.cat((x * box, cond), dim=1) for the conditional discriminator: x [N,Cx,H,W], box [N,1,H,W] or None (= 1), cond [N,Cc,H,W]
+    (float, bool or uint8, any device; never multiplied by box, never differentiated).  cond None: ops.mul_mask(x, box)."""
+    if cond is None:
+        return mul_mask(x, box)
+    if not torch.is_tensor(cond) or cond.dim() != 4 or x.dim() != 4 or (cond.shape[0], cond.shape[2], cond.shape[3]) != (x.shape[0], x.shape[2], x.shape[3]) or cond.shape[1] < 1:
+        raise ValueError("cond must be [B,Cc,H,W] matching the discriminator input %s, got %s"
+                         % (tuple(x.shape), tuple(cond.shape) if torch.is_tensor(cond) else type(cond)))
+    if cond.requires_grad:
+        raise ValueError("cond requires grad: the conditional discriminator's side channel is not differentiated (detach it)")
+    if box is not None and box.numel() != x.shape[0] * x.shape[2] * x.shape[3]:
+        raise ValueError("cat_mask: box %s does not match x %s" % (tuple(box.shape), tuple(x.shape)))
+    return _CatMask.apply(x, box, cond.to(x.device).float())
+
+
 def nhwc_to_nchw(x):
     """Contiguous NCHW copy of an NHWC-in-memory tensor (hand-off to NCHW consumers)."""
     L = _L()

@@ -87,10 +87,16 @@ def main(argv=None):
                       **trainer_kwargs(trainer_cfg))
     bs = config.data.params.batch_size
 
+    # model.params.cond_key: the synthetic batch carries a side channel of disc_in_channels - out_ch channels under that key; the pose
+    # model's loss_weights_key: a per-pixel weight map
+    side = dict(cond_key=getattr(model, "cond_key", None),
+                cond_channels=model.loss.discriminator.main[0].in_channels - model.decoder.conv_out.out_channels)
+
     def make(step):
         if hasattr(model, "image_key"):      # AutoencoderKL / Autoencoder: images alone
-            return synthetic.make_image_batch(bs, opt.height, seed=opt.seed + step, image_key=model.image_key)
-        return synthetic.make_batch(bs, opt.height, seed=opt.seed + step, mask_key=getattr(model, "image_mask_key", None))
+            return synthetic.make_image_batch(bs, opt.height, seed=opt.seed + step, image_key=model.image_key, **side)
+        return synthetic.make_batch(bs, opt.height, seed=opt.seed + step, mask_key=getattr(model, "image_mask_key", None),
+                                    weights_key=getattr(model, "loss_weights_key", None), **side)
     for step in range(opt.steps):
         batch = make(step)
         losses = trainer.training_batch(batch, step, last_in_epoch=step == opt.steps - 1)   # (closes an accumulation window)

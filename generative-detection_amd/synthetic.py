@@ -16,13 +16,28 @@ def dataset_stats_standin():
     return {lab: {k: torch.tensor([0.0, 0.0]) for k in ("t3", "l", "h", "w")} for lab in LABELS}
 
 
-def make_batch(batch_size, height, width=None, seed=23, class_id=0, mask_key=None):
+def _loss_side_inputs(batch_size, height, width, seed, cond_key, cond_channels, weights_key):
+    """The entries behind the models' cond_key / loss_weights_key, each from a generator of its own (every other entry keeps its bits):
+    cond ~ U[0,1) [B,cond_channels,H,W] (a side channel of the conditional discriminator), weights in {0.25, 0.5, ..., 2} [B,1,H,W] (a
+    per-pixel weight on the NLL)."""
+    extra = {}
+    if cond_key is not None:
+        gc = torch.Generator().manual_seed(seed + 1299709)
+        extra[cond_key] = torch.rand(batch_size, int(cond_channels), height, width, generator=gc)
+    if weights_key is not None:
+        gw = torch.Generator().manual_seed(seed + 15485863)
+        extra[weights_key] = torch.randint(1, 9, (batch_size, 1, height, width), generator=gw).float() / 4
+    return extra
+
+
+def make_batch(batch_size, height, width=None, seed=23, class_id=0, mask_key=None, cond_key=None, cond_channels=2, weights_key=None):
     """The batch dict PoseAutoencoder.training_step reads; `patch` ~ U[0,1) NCHW like ToTensor output.
     mask_key (the model's image_mask_key): a seeded {0,1} alpha mask [B,1,H,W] under that key, drawn from a generator of its own so that
-    the other entries are the ones a batch without it holds."""
+    the other entries are the ones a batch without it holds.  cond_key / weights_key (the model's cond_key / loss_weights_key): the same
+    for a [B,cond_channels,H,W] side channel and a per-pixel weight map [B,1,H,W]."""
     width = width or height
     g = torch.Generator().manual_seed(seed)
-    extra = {}
+    extra = _loss_side_inputs(batch_size, height, width, seed, cond_key, cond_channels, weights_key)
     if mask_key is not None:
         gm = torch.Generator().manual_seed(seed + 104729)
         extra[mask_key] = (torch.rand(batch_size, 1, height, width, generator=gm) < 0.5).float()
@@ -41,11 +56,13 @@ def make_batch(batch_size, height, width=None, seed=23, class_id=0, mask_key=Non
     }
 
 
-def make_image_batch(batch_size, height, width=None, seed=23, image_key="image"):
-    """The batch dict AutoencoderKL.training_step reads: `image` ~ U[-1,1) as [N, H, W, 3] (get_input permutes it to NCHW)."""
+def make_image_batch(batch_size, height, width=None, seed=23, image_key="image", cond_key=None, cond_channels=2):
+    """The batch dict AutoencoderKL.training_step reads: `image` ~ U[-1,1) as [N, H, W, 3] (get_input permutes it to NCHW).
+    cond_key: as in make_batch (NCHW; the plain model has no loss_weights_key)."""
     width = width or height
     g = torch.Generator().manual_seed(seed)
-    return {image_key: torch.rand(batch_size, height, width, 3, generator=g) * 2 - 1}
+    return {**_loss_side_inputs(batch_size, height, width, seed, cond_key, cond_channels, None),
+            image_key: torch.rand(batch_size, height, width, 3, generator=g) * 2 - 1}
 
 
 def make_noise(batch_size, latent_hw, z_channels=16, dropout_p=0.7, seed=99):
@@ -62,12 +79,14 @@ def make_noise(batch_size, latent_hw, z_channels=16, dropout_p=0.7, seed=99):
             "z_noise": torch.randn(shape, generator=g), "bbox_eps": torch.randn(batch_size, 8, generator=g)}
 
 
-def model_config(yaml_path, latent_hw=16, ch=None, phase="vae", perceptual_weight=0.0, disc_factor=0.0, disc_start=0):
+def model_config(yaml_path, latent_hw=16, ch=None, phase="vae", perceptual_weight=0.0, disc_factor=0.0, disc_start=0, cond_key=None,
+                 cond_channels=2, loss_weights_key=None):
     """The model section of the reference yaml with the benchmark overrides of SURVEY.md 8(d):
     phase "vae": encoder_pretrain_steps = 0 and pose_conditioned_generation_steps = 0 on both the model and the loss, so
     the decoder runs, L1 is on and dropout sits at its final value from step 0 (the regime the metric is quoted on);
     phase "asis": thresholds untouched.  perceptual_weight / disc_factor 0 = "rec+KL only".  latent_hw adapts the pose
-    MLPs when the input is not 256x256 (latent = H/16); ch narrows the network for tests."""
+    MLPs when the input is not 256x256 (latent = H/16); ch narrows the network for tests.  cond_key (with cond_channels) / loss_weights_key:
+    the model's params of those names; a cond_key also makes the discriminator conditional (disc_conditional, disc_in_channels + cond_channels)."""
     cfg = Config.load(yaml_path)
     model = copy.deepcopy(cfg.model)
     p = model.params
@@ -88,6 +107,12 @@ def model_config(yaml_path, latent_hw=16, ch=None, phase="vae", perceptual_weigh
         p["feat_dims"] = [16, latent_hw, latent_hw]
     if ch is not None:
         p.ddconfig["ch"] = ch
+    if cond_key is not None:
+        p["cond_key"] = cond_key
+        lp["disc_conditional"] = True
+        lp["disc_in_channels"] = int(lp.get("disc_in_channels", 3)) + int(cond_channels)
+    if loss_weights_key is not None:
+        p["loss_weights_key"] = loss_weights_key
     return model, cfg
 
 

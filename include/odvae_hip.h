@@ -360,6 +360,27 @@ int odvae_rgba_terms_f32(const float* rec, const float* rgb_gt, const float* mas
                          void* workspace, size_t workspace_bytes, void* stream);
 int odvae_rgba_terms_bwd_f32(const float* rec, const float* rgb_gt, const float* mask_gt, const float* box, int l2, const float* g_l1,
                              const float* g_mask, const float* g_rec_rgb_m, const float* g_rec_rgba_m, float* d_rec, int N, int HW, void* stream);
+/* The losses' `weights` argument as a weight map (contperceptual.py:147-158: weights * nll_loss on [N,C,H,W]): three per-sample sums from
+ * one pass.  x [N][HW][C]; xr [N][HW][Cr], Cr >= C, only its first C channels are read (a 4-channel reconstruction in place: C 3, Cr 4);
+ * box [N][HW] or NULL (= 1); wgt [N][HW] (wgt_per_channel 0) or [N][HW][C] (1).  Any 4-byte aligned bases; a 16-byte aligned xr with
+ * Cr == 4 is read with one load per pixel.  Per element, every operation separately rounded: xm = x*box, rm = xr*box, t = |xm - rm|,
+ * l1_sum[n] += t, wl1_sum[n] += wgt*t, w_sum[n] += wgt (a per-pixel weight counts once per channel; w_sum is not box-masked).  Each output
+ * is skipped when NULL; all three NULL is an error.  x and xr both NULL: w_sum alone may be asked for.  The sums go through the workspace
+ * (odvae_l1_weighted_workspace_bytes(N) bytes) in a fixed order, no atomics.  N <= 65535.
+ * odvae_l1_weighted_bwd_f32: dxr [N][HW][Cr], overwritten: ((g_l1[n] + g_wl1[n]*wgt) * sign(rm - xm)) * box for c < C (0 at a tie, as
+ * odvae_l1_masked_bwd_f32; a NULL gradient counts as zero), 0 for the channels C .. Cr-1. */
+size_t odvae_l1_weighted_workspace_bytes(int N);
+int odvae_l1_weighted_sums_f32(const float* x, const float* xr, const float* box, const float* wgt, int wgt_per_channel, float* l1_sum,
+                               float* wl1_sum, float* w_sum, int N, int HW, int C, int Cr, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int odvae_l1_weighted_bwd_f32(const float* x, const float* xr, const float* box, const float* wgt, int wgt_per_channel, const float* g_l1,
+                              const float* g_wl1, float* dxr, int N, int HW, int C, int Cr, void* stream);
+/* disc_conditional: the discriminator's input torch.cat((x * mask_2d_bbox, cond), dim=1) (contperceptual.py:283-289,354-361) in one pass.
+ * x [N][HW][Cx], box [N][HW] or NULL (= 1), cond [N][HW][Cc], y [N][HW][Cx+Cc]; cond is copied, never multiplied by box.  Any 4-byte
+ * aligned bases (a 16-byte aligned y with Cx + Cc == 4 is written with one store per pixel); N <= 65535, HW * (Cx + Cc) < 2^31.
+ * odvae_cat_mask_bwd_f32: dx [N][HW][Cx] = dy[..., :Cx] * box, dy [N][HW][Cx+Cc]. */
+int odvae_cat_mask_f32(const float* x, const float* box, const float* cond, float* y, int N, int HW, int Cx, int Cc, void* stream);
+int odvae_cat_mask_bwd_f32(const float* dy, const float* box, float* dx, int N, int HW, int Cx, int Cc, void* stream);
 /* bias gradient of a 1x1 convolution: out[c] = sum_rows x[row][c] */
 size_t odvae_colsum_workspace_bytes(int64_t rows, int C);
 int odvae_colsum_f32(const float* x, int64_t rows, int C, float* out, void* workspace, size_t workspace_bytes, void* stream);
