@@ -716,12 +716,20 @@ __global__ void norm_final_kernel(const float* __restrict__ part, int nblk, floa
     out[1] = coef;
   }
 }
-// torch.optim.Adam (no weight decay, no amsgrad); grads are scaled by *clip (device scalar) when non-null
+// torch.optim.Adam (no weight decay, no amsgrad).  CLAMP = false: grads are scaled by *clip (device scalar) when non-null.  CLAMP = true
+// (gradient_clip_algorithm: value): grads go through torch.clamp(g, -clamp, +clamp) instead -- two compares and selects, so NaN stays NaN,
+// +-inf becomes +-clamp and -0.0 stays -0.0 (fminf / fmaxf would turn NaN into the bound)
+template <bool CLAMP>
+__device__ __forceinline__ float adam_grad(float g, float cs) {
+  if (CLAMP) return g < -cs ? -cs : (g > cs ? cs : g);
+  return g * cs;
+}
+template <bool CLAMP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                    float lr, float beta1, float beta2, float eps,
-                                                   float bc1, float bc2_sqrt, const float* __restrict__ clip) {
-  const float cs = clip ? clip[1] : 1.f;
+                                                   float bc1, float bc2_sqrt, const float* __restrict__ clip, float clamp) {
+  const float cs = CLAMP ? clamp : (clip ? clip[1] : 1.f);
   const float step = lr / bc1;
   const int64_t n4 = n / 4;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
@@ -733,7 +741,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     float mm[4] = {mv.x, mv.y, mv.z, mv.w}, ww[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float gr = gg[j] * cs;
+      const float gr = adam_grad<CLAMP>(gg[j], cs);
       mm[j] = beta1 * mm[j] + (1.f - beta1) * gr;
       ww[j] = beta2 * ww[j] + (1.f - beta2) * gr * gr;
       pp[j] -= step * mm[j] / (sqrtf(ww[j]) / bc2_sqrt + eps);
@@ -744,12 +752,136 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
   if (blockIdx.x == 0)
     for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
-      const float gr = g[i] * cs;
+      const float gr = adam_grad<CLAMP>(g[i], cs);
       const float mi = beta1 * m[i] + (1.f - beta1) * gr;
       const float vi = beta2 * v[i] + (1.f - beta2) * gr * gr;
       m[i] = mi; v[i] = vi;
       p[i] -= step * mi / (sqrtf(vi) / bc2_sqrt + eps);
     }
+}
+
+// ---- segmented p-norms of one flat arena (Trainer(track_grad_norm=p), optim.FusedAdam.grad_norms): per-segment norms and their total.
+// Stage 1 (one launch per kSegNormSegs segments, the table a by-value kernel argument): a segment is cut into chunks of kSegNormChunk floats,
+// one block reduces one chunk to one double in the workspace; the block of a segment's first chunk also writes that segment's
+// {first partial, partials, counts} record there, so the later stages need no table.  Stage 2: one wavefront per segment folds its partials
+// and writes out[seg].  Stage 3: one block folds the f32-rounded out[] of the counting segments into out[n_seg].  Everything is summed in
+// f64 in an order fixed by the chunk grid alone (thread -> wave butterfly -> waves in order; partials lane-strided -> butterfly): no atomics,
+// the same bits on any launch grid.  A chunk never reads outside its segment: float4 up to the last whole one, then at most 3 scalars.
+constexpr int kSegNormSegs = 160;
+constexpr int kSegNormChunk = 4096;      // floats: four float4 per thread of a 256-thread block
+enum { kNormMax = 0, kNormL1 = 1, kNormL2 = 2, kNormP = 3 };
+struct SegNormTable {
+  int64_t off[kSegNormSegs];
+  int64_t len[kSegNormSegs];
+  unsigned chunk_prefix[kSegNormSegs + 1];
+  unsigned char counts[kSegNormSegs];
+  int count;
+  int seg_base;            // index of this launch's first segment in out[] / the records
+  unsigned chunk_base;     // partials in front of this launch's first chunk
+};
+static_assert(sizeof(SegNormTable) <= 3900, "the segment table travels in the kernel arguments (4 KiB) beside four scalars");
+struct SegNormRecord { unsigned first, chunks, counts, pad; };
+
+// torch.norm(inf) propagates NaN; fmax drops it
+__device__ __forceinline__ double nan_max(double a, double b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
+template <int KIND>
+__device__ __forceinline__ double norm_take(double s, float x, double p) {
+  const double a = (double)fabsf(x);
+  if (KIND == kNormMax) return nan_max(s, a);
+  if (KIND == kNormL1) return s + a;
+  if (KIND == kNormL2) return s + a * a;      // (the product of two f32 is exact in f64)
+  return s + pow(a, p);
+}
+template <int KIND>
+__device__ __forceinline__ double norm_fold(double a, double b) { return KIND == kNormMax ? nan_max(a, b) : a + b; }
+template <int KIND>
+__device__ __forceinline__ double norm_wave(double v) {      // fixed butterfly order
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = norm_fold<KIND>(v, __shfl_xor(v, o, 64));
+  return v;
+}
+template <int KIND>
+__device__ __forceinline__ float norm_finish(double s, double p) {
+  if (KIND == kNormL2) return (float)sqrt(s);
+  if (KIND == kNormP) return (float)pow(s, 1.0 / p);
+  return (float)s;
+}
+// 256 threads -> one value in thread 0 (waves folded in order 0..3)
+template <int KIND>
+__device__ __forceinline__ double norm_block(double s, double* sh) {
+  s = norm_wave<KIND>(s);
+  __syncthreads();      // (sh may still be read from the previous chunk)
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return norm_fold<KIND>(norm_fold<KIND>(norm_fold<KIND>(sh[0], sh[1]), sh[2]), sh[3]);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void seg_norm_partial_kernel(const float* __restrict__ g, const SegNormTable t, double p,
+                                                               double* __restrict__ part, SegNormRecord* __restrict__ rec) {
+  __shared__ double sh[4];
+  const unsigned total = t.chunk_prefix[t.count];
+  for (unsigned c = blockIdx.x; c < total; c += gridDim.x) {
+    int lo = 0, hi = t.count - 1;            // last segment whose prefix <= c
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (t.chunk_prefix[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    const int64_t base = (int64_t)(c - t.chunk_prefix[lo]) * kSegNormChunk;
+    const float* __restrict__ s = g + t.off[lo] + base;      // 16-byte aligned: the offset is, and so is a whole number of chunks
+    const int64_t left = t.len[lo] - base;
+    const int n = left < kSegNormChunk ? (int)left : kSegNormChunk;
+    const int n4 = n >> 2;
+    double acc = 0.0;
+    if (n4 == kSegNormChunk / 4) {           // full chunk: all four loads in flight before the first add
+      float4 a[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[k] = reinterpret_cast<const float4*>(s)[threadIdx.x + 256 * k];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        acc = norm_take<KIND>(acc, a[k].x, p); acc = norm_take<KIND>(acc, a[k].y, p);
+        acc = norm_take<KIND>(acc, a[k].z, p); acc = norm_take<KIND>(acc, a[k].w, p);
+      }
+    } else {
+      for (int i = threadIdx.x; i < n4; i += 256) {
+        const float4 a = reinterpret_cast<const float4*>(s)[i];
+        acc = norm_take<KIND>(acc, a.x, p); acc = norm_take<KIND>(acc, a.y, p);
+        acc = norm_take<KIND>(acc, a.z, p); acc = norm_take<KIND>(acc, a.w, p);
+      }
+      for (int i = n4 * 4 + threadIdx.x; i < n; i += 256) acc = norm_take<KIND>(acc, s[i], p);
+    }
+    acc = norm_block<KIND>(acc, sh);
+    if (threadIdx.x == 0) {
+      part[t.chunk_base + c] = acc;
+      if (c == t.chunk_prefix[lo]) {
+        SegNormRecord r;
+        r.first = t.chunk_base + c; r.chunks = t.chunk_prefix[lo + 1] - c; r.counts = t.counts[lo]; r.pad = 0;
+        rec[t.seg_base + lo] = r;
+      }
+    }
+  }
+}
+// one wavefront per segment
+template <int KIND>
+__global__ __launch_bounds__(256) void seg_norm_final_kernel(const double* __restrict__ part, const SegNormRecord* __restrict__ rec, int n_seg,
+                                                             double p, float* __restrict__ out) {
+  const int seg = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (seg >= n_seg) return;
+  const SegNormRecord r = rec[seg];
+  double s = 0.0;
+  for (unsigned i = threadIdx.x & 63; i < r.chunks; i += 64) s = norm_fold<KIND>(s, part[r.first + i]);
+  s = norm_wave<KIND>(s);
+  if ((threadIdx.x & 63) == 0) out[seg] = norm_finish<KIND>(s, p);
+}
+// out[n_seg] = the same norm of the f32 values out[0 .. n_seg) of the segments that count (one block)
+template <int KIND>
+__global__ __launch_bounds__(256) void seg_norm_total_kernel(const SegNormRecord* __restrict__ rec, int n_seg, double p, float* __restrict__ out) {
+  __shared__ double sh[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n_seg; i += 256)
+    if (rec[i].counts) s = norm_take<KIND>(s, out[i], p);
+  s = norm_block<KIND>(s, sh);
+  if (threadIdx.x == 0) out[n_seg] = norm_finish<KIND>(s, p);
 }
 
 // ---- gradient accumulation: arena[dst_off[i] + j] += src[i][j] over up to kGradAccSegs tensors per launch (Trainer(accumulate_grad_batches=N),
@@ -1378,8 +1510,106 @@ int odvae_adam_step_f32(float* p, const float* g, float* m, float* v, int64_t n,
   ODVAE_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step: arenas must be 16-byte aligned");
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_1d(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, n, lr, beta1, beta2, eps, bc1, bc2_sqrt, clip);
+  hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_1d(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, n, lr, beta1, beta2, eps, bc1, bc2_sqrt, clip, 0.f);
   ODVAE_LAUNCH_CHECK("adam_step");
+  return ODVAE_OK;
+}
+
+// the same step with gr = clamp(g, -clamp, +clamp) in place of g * coefficient (torch.nn.utils.clip_grad_value_ folded into the step)
+int odvae_adam_step_clamp_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                              float eps, int step, float clamp, void* stream) {
+  ODVAE_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "adam_step_clamp: bad arguments");
+  ODVAE_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step_clamp: arenas must be 16-byte aligned");
+  ODVAE_CHECK_ARG(clamp > 0.f, "adam_step_clamp: the clamp must be > 0, got %g", (double)clamp);      // (a NaN fails the comparison too)
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+  hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_1d(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, n, lr, beta1, beta2, eps, bc1, bc2_sqrt,
+                     (const float*)nullptr, clamp);
+  ODVAE_LAUNCH_CHECK("adam_step_clamp");
+  return ODVAE_OK;
+}
+
+int odvae_grad_seg_norms_segments_per_launch(void) { return kSegNormSegs; }
+
+// chunks of all segments, or -1 when a length is <= 0 or the chunks do not fit the 31-bit chunk index
+static int64_t seg_norm_chunks(const int64_t* len, int n_seg) {
+  int64_t chunks = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    if (len[i] <= 0 || len[i] > (int64_t)0x7fffffff * kSegNormChunk) return -1;
+    chunks += ceil_div64(len[i], kSegNormChunk);
+    if (chunks > 0x7fffffffll) return -1;
+  }
+  return chunks;
+}
+
+// one record per segment, then one double per chunk; 0 for arguments odvae_grad_seg_norms_f32 refuses
+size_t odvae_grad_seg_norms_workspace_bytes(const int64_t* len, int n_seg) {
+  if (!len || n_seg <= 0) return 0;
+  const int64_t chunks = seg_norm_chunks(len, n_seg);
+  if (chunks < 0) return 0;
+  return (size_t)n_seg * sizeof(SegNormRecord) + (size_t)chunks * sizeof(double);
+}
+
+extern "C++" {
+template <int KIND>
+static void seg_norm_launch(const float* g, const int64_t* off, const int64_t* len, const unsigned char* counts, int n_seg, double p, float* out,
+                            SegNormRecord* rec, double* part, hipStream_t st) {
+  SegNormTable t;
+  uint64_t chunk_base = 0;
+  for (int i = 0; i < n_seg;) {
+    uint64_t chunks = 0;
+    int k = 0;
+    t.seg_base = i;
+    for (; k < kSegNormSegs && i < n_seg; ++k, ++i) {
+      t.off[k] = off[i];
+      t.len[k] = len[i];
+      t.counts[k] = counts ? (counts[i] != 0) : 1;
+      t.chunk_prefix[k] = (unsigned)chunks;
+      chunks += (uint64_t)ceil_div64(len[i], kSegNormChunk);
+    }
+    for (int j = k; j <= kSegNormSegs; ++j) t.chunk_prefix[j] = (unsigned)chunks;
+    for (int j = k; j < kSegNormSegs; ++j) { t.off[j] = 0; t.len[j] = 0; t.counts[j] = 0; }
+    t.count = k;
+    t.chunk_base = (unsigned)chunk_base;
+    hipLaunchKernelGGL(seg_norm_partial_kernel<KIND>, dim3((unsigned)std::min<uint64_t>(chunks, 65536)), dim3(256), 0, st, g, t, p, part, rec);
+    chunk_base += chunks;
+  }
+  hipLaunchKernelGGL(seg_norm_final_kernel<KIND>, dim3(ceil_div(n_seg, 4)), dim3(256), 0, st, (const double*)part, (const SegNormRecord*)rec, n_seg, p, out);
+  hipLaunchKernelGGL(seg_norm_total_kernel<KIND>, dim3(1), dim3(256), 0, st, (const SegNormRecord*)rec, n_seg, p, out);
+}
+}  // extern "C++"
+
+// out[i] = p-norm of g[off[i] .. off[i] + len[i]), i < n_seg; out[n_seg] = the same norm of the f32 values out[i] with counts[i] != 0
+// (counts null: all).  off / len / counts are host arrays.  ceil(n_seg / K) + 2 launches; everything is validated before the first
+int odvae_grad_seg_norms_f32(const float* g, int64_t n, const int64_t* off, const int64_t* len, const unsigned char* counts, int n_seg,
+                             int kind, double p, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  ODVAE_CHECK_ARG(g && out && off && len && n > 0, "grad_seg_norms: null arena / table / out");
+  ODVAE_CHECK_ARG(n_seg > 0, "grad_seg_norms: n_seg %d <= 0", n_seg);
+  ODVAE_CHECK_ARG(((uintptr_t)g & 15) == 0 && ((uintptr_t)out & 3) == 0, "grad_seg_norms: g must be 16-byte, out 4-byte aligned");
+  ODVAE_CHECK_ARG(kind == kNormMax || kind == kNormL1 || kind == kNormL2 || kind == kNormP, "grad_seg_norms: unknown kind %d", kind);
+  ODVAE_CHECK_ARG(kind != kNormP || (p > 0.0 && p <= 1.7976931348623157e308), "grad_seg_norms: the general kind needs a finite p > 0, got %g", p);
+  for (int i = 0; i < n_seg; ++i) {
+    ODVAE_CHECK_ARG(len[i] > 0, "grad_seg_norms: segment %d has length %lld", i, (long long)len[i]);
+    ODVAE_CHECK_ARG(off[i] >= 0 && (off[i] & 3) == 0, "grad_seg_norms: segment %d starts at float %lld, not on a 16-byte boundary", i, (long long)off[i]);
+    ODVAE_CHECK_ARG(off[i] <= n && len[i] <= n - off[i], "grad_seg_norms: segment %d [%lld, +%lld) leaves the arena of %lld floats", i,
+                    (long long)off[i], (long long)len[i], (long long)n);
+  }
+  const size_t need = odvae_grad_seg_norms_workspace_bytes(len, n_seg);
+  ODVAE_CHECK_ARG(need > 0, "grad_seg_norms: the segments have too many chunks of %d floats", kSegNormChunk);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15) != 0) {
+    odvae_set_error("grad_seg_norms: needs %zu workspace bytes, 16-byte aligned", need);
+    return ODVAE_ERR_WORKSPACE;
+  }
+  SegNormRecord* rec = static_cast<SegNormRecord*>(workspace);
+  double* part = reinterpret_cast<double*>(rec + n_seg);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (kind) {
+    case kNormMax: seg_norm_launch<kNormMax>(g, off, len, counts, n_seg, p, out, rec, part, st); break;
+    case kNormL1: seg_norm_launch<kNormL1>(g, off, len, counts, n_seg, p, out, rec, part, st); break;
+    case kNormL2: seg_norm_launch<kNormL2>(g, off, len, counts, n_seg, p, out, rec, part, st); break;
+    default: seg_norm_launch<kNormP>(g, off, len, counts, n_seg, p, out, rec, part, st); break;
+  }
+  ODVAE_LAUNCH_CHECK("grad_seg_norms");
   return ODVAE_OK;
 }
 

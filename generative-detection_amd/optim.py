@@ -22,6 +22,9 @@ class FusedAdam(torch.optim.Optimizer):
         self._steps = 0
         self._clip = None       # device [norm, coef] written by clip_grad_norm_
         self._clip_armed = False
+        self._clamp = None      # clip_grad_value_'s bound, armed for the next step()
+        self._norms = None      # device [n_params + 1] written by grad_norms
+        self._norm_args = {}    # touched-parameter tuple -> cached ctypes (off, len, counts) arrays of the segmented-norm entry point
         self._window = False    # True between begin_microbatch() and the next zero_grad() / step(): the arena holds running sums
         self._acc_args = {}     # fresh-parameter tuple -> cached ctypes (dst_off, numel) arrays of the accumulate entry point
         self.accumulate_calls = 0   # calls of odvae_grad_accumulate_f32 so far (one launch each; host counter, tests read it)
@@ -162,6 +165,7 @@ class FusedAdam(torch.optim.Optimizer):
         self._touched.clear()
         self._window = False
         self._clip_armed = False
+        self._clamp = None
 
     def _ensure_grad_views(self):
         if self._window:
@@ -199,8 +203,55 @@ class FusedAdam(torch.optim.Optimizer):
         wp, wn = _lib.workspace.get(8192, f["g"].device)
         _lib.check(L.odvae_grad_norm_f32(f["g"].data_ptr(), f["total"], float(max_norm), self._clip.data_ptr(), wp, wn,
                                          _lib.stream_ptr()), "grad_norm")
+        if self._clamp is not None:
+            raise RuntimeError("FusedAdam: clip_grad_value_ is already armed for this step; one step takes one kind of clipping")
         self._clip_armed = True
         return self._clip[0]
+
+    def clip_grad_value_(self, clip_value):
+        """torch.nn.utils.clip_grad_value_ for the next step(): every gradient element goes through clamp(g, -clip_value, +clip_value)
+        inside the Adam kernel (odvae_adam_step_clamp_f32: no extra pass over the gradients).  Deliberate deviation from torch, the same
+        one clip_grad_norm_ has: `.grad` is NOT rewritten, the arena keeps the unclipped gradients.  Arming both kinds of clipping
+        before one step raises; step() and discard_window() disarm."""
+        c = float(clip_value)
+        if not c > 0.0 or c == float("inf"):
+            raise ValueError("clip_grad_value_: clip_value must be a finite number > 0, got %r" % (clip_value,))
+        if self._clip_armed:
+            raise RuntimeError("FusedAdam: clip_grad_norm_ is already armed for this step; one step takes one kind of clipping")
+        self.materialize()
+        self._clamp = c
+
+    def grad_norms(self, norm_type=2.0):
+        """The p-norm of every parameter's gradient and their total (torch.tensor([g.norm(p) ...]).norm(p) over the parameters a
+        backward has reached since the last step: the host set `_touched`, nothing is read back) as ONE device f32 vector
+        [n_params + 1] in arena order, total last; the buffer is reused by the next call.  norm_type: a number > 0 or 'inf'.  Fresh or
+        accumulated gradients are brought into the arena first; ceil(n_params / K) + 2 launches (odvae_grad_seg_norms_f32), no host wait.
+        A parameter no backward reached reads as the norm of its (zeroed) slice and does not enter the total."""
+        import ctypes
+        kind, p = norm_kind(norm_type)
+        f = self.materialize()
+        self._ensure_grad_views()
+        L = _lib.load()
+        params = f["params"]
+        key = tuple(sorted(self._touched))
+        args = self._norm_args.get(key)
+        if args is None:       # offsets and sizes never change; the counting set is the same from step to step
+            if len(self._norm_args) >= 16:
+                self._norm_args.clear()
+            n = len(params)
+            lens = (ctypes.c_int64 * n)(*[q.numel() for q in params])
+            flags = bytearray(n)
+            for i in key:
+                flags[i] = 1
+            args = self._norm_args[key] = ((ctypes.c_int64 * n)(*f["offsets"]), lens, (ctypes.c_ubyte * n).from_buffer_copy(bytes(flags)),
+                                           int(L.odvae_grad_seg_norms_workspace_bytes(lens, n)))
+        off, lens, counts, need = args
+        if self._norms is None:
+            self._norms = torch.zeros(len(params) + 1, dtype=torch.float32, device=f["g"].device)
+        wp, wn = _lib.workspace.get(need, f["g"].device)
+        _lib.check(L.odvae_grad_seg_norms_f32(f["g"].data_ptr(), f["total"], off, lens, counts, len(params), kind, p,
+                                              self._norms.data_ptr(), wp, wn, _lib.stream_ptr()), "grad_seg_norms")
+        return self._norms
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -227,6 +278,12 @@ class FusedAdam(torch.optim.Optimizer):
                     runs.append(cur)
         clip = self._clip.data_ptr() if self._clip_armed else None
         for beg, end, count in runs:
+            if self._clamp is not None:
+                _lib.check(L.odvae_adam_step_clamp_f32(f["p"].data_ptr() + 4 * beg, f["g"].data_ptr() + 4 * beg,
+                                                       f["m"].data_ptr() + 4 * beg, f["v"].data_ptr() + 4 * beg, end - beg,
+                                                       float(g0["lr"]), float(g0["betas"][0]), float(g0["betas"][1]),
+                                                       float(g0["eps"]), count, self._clamp, _lib.stream_ptr()), "adam_step_clamp")
+                continue
             _lib.check(L.odvae_adam_step_f32(f["p"].data_ptr() + 4 * beg, f["g"].data_ptr() + 4 * beg,
                                              f["m"].data_ptr() + 4 * beg, f["v"].data_ptr() + 4 * beg, end - beg,
                                              float(g0["lr"]), float(g0["betas"][0]), float(g0["betas"][1]),
@@ -235,6 +292,7 @@ class FusedAdam(torch.optim.Optimizer):
         ops.PACK_CACHE.bump(stepped=[f["params"][i] for i in self._touched])   # parameters changed under torch's version counters: conv weight packs are stale
         self._touched.clear()
         self._clip_armed = False
+        self._clamp = None
         self._window = False
         return loss
 
@@ -273,6 +331,23 @@ class FusedAdam(torch.optim.Optimizer):
                 self._counts[i] = int(round(float(st["step"])))
         self._steps = max(self._counts) if self._counts else 0
         self.state.clear()
+
+
+NORM_MAX, NORM_L1, NORM_L2, NORM_P = 0, 1, 2, 3      # ODVAE_NORM_* of include/odvae_hip.h
+
+
+def norm_kind(norm_type):
+    """(kind, p) of the segmented-norm entry point for a torch-style norm_type: a number > 0, float('inf') or 'inf'."""
+    if isinstance(norm_type, str):
+        if norm_type != "inf":
+            raise ValueError("norm_type must be a number > 0 or 'inf', got %r" % (norm_type,))
+        return NORM_MAX, 0.0
+    if isinstance(norm_type, bool) or not isinstance(norm_type, (int, float)) or not float(norm_type) > 0.0:
+        raise ValueError("norm_type must be a number > 0 or 'inf', got %r" % (norm_type,))
+    p = float(norm_type)
+    if p == float("inf"):
+        return NORM_MAX, 0.0
+    return (NORM_L1 if p == 1.0 else NORM_L2 if p == 2.0 else NORM_P), p
 
 
 def make_adam(params, lr, betas):

@@ -45,7 +45,9 @@ def parse(argv):
 
 def trainer_kwargs(trainer_cfg):
     """The `lightning.trainer` keys of the yaml this Trainer honours: gradient_clip_val, precision, detect_anomaly (yaml:138; absent
-    = None, which leaves the choice to ODVAE_DETECT_ANOMALY), accumulate_grad_batches (yaml:134; passed on only when it is not 1) and sync_batchnorm (passed on only when the yaml sets it)."""
+    = None, which leaves the choice to ODVAE_DETECT_ANOMALY), accumulate_grad_batches (yaml:134; passed on only when it is not 1) and sync_batchnorm (passed on only when the yaml sets it); gradient_clip_algorithm ('norm' / 'value') and track_grad_norm (-1, a
+    number > 0 or 'inf'), the two PL-1.9 Trainer arguments of the gradient path, likewise only when the yaml or a dotlist override
+    (lightning.trainer.track_grad_norm=2) sets them."""
     kw = {"gradient_clip_val": trainer_cfg.get("gradient_clip_val", None), "precision": trainer_cfg.get("precision", None),
           "detect_anomaly": trainer_cfg.get("detect_anomaly", None)}
     accumulate = trainer_cfg.get("accumulate_grad_batches", 1)
@@ -53,6 +55,9 @@ def trainer_kwargs(trainer_cfg):
         kw["accumulate_grad_batches"] = accumulate
     if "sync_batchnorm" in trainer_cfg:      # (PL: SyncBatchNorm over the discriminator's BatchNorm layers; Trainer refuses a non-bool)
         kw["sync_batchnorm"] = trainer_cfg["sync_batchnorm"]
+    for key in ("gradient_clip_algorithm", "track_grad_norm"):      # (Trainer validates both)
+        if key in trainer_cfg:
+            kw[key] = trainer_cfg[key]
     return kw
 
 

@@ -33,7 +33,7 @@ class Trainer:
     def __init__(self, model, gradient_clip_val=None, optimizer_indices=(0, 1), process_group=None, bucket_mb=None, precision=None,
                  distributed=None, comm_dtype=None, callbacks=(), logger=None, comm_f32_accumulate=False,
                  detect_anomaly=None, accumulate_grad_batches=1, perceptual_precision=None, discriminator_precision=None,
-                 sync_batchnorm=False, float32_matmul_precision=None):
+                 sync_batchnorm=False, float32_matmul_precision=None, gradient_clip_algorithm=None, track_grad_norm=-1):
         """optimizer_indices: which of the model's optimizers run each batch; (0,) is the "rec+KL only" benchmark
         configuration (discriminator off, optimizer 1 skipped -- SURVEY.md 8(d)).
         comm_dtype: dtype of the gradient buckets on the wire; None = f32 in every precision -- what the reference's `strategy: ddp`
@@ -59,7 +59,32 @@ class Trainer:
         process group (gan.BatchNormLReLU.dist_group).  Not data-parallel, one rank, or use_actnorm: nothing changes.
         float32_matmul_precision: "highest", "high", "medium" or "torch" -- what the reference's launcher sets with
         torch.set_float32_matmul_precision (train.py:521: 'medium'); ops/precision.py.  Process-global, like torch's, and not
-        restored when the trainer goes away.  None leaves the setting (ODVAE_FLOAT32_MATMUL_PRECISION, default highest) alone."""
+        restored when the trainer goes away.  None leaves the setting (ODVAE_FLOAT32_MATMUL_PRECISION, default highest) alone.
+        gradient_clip_algorithm: the PL-1.9 Trainer argument.  None or "norm": gradient_clip_val is the global L2 bound of
+        clip_grad_norm_ (today's path, bit for bit).  "value": gradient_clip_val is an element-wise bound, torch.nn.utils.clip_grad_value_
+        (FusedAdam clamps inside the Adam kernel and leaves `.grad` unclipped, as its norm clipping does); it needs a gradient_clip_val.
+        Anything else raises ValueError.
+        track_grad_norm: the PL-1.9 Trainer argument.  -1 = off; a number > 0, 'inf' or float('inf') = on every stepping batch, after the
+        backward, the reducer's finish() and the anomaly check and BEFORE clipping, the p-norm of the gradient of every parameter of
+        the optimizer being stepped that the backward reached, and their total, go through `model.log_dict` under
+        "grad_<p>_norm/<name>" and "grad_<p>_norm_total" (<p> = float(p): 2.0, inf; <name> from model.named_parameters()).  The values
+        are 0-d views of one device vector (FusedAdam.grad_norms: no host wait); `self.grad_norms[optimizer_idx] = (names, vector)`
+        keeps each optimizer's last vector, total last.  Data-parallel: the norms of the reduced gradients, the same on every rank.
+        Inside an accumulation window nothing is tracked before the window's last batch; then the norms are of the summed gradients.
+        Tracking changes no bit of the run.  Deviation from PL (restated, not pinned against it: pytorch_lightning is not available to
+        the build): PL walks every named parameter with a non-None `.grad`, stale gradients of the untoggled optimizer included; this
+        trainer tracks the stepped optimizer's parameters only.  An optimizer that is not a FusedAdam (CPU, gloo) takes p.grad.norm(p) of its
+        parameters whose `.grad` is not None (PL's rule; the gradient reducer hands every parameter a slice of its bucket, so an unreached one
+        reads 0 there) and torch.nn.utils.clip_grad_value_.  bool, 0, other negatives, NaN and other strings raise ValueError."""
+        if gradient_clip_algorithm not in (None, "norm", "value"):
+            raise ValueError("gradient_clip_algorithm must be None, 'norm' or 'value', got %r" % (gradient_clip_algorithm,))
+        if gradient_clip_algorithm == "value" and not gradient_clip_val:
+            raise ValueError("gradient_clip_algorithm='value' needs a gradient_clip_val, got %r" % (gradient_clip_val,))
+        self.gradient_clip_algorithm = gradient_clip_algorithm
+        self.track_grad_norm = parse_track_grad_norm(track_grad_norm)      # None = off, else a float (inf for 'inf')
+        self.grad_norms = {}              # optimizer_idx -> (names, device vector [len(names) + 1], total last) of its last tracked step
+        self._param_names = None
+        self._norm_picks = {}             # (optimizer_idx, reached parameters) -> device index vector, when not every parameter was reached
         if float32_matmul_precision is not None:
             from . import ops
             ops.set_float32_matmul_precision(float32_matmul_precision)      # (a bad name raises before anything else is touched)
@@ -223,8 +248,15 @@ class Trainer:
                         self._check_anomaly(an, idx, red)
                     if final:
                         # (FusedAdam inside a window: clip_grad_norm_ / step add whatever this backward left fresh to the arena's sums first)
+                        if self.track_grad_norm is not None:
+                            self._track_grad_norms(idx, opt)      # the unclipped gradients, as in PL
                         if self.clip:
-                            if hasattr(opt, "clip_grad_norm_"):
+                            if self.gradient_clip_algorithm == "value":
+                                if hasattr(opt, "clip_grad_value_"):
+                                    opt.clip_grad_value_(self.clip)
+                                else:
+                                    torch.nn.utils.clip_grad_value_([p for g in opt.param_groups for p in g["params"]], self.clip)
+                            elif hasattr(opt, "clip_grad_norm_"):
                                 opt.clip_grad_norm_(self.clip)
                             else:
                                 torch.nn.utils.clip_grad_norm_([p for g in opt.param_groups for p in g["params"]], self.clip)
@@ -251,6 +283,40 @@ class Trainer:
         if hook is not None:
             hook(losses, batch, batch_idx)
         return losses
+
+    def _track_grad_norms(self, idx, opt):
+        """track_grad_norm for the optimizer about to be stepped: names, one vector, log_dict (the constructor's docstring)."""
+        p = self.track_grad_norm
+        if self._param_names is None:
+            self._param_names = {id(q): name for name, q in self.model.named_parameters()}
+        names = self._param_names
+        params = [q for g in opt.param_groups for q in g["params"]]
+        if hasattr(opt, "grad_norms"):
+            reached = [i for i in sorted(opt._touched) if id(params[i]) in names]      # (read before grad_norms: a host set)
+            vec = opt.grad_norms(p)
+            if len(reached) != len(params):      # some parameters had no gradient: their entries leave the vector (index cached per set)
+                key = (idx, tuple(reached))
+                pick = self._norm_picks.get(key)
+                if pick is None:
+                    if len(self._norm_picks) >= 16:
+                        self._norm_picks.clear()
+                    pick = self._norm_picks[key] = torch.tensor(reached + [len(params)], dtype=torch.long, device=vec.device)
+                vec = vec.index_select(0, pick)
+            logged = [names[id(params[i])] for i in reached]
+            picked = vec
+            values = vec.unbind(0)      # 0-d views of the one vector
+            total = values[-1]
+        else:
+            keep = [q for q in params if q.grad is not None and id(q) in names]
+            logged = [names[id(q)] for q in keep]
+            with torch.no_grad():
+                values = [q.grad.detach().norm(p) for q in keep]
+                total = torch.stack(values).norm(p) if values else torch.zeros(())
+                picked = torch.stack(values + [total])
+        self.grad_norms[idx] = (logged, picked)
+        d = {"grad_%s_norm/%s" % (p, name): v for name, v in zip(logged, values)}
+        d["grad_%s_norm_total" % p] = total
+        self.model.log_dict(d, prog_bar=False, logger=True, on_step=True, on_epoch=False)
 
     def _check_anomaly(self, an, idx, red):
         """One host wait for the phase's anomaly record (all-reduced MIN over the ranks when data-parallel, so every rank raises);
@@ -463,6 +529,19 @@ class Trainer:
             for o, sd in zip(self.optimizers, states):
                 o.load_state_dict(sd)
         return res
+
+
+def parse_track_grad_norm(value):
+    """PL-1.9's Trainer(track_grad_norm=...): -1 -> None (off); a number > 0, 'inf' or float('inf') -> that norm as a float."""
+    if isinstance(value, str):
+        if value == "inf":
+            return float("inf")
+    elif not isinstance(value, bool) and isinstance(value, (int, float)):
+        if value == -1:
+            return None
+        if value > 0:       # (NaN fails the comparison)
+            return float(value)
+    raise ValueError("track_grad_norm must be -1 (off), a number > 0 or 'inf', got %r" % (value,))
 
 
 def _batch_size(batch):

@@ -389,6 +389,30 @@ int odvae_grad_norm_f32(const float* g, int64_t n, float max_norm, float* out, v
 /* torch.optim.Adam step (src/models/autoencoder.py:365-377) over flat arenas; clip = odvae_grad_norm_f32 output or NULL */
 int odvae_adam_step_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                         float eps, int step, const float* clip, void* stream);
+/* The same step with gr = clamp(g, -clamp, +clamp) in place of g * coefficient (lightning.trainer.gradient_clip_algorithm: value;
+ * torch.nn.utils.clip_grad_value_ folded into the step, g itself is not rewritten).  torch.clamp's rules: NaN stays NaN, +-inf becomes
+ * +-clamp, -0.0 stays -0.0.  clamp is a host float > 0 (anything else, NaN included, is refused). */
+int odvae_adam_step_clamp_f32(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                              float eps, int step, float clamp, void* stream);
+/* Segmented p-norms of one flat f32 arena (lightning.trainer.track_grad_norm): out[i] = the norm of g[off[i] .. off[i] + len[i]) for
+ * i < n_seg, out[n_seg] = the same kind of norm of the f32 values out[i] of the segments with counts[i] != 0 (counts NULL: all of them;
+ * none: 0) -- what torch.tensor([p.grad.norm(k) ...]).norm(k) computes.  kind: ODVAE_NORM_MAX ('inf': the largest |g|, a NaN propagates
+ * as in torch.norm), ODVAE_NORM_L1, ODVAE_NORM_L2, ODVAE_NORM_P (the general kind, p finite and > 0; p is ignored by the others).
+ * Every sum is taken in f64 ((double)g products, pow in f64), in an order fixed by the segments alone: no atomics, the same bits on any
+ * launch grid; a segment's norm is (float)S, (float)sqrt(S) or (float)pow(S, 1 / p), the total is summed in f64 again and rounded once.
+ * off / len / counts are host arrays (floats; len >= 1, off a multiple of 4 floats, off + len <= n); nothing outside a segment is read,
+ * nothing but out[0 .. n_seg] is written.  The tables travel in the kernel arguments: no copy, no allocation, no host wait;
+ * ceil(n_seg / K) + 2 launches, K = odvae_grad_seg_norms_segments_per_launch() (one block per 4096-float chunk of a segment, one
+ * wavefront per segment, one block for the total).  workspace: 16-byte aligned, odvae_grad_seg_norms_workspace_bytes(len, n_seg) bytes
+ * (0 for lengths the call refuses).  A refused call launches nothing. */
+#define ODVAE_NORM_MAX 0
+#define ODVAE_NORM_L1 1
+#define ODVAE_NORM_L2 2
+#define ODVAE_NORM_P 3
+int odvae_grad_seg_norms_segments_per_launch(void);
+size_t odvae_grad_seg_norms_workspace_bytes(const int64_t* len, int n_seg);
+int odvae_grad_seg_norms_f32(const float* g, int64_t n, const int64_t* off, const int64_t* len, const unsigned char* counts, int n_seg,
+                             int kind, double p, float* out, void* workspace, size_t workspace_bytes, void* stream);
 /* Gradient accumulation (lightning.trainer.accumulate_grad_batches): arena[dst_off[i] + j] += src[i][j], j < numel[i], for `count` disjoint
  * segments in ceil(count / K) launches, K = odvae_grad_accumulate_segments_per_launch().  dst_off / numel are host arrays, src a host array
  * of device pointers; the table travels in the kernel arguments (no copy, no allocation, no host wait).  One f32 rounding per element, no
