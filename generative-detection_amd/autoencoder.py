@@ -20,6 +20,7 @@ from .latent_noise import CallCounter, make_draw, with_stream
 from .lightning import LightningModule
 from .modules import Conv1x1, Decoder, Encoder
 from .optim import make_adam
+from .quantize import VectorQuantizer
 
 POSE_6D_DIM = 4
 FILL_FACTOR_DIM = 1
@@ -46,9 +47,7 @@ class AutoencoderKL(LightningModule):
         device_noise: an extension (neither upstream nor the reference has it).  None = the noise is drawn with the host RNG and
         uploaded, as the reference does; an integer is the seed of the device-side draws (latent_noise.py): no host RNG, no upload."""
         super().__init__()
-        self.learn_logvar = learn_logvar
-        self.image_key = image_key
-        self.cond_key = cond_key
+        self._init_image_model(image_key, cond_key, learn_logvar, device_noise)
         self.encoder = Encoder(**ddconfig)
         self.decoder = Decoder(**ddconfig)
         self.loss = instantiate_from_config(lossconfig)
@@ -56,17 +55,29 @@ class AutoencoderKL(LightningModule):
         self.quant_conv = Conv1x1(2 * ddconfig["z_channels"], 2 * embed_dim)
         self.post_quant_conv = Conv1x1(embed_dim, ddconfig["z_channels"])
         self.embed_dim = embed_dim
+        self._init_colorize_and_monitor(colorize_nlabels, monitor)
+        if ckpt_path is not None:
+            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
+        self._init_ema(ema_decay)
+
+    def _init_image_model(self, image_key, cond_key=None, learn_logvar=False, device_noise=None):
+        """The state every method of this class reads, whatever the latent stage: AutoencoderKL and VQModel both start here, so a method
+        that comes to need a new attribute gets it in both."""
+        self.learn_logvar = learn_logvar
+        self.image_key = image_key
+        self.cond_key = cond_key
+        # test hook: {"posterior_eps", "samples_eps"} tensors replace the host RNG draws of forward and log_images
+        self.injected_noise = None
+        self._init_device_noise(device_noise)
+        self.use_ema = False
+        self._in_ema_scope = False
+
+    def _init_colorize_and_monitor(self, colorize_nlabels, monitor):
         if colorize_nlabels is not None:
             assert type(colorize_nlabels) == int
             self.register_buffer("colorize", torch.randn(3, colorize_nlabels, 1, 1))
         if monitor is not None:
             self.monitor = monitor
-        if ckpt_path is not None:
-            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
-        # test hook: {"posterior_eps", "samples_eps"} tensors replace the host RNG draws of forward and log_images
-        self.injected_noise = None
-        self._init_device_noise(device_noise)
-        self._init_ema(ema_decay)
 
     def _noise(self, key):
         noise = getattr(self, "injected_noise", None)
@@ -97,13 +108,14 @@ class AutoencoderKL(LightningModule):
         return ops.noise_fill(shape, with_stream(draw, stream), self.device, kind=kind, p=p, nhwc=len(shape) == 4)
 
     # ---- exponential moving average of the weights ([UPSTREAM] the stable-diffusion revision of this class; ema.LitEma) -------------
-    def _init_ema(self, ema_decay):
-        """Last in __init__ (after init_from_ckpt): the shadows start as clones of the weights the model starts with"""
-        self.use_ema = ema_decay is not None
+    def _init_ema(self, ema_decay, use_ema=None):
+        """Last in __init__ (after init_from_ckpt): the shadows start as clones of the weights the model starts with.  use_ema=True with
+        ema_decay None (VQModel): LitEma's own default decay, as upstream."""
+        self.use_ema = ema_decay is not None if use_ema is None else bool(use_ema)
         self._in_ema_scope = False
         if self.use_ema:
-            assert 0. < ema_decay < 1.
-            self.model_ema = LitEma(self, decay=ema_decay)
+            assert ema_decay is None or 0. < ema_decay < 1.
+            self.model_ema = LitEma(self) if ema_decay is None else LitEma(self, decay=ema_decay)
             print(f"Keeping EMAs of {len(list(self.model_ema.buffers()))}.")
 
     @contextlib.contextmanager
@@ -297,6 +309,147 @@ class AutoencoderKL(LightningModule):
 
 class Autoencoder(AutoencoderKL):
     """src/models/autoencoder.py:29-32"""
+
+
+class VQModel(AutoencoderKL):
+    """[UPSTREAM] ldm.models.autoencoder.VQModel: the family's second member (vq-f4, vq-f8, vq-f16; taming's VQGAN).  Encoder without the
+    doubled latent, quant_conv to embed_dim, VectorQuantizer, post_quant_conv, Decoder; loss VQLPIPSWithDiscriminator.  What it shares
+    with AutoencoderKL (get_input, get_last_layer, init_from_ckpt, to_rgb, ema_scope, on_train_batch_end, set_precision) is inherited;
+    under precision "bf16" the quantiser still runs in f32 (the encoder hands quant_conv an f32 latent)."""
+
+    def __init__(self, ddconfig, lossconfig, n_embed, embed_dim, ckpt_path=None, ignore_keys=[], image_key="image",
+                 colorize_nlabels=None, monitor=None, batch_resize_range=None, scheduler_config=None, lr_g_factor=1.0,
+                 remap=None, sane_index_shape=False, use_ema=False):
+        LightningModule.__init__(self)      # (AutoencoderKL.__init__ builds the doubled quant_conv and the KL loss)
+        if batch_resize_range is not None:
+            raise NotImplementedError("VQModel(batch_resize_range=%r): random batch resizing is not implemented" % (batch_resize_range,))
+        if scheduler_config is not None:
+            raise NotImplementedError("VQModel(scheduler_config=...): learning-rate schedulers are not implemented")
+        self._init_image_model(image_key)
+        self.embed_dim = embed_dim
+        self.n_embed = n_embed
+        self.encoder = Encoder(**ddconfig)
+        self.decoder = Decoder(**ddconfig)
+        self.loss = instantiate_from_config(lossconfig)
+        self.quantize = VectorQuantizer(n_embed, embed_dim, beta=0.25, remap=remap, sane_index_shape=sane_index_shape)
+        self.quant_conv = Conv1x1(ddconfig["z_channels"], embed_dim)
+        self.post_quant_conv = Conv1x1(embed_dim, ddconfig["z_channels"])
+        self._init_colorize_and_monitor(colorize_nlabels, monitor)
+        self.batch_resize_range = batch_resize_range
+        self.scheduler_config = scheduler_config
+        self.lr_g_factor = lr_g_factor
+        self._init_ema(None, use_ema=use_ema)      # upstream's default decay
+        if ckpt_path is not None:      # (upstream loads after the EMA is built: a checkpoint's model_ema.* keys land in it)
+            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
+
+    def encode(self, x):
+        h = self.quant_conv(self.encoder(x))
+        quant, emb_loss, info = self.quantize(h)
+        return quant, emb_loss, info
+
+    def encode_to_prequant(self, x):
+        return self.quant_conv(self.encoder(x))
+
+    def decode(self, quant):
+        return self.decoder(self.post_quant_conv(quant))
+
+    def decode_code(self, code_b):
+        """code_b int64 [N, H, W] -> images"""
+        n, h, w = code_b.shape
+        return self.decode(self.quantize.get_codebook_entry(code_b.reshape(-1), (n, h, w, self.embed_dim)))
+
+    def forward(self, input, return_pred_indices=False):
+        quant, diff, (_, _, ind) = self.encode(input)
+        dec = self.decode(quant)
+        if return_pred_indices:
+            return dec, diff, ind
+        return dec, diff
+
+    def training_step(self, batch, batch_idx, optimizer_idx):
+        x = self.get_input(batch, self.image_key)
+        xrec, qloss, ind = self(x, return_pred_indices=True)
+        if optimizer_idx == 0:
+            aeloss, log_dict_ae = self.loss(qloss, x, xrec, optimizer_idx, self.global_step, last_layer=self.get_last_layer(),
+                                            split="train", predicted_indices=ind)
+            self.log_dict(log_dict_ae, prog_bar=False, logger=True, on_step=True, on_epoch=True)
+            return aeloss
+        if optimizer_idx == 1:
+            discloss, log_dict_disc = self.loss(qloss, x, xrec, optimizer_idx, self.global_step, last_layer=self.get_last_layer(),
+                                                split="train")
+            self.log_dict(log_dict_disc, prog_bar=False, logger=True, on_step=True, on_epoch=True)
+            return discloss
+
+    def validation_step(self, batch, batch_idx):
+        log_dict = self._validation_step(batch, batch_idx)
+        if self.use_ema:
+            with self.ema_scope():
+                self._validation_step(batch, batch_idx, suffix="_ema")
+        return log_dict
+
+    def _validation_step(self, batch, batch_idx, suffix=""):
+        x = self.get_input(batch, self.image_key)
+        xrec, qloss, ind = self(x, return_pred_indices=True)
+        aeloss, log_dict_ae = self.loss(qloss, x, xrec, 0, self.global_step, last_layer=self.get_last_layer(), split="val" + suffix,
+                                        predicted_indices=ind)
+        discloss, log_dict_disc = self.loss(qloss, x, xrec, 1, self.global_step, last_layer=self.get_last_layer(), split="val" + suffix,
+                                            predicted_indices=ind)
+        rec_loss = log_dict_ae[f"val{suffix}/rec_loss"]
+        self.log(f"val{suffix}/rec_loss", rec_loss, prog_bar=True, logger=True, on_step=False, on_epoch=True, sync_dist=True)
+        self.log(f"val{suffix}/aeloss", aeloss, prog_bar=True, logger=True, on_step=False, on_epoch=True, sync_dist=True)
+        del log_dict_ae[f"val{suffix}/rec_loss"]
+        self.log_dict(log_dict_ae)
+        self.log_dict(log_dict_disc)
+        return self.log_dict
+
+    def configure_optimizers(self):
+        lr_d = self.learning_rate
+        lr_g = self.lr_g_factor * self.learning_rate
+        print("lr_d", lr_d)
+        print("lr_g", lr_g)
+        opt_ae = make_adam(list(self.encoder.parameters()) + list(self.decoder.parameters()) + list(self.quantize.parameters())
+                           + list(self.quant_conv.parameters()) + list(self.post_quant_conv.parameters()), lr=lr_g, betas=(0.5, 0.9))
+        opt_disc = make_adam(self.loss.discriminator.parameters(), lr=lr_d, betas=(0.5, 0.9))
+        return [opt_ae, opt_disc], []
+
+    @torch.no_grad()
+    def log_images(self, batch, only_inputs=False, plot_ema=False, **kwargs):
+        log = dict()
+        x = self.get_input(batch, self.image_key)
+        if only_inputs:
+            log["inputs"] = x
+            return log
+        xrec, _ = self(x)
+        x_in = x
+        if x.shape[1] > 3:      # more than three channels (label maps): both sides go through the fixed `colorize` projection
+            assert xrec.shape[1] > 3
+            x, xrec = self.to_rgb(x), self.to_rgb(xrec)
+        log["inputs"] = x
+        log["reconstructions"] = xrec
+        if plot_ema:
+            with self.ema_scope():
+                xrec_ema, _ = self(x_in)
+                if x_in.shape[1] > 3:
+                    xrec_ema = self.to_rgb(xrec_ema)
+                log["reconstructions_ema"] = xrec_ema
+        return log
+
+
+class VQModelInterface(VQModel):
+    """[UPSTREAM] ldm VQModelInterface: the face a latent-diffusion model sees -- encode stops before the quantiser, decode quantises."""
+
+    def __init__(self, embed_dim, *args, **kwargs):
+        super().__init__(embed_dim=embed_dim, *args, **kwargs)
+        self.embed_dim = embed_dim
+
+    def encode(self, x):
+        return self.quant_conv(self.encoder(x))
+
+    def decode(self, h, force_not_quantize=False):
+        if not force_not_quantize:
+            quant, emb_loss, info = self.quantize(h)
+        else:
+            quant = h
+        return self.decoder(self.post_quant_conv(quant))
 
 
 class PoseAutoencoder(AutoencoderKL):

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(HERE, "libodvae_hip.so")
 HIP_SOURCES = ["gemm_f32.hip", "gemm_f32_split.hip", "conv3x3_f32.hip", "conv3x3_wino_f32.hip", "conv3x3_wino4_f32.hip", "conv3x3_wgrad_f32.hip", "conv4x4_wgrad_f32.hip", "conv3x3_wgrad_wino_f32.hip", "groupnorm.hip", "elementwise.hip",
                "gan_f32.hip", "gan_norm.hip", "lpips_f32.hip", "patch_u8.hip", "pose_f32.hip", "linear_f32.hip",
                "conv_bf16.hip", "conv_wgrad_bf16.hip", "flash_attn_bf16.hip", "bf16_ops.hip", "lpips_bf16.hip",
-               "flash_attn_f32.hip", "linattn_f32.hip", "anomaly.hip", "latent_noise.hip"]
+               "flash_attn_f32.hip", "linattn_f32.hip", "anomaly.hip", "latent_noise.hip", "vq_f32.hip"]
 CXX_SOURCES = ["runtime.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", CSRC, "-I", INCLUDE]

@@ -42,7 +42,8 @@ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b;
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 constexpr int round_up(int a, int b) { return (a + b - 1) / b * b; }
 // blocks of 256 threads for a grid-stride loop over `items`
-static inline int grid_1d(int64_t items, int cap = 8192) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div64(items, 256), 1), cap); }
+constexpr int GRID_1D_CAP = 8192;
+static inline int grid_1d(int64_t items, int cap = GRID_1D_CAP) { return (int)std::min<int64_t>(std::max<int64_t>(ceil_div64(items, 256), 1), cap); }
 // blocks of the BatchNorm / ActNorm column statistics (gan_norm.hip): odvae_batchnorm_workspace_bytes sizes the workspace by it
 static inline int stat_blocks(int64_t rows) { return (int)std::min<int64_t>(std::max<int64_t>(rows / 128, 1), 1024); }
 

@@ -188,7 +188,6 @@ class LPIPSWithDiscriminator(nn.Module):
         else:
             assert self.disc_conditional
         cond = self._checked_cond(cond, reconstructions)
-        dev = inputs.device
         n, c, h, w = inputs.shape
         chw = float(c * h * w)
         rec_sums = ops.l1_masked_sum(inputs, reconstructions, None)      # per-sample sums of |x - x_rec|
@@ -199,7 +198,36 @@ class LPIPSWithDiscriminator(nn.Module):
         nll_loss, weighted_nll_loss = self._plain_nll(rec_sums, chw, weights)
         rec_mean = rec_sums.detach().sum() / (n * chw)
         kl_loss = torch.sum(posteriors.kl()) / n
+        g_loss, d_weight, one_pass = self._generator_gan_terms(nll_loss, reconstructions, cond, last_layer, weights)
+        disc_factor = adopt_weight(self.disc_factor, global_step, threshold=self.discriminator_iter_start)
 
+        if one_pass is None:
+            loss = weighted_nll_loss + self.kl_weight * kl_loss + d_weight * disc_factor * g_loss
+        else:
+            # the reconstruction-dependent terms enter by VALUE (same expression, same order of additions) and their gradient through
+            # `surrogate`, whose derivative w.r.t. the reconstruction is d nll / d x_rec + d_weight * disc_factor * d g_loss / d x_rec; the
+            # value added is an exact 0.  logvar keeps its gradient through the same trick on the per-sample sums.
+            loss = weighted_nll_loss.detach() + self.kl_weight * kl_loss + d_weight * disc_factor * g_loss.detach()
+            grad_at_rec = (one_pass[0] + (d_weight * disc_factor) * one_pass[1]).detach()
+            surrogate = (reconstructions * grad_at_rec).sum()
+            nll_lv = self._plain_nll(rec_sums.detach(), chw)[0]
+            loss = loss + (surrogate - surrogate.detach()) + (nll_lv - nll_lv.detach())
+
+        log = {"{}/total_loss".format(split): loss.clone().detach().mean(),
+               "{}/logvar".format(split): self.logvar.detach(),
+               "{}/kl_loss".format(split): kl_loss.detach().mean(),
+               "{}/nll_loss".format(split): nll_loss.detach().mean(),
+               "{}/rec_loss".format(split): rec_mean,
+               "{}/d_weight".format(split): d_weight.detach(),
+               "{}/disc_factor".format(split): torch.tensor(disc_factor),
+               "{}/g_loss".format(split): g_loss.detach().mean()}
+        return loss, log
+
+    def _generator_gan_terms(self, nll_loss, reconstructions, cond, last_layer, weights=None):
+        """(g_loss, d_weight, one_pass) of the generator phase: g_loss = -mean D(x_rec) (or the disc_factor == 0 shortcut), the adaptive
+        weight, and (g_nll, g_g) when the main backward is to start from the combined gradient at the reconstruction (else None).
+        Shared by LPIPSWithDiscriminator and VQLPIPSWithDiscriminator."""
+        dev = reconstructions.device
         if self.disc_factor > 0.0:
             g_loss = -ops.gan_logit_terms(None, self.discriminator(ops.cat_mask(reconstructions, None, cond)))[1]
         elif self.log_exact_g_loss or (self.discriminator.training and self.discriminator.actnorm_uninitialized()):
@@ -230,29 +258,7 @@ class LPIPSWithDiscriminator(nn.Module):
                     d_weight = torch.zeros((), device=dev)
         else:
             d_weight = torch.zeros((), device=dev)
-        disc_factor = adopt_weight(self.disc_factor, global_step, threshold=self.discriminator_iter_start)
-
-        if one_pass is None:
-            loss = weighted_nll_loss + self.kl_weight * kl_loss + d_weight * disc_factor * g_loss
-        else:
-            # the reconstruction-dependent terms enter by VALUE (same expression, same order of additions) and their gradient through
-            # `surrogate`, whose derivative w.r.t. the reconstruction is d nll / d x_rec + d_weight * disc_factor * d g_loss / d x_rec; the
-            # value added is an exact 0.  logvar keeps its gradient through the same trick on the per-sample sums.
-            loss = weighted_nll_loss.detach() + self.kl_weight * kl_loss + d_weight * disc_factor * g_loss.detach()
-            grad_at_rec = (one_pass[0] + (d_weight * disc_factor) * one_pass[1]).detach()
-            surrogate = (reconstructions * grad_at_rec).sum()
-            nll_lv = self._plain_nll(rec_sums.detach(), chw)[0]
-            loss = loss + (surrogate - surrogate.detach()) + (nll_lv - nll_lv.detach())
-
-        log = {"{}/total_loss".format(split): loss.clone().detach().mean(),
-               "{}/logvar".format(split): self.logvar.detach(),
-               "{}/kl_loss".format(split): kl_loss.detach().mean(),
-               "{}/nll_loss".format(split): nll_loss.detach().mean(),
-               "{}/rec_loss".format(split): rec_mean,
-               "{}/d_weight".format(split): d_weight.detach(),
-               "{}/disc_factor".format(split): torch.tensor(disc_factor),
-               "{}/g_loss".format(split): g_loss.detach().mean()}
-        return loss, log
+        return g_loss, d_weight, one_pass
 
     def _plain_discriminator_phase(self, inputs, reconstructions, global_step, cond, split):
         """optimizer_idx == 1: hinge / vanilla loss of the discriminator on the target and the detached reconstruction; the two loss terms
@@ -271,6 +277,86 @@ class LPIPSWithDiscriminator(nn.Module):
                "{}/logits_real".format(split): terms[0].detach(),
                "{}/logits_fake".format(split): terms[1].detach()}
         return d_loss, log
+
+
+class VQLPIPSWithDiscriminator(LPIPSWithDiscriminator):
+    """[UPSTREAM] ldm.modules.losses.vqperceptual.VQLPIPSWithDiscriminator (a superset of taming's): the loss of VQModel.  No logvar and
+    no KL term: nll_loss = mean(|x - x_rec| + perceptual_weight * p_loss), plus the adaptive GAN term and codebook_weight times the
+    quantiser's loss.  The GAN terms, the one-pass adaptive weight, the disc_factor == 0 shortcut and the discriminator phase are
+    LPIPSWithDiscriminator's own code."""
+
+    def __init__(self, disc_start, codebook_weight=1.0, pixelloss_weight=1.0, disc_num_layers=3, disc_in_channels=3, disc_factor=1.0,
+                 disc_weight=1.0, perceptual_weight=1.0, use_actnorm=False, disc_conditional=False, disc_ndf=64, disc_loss="hinge",
+                 n_classes=None, perceptual_loss="lpips", pixel_loss="l1"):
+        nn.Module.__init__(self)      # (LPIPSWithDiscriminator.__init__ would add the logvar parameter, which this loss does not have)
+        assert disc_loss in ["hinge", "vanilla"]
+        if perceptual_loss != "lpips":
+            raise NotImplementedError("VQLPIPSWithDiscriminator(perceptual_loss=%r): only 'lpips' is implemented" % (perceptual_loss,))
+        if pixel_loss != "l1":
+            raise NotImplementedError("VQLPIPSWithDiscriminator(pixel_loss=%r): only 'l1' is implemented" % (pixel_loss,))
+        self.codebook_weight = codebook_weight
+        self.pixel_weight = pixelloss_weight
+        self.perceptual_loss = LPIPSStyle().eval()
+        self.perceptual_weight = perceptual_weight
+        self.discriminator = NLayerDiscriminator(input_nc=disc_in_channels, n_layers=disc_num_layers, use_actnorm=use_actnorm,
+                                                 ndf=disc_ndf).apply(weights_init)
+        self.discriminator_iter_start = disc_start
+        self.disc_loss = hinge_d_loss if disc_loss == "hinge" else vanilla_d_loss
+        print(f"VQLPIPSWithDiscriminator running with {disc_loss} loss.")
+        self.disc_factor = disc_factor
+        self.discriminator_weight = disc_weight
+        self.disc_conditional = disc_conditional
+        self.n_classes = n_classes
+        self.log_exact_g_loss = False      # (as in LPIPSWithDiscriminator: with disc_factor == 0, log the exact -mean D(x_rec) instead of 0)
+
+    def forward(self, codebook_loss, inputs, reconstructions, optimizer_idx, global_step, last_layer=None, cond=None, split="train",
+                predicted_indices=None):
+        if optimizer_idx == 1:
+            return self._plain_discriminator_phase(inputs, reconstructions, global_step, cond, split)
+        if optimizer_idx != 0:
+            return None
+        if cond is None:
+            assert not self.disc_conditional
+        else:
+            assert self.disc_conditional
+        cond = self._checked_cond(cond, reconstructions)
+        n, c, h, w = inputs.shape
+        chw = float(c * h * w)
+        rec_sums = ops.l1_masked_sum(inputs, reconstructions, None)      # per-sample sums of |x - x_rec|
+        if self.perceptual_weight > 0:
+            self._check_perceptual_weights()
+            p_loss = self.perceptual_loss(inputs, reconstructions)
+            rec_sums = rec_sums + self.perceptual_weight * p_loss.reshape(n) * chw
+            p_mean = p_loss.detach().mean()
+        else:
+            p_mean = torch.zeros((), device=inputs.device)
+        nll_loss = torch.sum(rec_sums) / (n * chw)      # mean(rec_loss): no logvar here
+        g_loss, d_weight, one_pass = self._generator_gan_terms(nll_loss, reconstructions, cond, last_layer)
+        disc_factor = adopt_weight(self.disc_factor, global_step, threshold=self.discriminator_iter_start)
+        quant_loss = codebook_loss.mean()
+        if one_pass is None:
+            loss = nll_loss + d_weight * disc_factor * g_loss + self.codebook_weight * quant_loss
+        else:      # (the surrogate of LPIPSWithDiscriminator.forward: values by value, the gradient at the reconstruction in one traversal)
+            loss = nll_loss.detach() + d_weight * disc_factor * g_loss.detach() + self.codebook_weight * quant_loss
+            grad_at_rec = (one_pass[0] + (d_weight * disc_factor) * one_pass[1]).detach()
+            surrogate = (reconstructions * grad_at_rec).sum()
+            loss = loss + (surrogate - surrogate.detach())
+        log = {"{}/total_loss".format(split): loss.clone().detach().mean(),
+               "{}/quant_loss".format(split): codebook_loss.detach().mean(),
+               "{}/nll_loss".format(split): nll_loss.detach().mean(),
+               "{}/rec_loss".format(split): nll_loss.detach().mean(),
+               "{}/p_loss".format(split): p_mean,
+               "{}/d_weight".format(split): d_weight.detach(),
+               "{}/disc_factor".format(split): torch.tensor(disc_factor),
+               "{}/g_loss".format(split): g_loss.detach().mean()}
+        if predicted_indices is not None and self.n_classes is not None:
+            # DEVIATION: upstream asserts n_classes whenever indices arrive (and VQModel always sends them); here the two figures are logged
+            # when n_classes is set and skipped otherwise
+            with torch.no_grad():
+                _, perplexity, cluster_usage = ops.vq_usage(predicted_indices, self.n_classes)
+            log["{}/perplexity".format(split)] = perplexity
+            log["{}/cluster_usage".format(split)] = cluster_usage
+        return loss, log
 
 
 class PoseLoss(LPIPSWithDiscriminator):

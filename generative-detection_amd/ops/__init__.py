@@ -130,3 +130,5 @@ from .elementwise import (  # noqa: E402
 from .patchgan import (  # noqa: E402
     _conv4x4_out, _Conv4x4, _conv4x4_i_raw, _check_pack_current, _Conv4x4I, conv4x4, _BatchNormLReLU, batchnorm_lrelu, _ActNormLReLU, actnorm_init, actnorm_lrelu, _LeakyReLU,
     leaky_relu, _GanLogitTerms, gan_logit_terms, _conv4x4_b_raw, _Conv4x4B, conv4x4_bf16, _gather_f64, _SyncBatchNormLReLU, _sync_group)
+from .vq import (  # noqa: E402
+    VQ_PLAN_FIELDS, vq_plan, _row_strides, _rows_view, _dense, _codebook, _VqQuantize, vq_quantize, vq_gather, vq_usage)

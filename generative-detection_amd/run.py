@@ -107,7 +107,17 @@ def main(argv=None):
         losses = trainer.training_batch(batch, step, last_in_epoch=step == opt.steps - 1)   # (closes an accumulation window)
         print("batch %d  global_step %d  aeloss %.4f  discloss %.4f  lr %.2e" %
               (step, model.global_step, losses[0].item(), losses[1].item(), model.learning_rate), flush=True)
-    if getattr(model, "use_ema", False):     # model.params.ema_decay: one validation batch under the trained and the averaged weights
+    if hasattr(model, "quantize"):     # VQModel: one validation batch (and the same under the averaged weights with model.params.use_ema)
+        metrics = trainer.validate([make(opt.steps)])
+        line = "validation  val/rec_loss %.4f  val/aeloss %.4f  val/quant_loss %.4f" % (
+            metrics["val/rec_loss"].item(), metrics["val/aeloss"].item(), metrics["val/quant_loss"].item())
+        if getattr(model, "use_ema", False):
+            line += "  val_ema/rec_loss %.4f" % metrics["val_ema/rec_loss"].item()
+        print(line, flush=True)
+        ckpt = opt.checkpoint or (os.path.join(opt.logdir, "checkpoints", "last.ckpt") if opt.logdir else None)
+        if ckpt:
+            print("checkpoint  %s" % trainer.save_checkpoint(ckpt), flush=True)
+    elif getattr(model, "use_ema", False):     # model.params.ema_decay: one validation batch under the trained and the averaged weights
         metrics = trainer.validate([make(opt.steps)])
         print("validation  val/rec_loss %.4f  val_ema/rec_loss %.4f  ema updates %d" %
               (metrics["val/rec_loss"].item(), metrics["val_ema/rec_loss"].item(), int(model.model_ema.num_updates)), flush=True)

@@ -780,6 +780,42 @@ typedef struct { const void* ptr; int64_t numel; int32_t dtype; int32_t output_i
 int odvae_anomaly_scan(const OdvaeAnomalyTensor* tensors /* host */, int n, int64_t node_seq, int mode, uint64_t* record, void* stream);
 int odvae_anomaly_reset(uint64_t* record, void* stream);
 
+/* ---- vq_f32.hip: the vector quantiser of ldm's VQModel ([UPSTREAM] taming VectorQuantizer2), f32 -------------------------------
+ * A row m = (n, p), M = N * HW rows, is one position of a logical [N][D][H][W] tensor addressed by ELEMENT strides (sn, sc, sp):
+ * element (n, d, p) is at n sn + d sc + p sp.  NCHW is (D HW, HW, 1); the NHWC memory the conv kernels write is (HW D, 1, D): neither
+ * needs a permute copy.  E is the codebook [K][D], row-major.  idx is int64 [M].
+ * Sizes: 1 <= D <= 512, 1 <= K <= 2^20, 1 <= M < 2^31, strides sc, sp >= 1, sn >= 0; anything else is ODVAE_ERR_ARG (no launch).
+ * Nothing of size M x K is ever written.  No float atomics anywhere: two runs give the same bits, dE included. */
+/* out[16]: 0 tile_rows, 1 chunk (codes per LDS chunk), 2 slab depth, 3 slabs per row, 4 nsplit (codebook splits across workgroups),
+ * 5 codes_per_split, 6 search grid x, 7 its cap (row tiles beyond it: grid-stride loop), 8 finish workgroups, 9 their cap, 10 codes per
+ * sort workgroup, 11 sort code ranges, 12 sort row segments, 13 rows per segment, 14 cap of the streaming grids (256 rows each), 15 0.
+ * Host only. */
+int odvae_vq_plan(int64_t M, int K, int D, int* out);
+size_t odvae_vq_assign_workspace_bytes(int64_t M, int K, int D);
+/* idx[m] = argmin_k |e_k|^2 - 2 z_m . e_k: `s < best` from (+inf, 0) over ascending k, so ties go to the lowest k, a row holding NaN
+ * gets 0 and every index written is in [0, K).  zq[m] = E[idx[m]] (strides q_*).  The workspace (16-byte aligned) keeps the f64 partial
+ * sums of (z_q - z)^2 for odvae_vq_loss_finalize, which must see it untouched. */
+int odvae_vq_assign_f32(const float* z, int64_t z_sn, int64_t z_sc, int64_t z_sp, int64_t N, int64_t HW, int D, const float* E, int K,
+                        int64_t* idx, float* zq, int64_t q_sn, int64_t q_sc, int64_t q_sp, void* workspace, size_t workspace_bytes,
+                        void* stream);
+/* *loss = (1 + beta) sum (z_q - z)^2 / (M D) from the workspace of the odvae_vq_assign_f32 call with the same (M, K, D): differences,
+ * squares and sums in f64 in a fixed order, one rounding to f32 */
+int odvae_vq_loss_finalize(const void* workspace, size_t workspace_bytes, int64_t M, int K, int D, float beta, float* loss, void* stream);
+size_t odvae_vq_backward_workspace_bytes(int64_t M, int K, int D);
+/* dz = gq + gl (2 c_z / (M D)) (z - E[idx]) and dE[k] = gl (2 c_e / (M D)) sum_{idx[m] = k} (e_k - z_m) (0 for unused codes);
+ * legacy != 0: c_z = 1, c_e = beta; legacy == 0: c_z = beta, c_e = 1.  z, gq and dz share the strides; gl is a DEVICE scalar.  gq NULL
+ * and gl NULL count as zero; dz NULL or dE NULL skips that half (the workspace is needed for dE only).  f64 arithmetic, one rounding
+ * per output.  Indices outside [0, K) are clamped for dz and own no row of dE. */
+int odvae_vq_backward_f32(const float* z, const float* gq, float* dz, int64_t sn, int64_t sc, int64_t sp, int64_t N, int64_t HW, int D,
+                          const float* E, int K, const int64_t* idx, const float* gl, float beta, int legacy, float* dE, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* out[m] = E[clamp(idx[m], 0, K - 1)]: an out-of-range index is CLAMPED, never read past E */
+int odvae_vq_gather_f32(const int64_t* idx, int64_t N, int64_t HW, const float* E, int K, int D, float* out, int64_t o_sn, int64_t o_sc,
+                        int64_t o_sp, void* stream);
+/* counts int32 [K] (zeroed here; indices outside [0, K) are not counted); out[0] = exp(-sum p log(p + 1e-10)), p = count / M;
+ * out[1] = number of codes with count > 0.  Integer atomics for the counts, f64 in a fixed order for the rest */
+int odvae_vq_usage(const int64_t* idx, int64_t M, int K, int* counts, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
